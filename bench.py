@@ -1,8 +1,11 @@
 #!/usr/bin/env python
 """bench.py -- BASELINE.json's metric on MI355X: images/sec at 50 steps for SDXL H=1024 x W=2048 (configs[2]:
-view_batch_size=16, resampling_steps=7), plus per-view UNet ms, roofline figures and a CPU baseline.
+view_batch_size=16, resampling_steps=7); with --full also roofline figures, per-kernel timings, the other modes and
+layouts, the live fp32 leg and a CPU baseline.
 
     python bench.py --gpus 1 --steps K --warmup W          (N>1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus 1 --steps K --warmup W --full   (everything beyond the headline figure, after the timed region)
+    python bench.py ... --dump-outputs DIR                 (the last timed image's latents / pixels as DIR/*.npy)
 
 One "step" = ONE full image through the hot path: generate_image() = 50 denoising timesteps of the patched
 global/local loop (1294 SDXL UNet forward-samples, ~8.75 PFLOP) + the VAE decode.  Inputs (text embeddings, weights)
@@ -223,6 +226,24 @@ def unet_kernel_profile(pipe, wl, T, in_flight=1, shard=1):
     return res
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, seed, arrays):
+    """--dump-outputs: write ``arrays`` ({name: tensor or None}) as ``out_dir/<name>.npy`` in float32 -> what was written.
+    Inputs are fixed by the arguments (seeded weights, fixed prompts, image seeds 0 .. steps-1), so two builds of the
+    project run with the same arguments can be compared output for output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items() if v is not None}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return {"dir": out_dir, "seed": seed, "arrays": {k: list(a.shape) for k, a in host.items()}, "dtype": "float32"}
+
+
 def load_profile_json(name):
     try:
         return json.load(open(os.path.join(ROOT, "profiles", name)))
@@ -281,6 +302,14 @@ def main():
     ap.add_argument("--force-exchange", action="store_true",
                     help="N = 1 only: initialise RCCL with one rank and send every sharded batch through the all-gather path "
                          "(what a 1-GPU box can exercise of the multi-GPU exchange)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: per-kernel timing and roofline figures, the other "
+                         "in-flight / background-cache modes and layouts (extras), the live fp32 leg (--fp32-leg auto), the CPU "
+                         "baseline, the 16-bit parity leg and the tolerance statement.  Off: a plain run sets up, warms up, "
+                         "times the --steps images and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what the timed path computed for its last image (the seed of the last "
+                         "timed step) as DIR/latents.npy and DIR/images.npy (float32); inputs are fixed by the arguments")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -366,7 +395,8 @@ def main():
         cond_img = torch.cat([yy, xx, 0.5 * (yy + xx)], dim=1).contiguous()
         kw.update(condition_image=cond_img, controlnet_conditioning_scale=cn_scale)
     prompt, negative = "An astronaut riding a corgi on the moon", "blurry, ugly, poorly drawn, deformed"
-    state = {"imgs": None, "latency": None, "keep_latents": None}
+    # keep_imgs: {seed: decoded images} of the one seed --dump-outputs writes (None: keep nothing)
+    state = {"imgs": None, "latency": None, "keep_latents": None, "keep_imgs": None}
 
     def run_images(p, seeds, in_flight):
         """``len(seeds)`` images through pipeline ``p`` (latents + decode); all ranks of p's shard group call this with
@@ -379,6 +409,8 @@ def main():
                                                     progress=lambda it: it, **kw)
                 if state.get("keep_latents") is not None:    # (512 KiB device copy, asynchronous: the fp32 leg compares against it)
                     state["keep_latents"][sd_] = p.last_latents.detach().clone()
+                if state.get("keep_imgs") is not None and sd_ in state["keep_imgs"]:
+                    state["keep_imgs"][sd_] = state["imgs"]
             return
         jobs = [dict(prompts=prompt, negative_prompts=negative, seed=sd_, condition_image=cond_img) for sd_ in seeds]
 
@@ -392,6 +424,8 @@ def main():
             if p.sharder.world_size == 1 or wl["tiled"] or j % p.sharder.world_size == p.sharder.rank:
                 state["imgs"] = torch.cat([dec(z[i:i + 1]) for i in range(len(z))])
                 decoded_here.add(j)
+                if state.get("keep_imgs") is not None and seeds[j] in state["keep_imgs"]:
+                    state["keep_imgs"][seeds[j]] = state["imgs"]
 
         kwi = {k: v for k, v in kw.items() if k != "condition_image"}
         p.generate_latents_interleaved(jobs, in_flight=in_flight, on_done=on_done, **kwi)
@@ -432,12 +466,20 @@ def main():
         # those batch shapes now, not inside the timed region
         tail = len(my_seeds(0, n_timed, n_groups, group_id)) % m
         run_images(pipe, [1900 + i for i in range(tail)], m)
-    timing = (not args.no_kernel_timing)
+    # per-kernel timing brackets every glue launch of the timed region with HIP events: a --full figure, never the plain run's
+    timing = args.full and not args.no_kernel_timing
+    want_fp32 = args.fp32_leg == "on" or (args.fp32_leg == "auto" and args.full and args.workload == "sdxl_1024x2048"
+                                          and args.timesteps == 50 and n_timed >= 2 and not args.no_extras)
+    want_fp32 = want_fp32 and world == 1 and dtype != torch.float32 and not args.small
     if timing:
         fence()
         ops.TIMER.start()
-    if world == 1:
+    mine = my_seeds(0, n_timed, n_groups, group_id)
+    dump_seed = mine[-1] if (args.dump_outputs and mine) else None   # the last timed step of this rank's group
+    if want_fp32 or dump_seed is not None:
         state["keep_latents"] = {}
+    if dump_seed is not None:
+        state["keep_imgs"] = {dump_seed: None}
     elapsed = timed(pipe, 0, n_timed, m, n_groups, group_id)
     ktimes = ops.TIMER.stop() if timing else {}
     lat_timed = state["latency"]
@@ -445,7 +487,15 @@ def main():
     n_cmp = max(1, min(args.fp32_leg_seeds, n_timed))
     z16_last = ({sd_: z.detach().clone() for sd_, z in (state["keep_latents"] or {}).items() if sd_ >= n_timed - n_cmp and z is not None}
                 or None)
-    state["keep_latents"] = None
+    dumped = None
+    if dump_seed is not None and rank == 0:
+        z_dump = (state["keep_latents"] or {}).get(dump_seed)
+        img_dump = state["keep_imgs"].get(dump_seed)
+        if img_dump is None and z_dump is not None and not wl["tiled"]:
+            # another rank of the group decoded this image in the timed region; decode_latents is rank-local and deterministic
+            img_dump = pipe.decode_latents(z_dump)
+        dumped = dump_outputs(args.dump_outputs, dump_seed, {"latents": z_dump, "images": img_dump})
+    state["keep_latents"], state["keep_imgs"] = None, None
     finite = bool(torch.isfinite(state["imgs"]).all()) if state["imgs"] is not None else True
     phases = pipe.phase_times()
     host_ms = {k: round(1e3 * v, 1) for k, v in pipe.host_s.items()}
@@ -454,7 +504,7 @@ def main():
 
     # ---- informative extras, all OUTSIDE the timed region and never `value` ------------------------------------------
     layouts, cached_s, two_s, extras_error = {}, None, None, None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         try:  # an informative extra must never cost the run its headline line
             if world == 1 and not args.cache_backgrounds:
                 pipe.cache_backgrounds = True
@@ -490,9 +540,7 @@ def main():
 
     # ---- north_star's tolerance, measured live: the same workload, same seed, fp32 UNet -----------------
     fp32_live = None
-    want_fp32 = args.fp32_leg == "on" or (args.fp32_leg == "auto" and args.workload == "sdxl_1024x2048" and args.timesteps == 50
-                                          and n_timed >= 2 and not args.no_extras)
-    if want_fp32 and world == 1 and dtype != torch.float32 and not args.small and z16_last is not None:
+    if want_fp32 and z16_last is not None:
         try:
             fp32_live = fp32_same_workload(make_pipe, pipe, kw, prompt, negative, wl, z16_last, args.dtype)
         except Exception as e:  # noqa: BLE001 -- never costs the run its headline line
@@ -508,7 +556,7 @@ def main():
         V = geometry.ViewPlan(Hl, Wl, vc["window_size"], vc["stride"], vc["context_size"]).V
         T, R = args.timesteps, wl["R"]
         fs = forward_samples(T, R, V)
-        flops_sample = 0.0 if args.small else unet_flops_per_sample(fam, dtype, controlnet=cn_scale is not None)
+        flops_sample = 0.0 if (args.small or not args.full) else unet_flops_per_sample(fam, dtype, controlnet=cn_scale is not None)
         img_per_s = n_timed / elapsed
         sec_per_img = elapsed / n_timed               # wall time per image of the whole job (all N GPUs)
         e2e_tf = fs * flops_sample / sec_per_img / 1e12 / world
@@ -595,29 +643,35 @@ def main():
             "latency_note": (f"{m} image(s) in flight per shard group: the value above is THROUGHPUT (images completed per "
                              "second); one image takes latency_s_per_image from its first kernel to its decoded pixels"),
             "rccl": rccl,
-            "tolerance": tolerance_statement(args.dtype, fp32_live),
             "per_view_unet_ms": round(per_view_ms, 3),
             "finite_output": finite,
             "graphs": graph_stats,
             "rows_computed_over_rows_total_rank0": list(rows_share),
-            "layouts": layouts,
-            "extras": {"images_per_s_with_background_cache": None if cached_s is None else round(1.0 / cached_s, 5),
-                       ("images_per_s_one_image_in_flight" if m > 1 else "images_per_s_two_images_in_flight"):
-                           None if two_s is None else round(1.0 / two_s, 5),
-                       "error": extras_error,
-                       "note": "other modes measured after the timed region, never the headline; the background-cache figure is at ONE image in "
-                               "flight: compare it with images_per_s_one_image_in_flight"},
             "phase_ms_last_image": {k: round(v, 1) for k, v in phases.items()},
             "host_ms_last_image": host_ms,
-            "roofline": roof,
-            "roofline_e2e": {"bound": "mfma", "achieved": round(e2e_tf, 1), "peak": e2e_peak, "unit": "TFLOP/s",
-                             "frac": round(e2e_tf / e2e_peak, 4),
-                             "flops_per_forward_sample": flops_sample, "forward_samples": fs,
-                             "note": "UNet FLOPs only (VAE / glue excluded from the numerator), per GPU"},
-            "unet_kernels": unet_k,
-            "glue_kernels": kern,
         }
-        if not args.no_cpu_baseline and world == 1 and not args.small:
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        if args.full or fp32_live is not None:
+            out["tolerance"] = tolerance_statement(args.dtype, fp32_live)
+        if args.full:
+            out.update({
+                "layouts": layouts,
+                "extras": {"images_per_s_with_background_cache": None if cached_s is None else round(1.0 / cached_s, 5),
+                           ("images_per_s_one_image_in_flight" if m > 1 else "images_per_s_two_images_in_flight"):
+                               None if two_s is None else round(1.0 / two_s, 5),
+                           "error": extras_error,
+                           "note": "other modes measured after the timed region, never the headline; the background-cache figure is at ONE image in "
+                                   "flight: compare it with images_per_s_one_image_in_flight"},
+                "roofline": roof,
+                "roofline_e2e": {"bound": "mfma", "achieved": round(e2e_tf, 1), "peak": e2e_peak, "unit": "TFLOP/s",
+                                 "frac": round(e2e_tf / e2e_peak, 4),
+                                 "flops_per_forward_sample": flops_sample, "forward_samples": fs,
+                                 "note": "UNet FLOPs only (VAE / glue excluded from the numerator), per GPU"},
+                "unet_kernels": unet_k,
+                "glue_kernels": kern,
+            })
+        if args.full and not args.no_cpu_baseline and world == 1 and not args.small:
             out["cpu_baseline"] = guarded(cpu_baseline, pipe, wl, T, fs, V, args.cpu_baseline)
             full = (load_profile_json("r2_cpu_baseline_full.json") or {}).get("cpu_baseline")
             if isinstance(out["cpu_baseline"], dict) and "error" not in out["cpu_baseline"] and full and \

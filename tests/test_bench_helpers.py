@@ -41,6 +41,27 @@ def test_bench_and_cli_help_run_without_gpu():
         assert out.returncode == 0 and "--" in out.stdout, out.stderr
 
 
+def test_bench_full_and_dump_outputs_options(tmp_path):
+    """--full (everything beyond the headline figure) and --dump-outputs DIR exist; the dump writes float32 .npy files per
+    array, skips arrays a rank does not hold, and refuses more than 64 MB."""
+    import os
+    import numpy as np
+    import pytest
+    import torch
+    out = subprocess.run([sys.executable, "bench.py", "--help"], capture_output=True, text=True, cwd=bench.ROOT, timeout=300)
+    assert out.returncode == 0 and "--full" in out.stdout and "--dump-outputs" in out.stdout, out.stderr
+    z = torch.randn(1, 4, 8, 16, dtype=torch.float64)
+    img = torch.rand(1, 3, 64, 128, dtype=torch.float16)
+    rec = bench.dump_outputs(str(tmp_path / "d"), 7, {"latents": z, "images": img, "absent": None})
+    assert rec["seed"] == 7 and rec["arrays"] == {"latents": [1, 4, 8, 16], "images": [1, 3, 64, 128]}
+    assert sorted(os.listdir(tmp_path / "d")) == ["images.npy", "latents.npy"]
+    a = np.load(tmp_path / "d" / "latents.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, z.float().numpy())
+    assert np.array_equal(np.load(tmp_path / "d" / "images.npy"), img.float().numpy())
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), 0, {"x": torch.empty(bench.DUMP_LIMIT_BYTES // 4 + 1)})
+
+
 def test_workloads_cover_every_baseline_config_and_controlnet_flops():
     import torch
     assert set(bench.WORKLOADS) == {"sdxl_1024x2048", "sd15_512x1024", "sdxl_2048x2048_tiled", "sdxl_1024x2048_controlnet"}

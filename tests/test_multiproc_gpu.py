@@ -108,7 +108,7 @@ def test_bench_multi_rank_rehearsal(flags):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), "bench.py", *flags, "--steps", "2", "--warmup", "1", "--small",
-           "--workload", "sd15_512x1024", "--timesteps", "3", "--no-cpu-baseline"]
+           "--workload", "sd15_512x1024", "--timesteps", "3", "--no-cpu-baseline", "--full"]
     # every rank's stdout / stderr goes to its OWN file (torchrun --redirects 3): a native abort of one rank keeps that rank's last words
     # instead of a tail of eight interleaved streams buried in MIOpen warnings (round 5 lost the cause of its one SIGABRT that way)
     import glob
