@@ -19,6 +19,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import ops      # (imports without the shared library: it is loaded at the first launch)
+
 
 # Fused HIP kernels inside the UNet (csrc/unet_kernels.hip): used for 16-bit CUDA activations; anything else (the fp32
 # VAE, the CPU-baseline copy of the UNet, odd shapes) takes the plain torch ops.  Toggle for A/B measurements.
@@ -35,13 +37,15 @@ FUSED_KERNELS = True
 CHANNELS_LAST = os.environ.get("ED_CHANNELS_LAST", "1") == "1"
 
 
+_HALF = (torch.bfloat16, torch.float16)
+
+
 def _fusable(x):
-    return FUSED_KERNELS and x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and x.is_contiguous()
+    return FUSED_KERNELS and x.is_cuda and x.dtype in _HALF and x.is_contiguous()
 
 
 def _fusable_nhwc(x):
-    return (FUSED_KERNELS and x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and x.dim() == 4
-            and not x.is_contiguous() and x.is_contiguous(memory_format=torch.channels_last))
+    return FUSED_KERNELS and x.is_cuda and x.dtype in _HALF and ops.is_nhwc(x)
 
 
 # ---- fp32 residual stream under a 16-bit model (round 6, ``UNet2DConditionModel.residual_fp32``) ---------------------------------------
@@ -53,31 +57,30 @@ def _fusable_nhwc(x):
 # up / down-sampling and shortcut convolutions after a cast; everything that WRITES it adds a 16-bit branch result to the fp32 stream.
 def _stream32(x, module_dtype):
     """is ``x`` an fp32 residual stream feeding a module whose parameters are 16-bit?"""
-    return x.dtype == torch.float32 and module_dtype in (torch.float16, torch.bfloat16)
+    return x.dtype == torch.float32 and module_dtype in _HALF
+
+
+def _derived(module, slot, params, build):
+    """``build()``, cached on ``module`` under ``slot`` and rebuilt when one of the source ``params`` is replaced (id: a fresh Parameter
+    the caching allocator placed at the freed address has the same data_ptr and version 0), moved, written in place or cast"""
+    key = tuple((id(p), p.data_ptr(), p._version, p.dtype, str(p.device)) for p in params)
+    cache = module.__dict__.setdefault("_derived", {})
+    hit = cache.get(slot)
+    if hit is None or hit[0] != key:
+        hit = cache[slot] = (key, build())
+    return hit[1]
 
 
 def _f32_params(norm):
-    """fp32 copies of a normalisation layer's (weight, bias), rebuilt when they change"""
+    """fp32 copies of a normalisation layer's (weight, bias)"""
     w, b = norm.weight, norm.bias
-    key = (id(w), w.data_ptr(), w._version, id(b), b._version)
-    hit = norm.__dict__.get("_p32")
-    if hit is None or hit[0] != key:
-        hit = (key, w.detach().float(), b.detach().float())
-        norm.__dict__["_p32"] = hit
-    return hit[1], hit[2]
+    return _derived(norm, "f32", (w, b), lambda: (w.detach().float(), b.detach().float()))
 
 
 def _f32_bias(mod):
-    """fp32 copy of a module's bias (None without one), rebuilt when it changes"""
+    """fp32 copy of a module's bias (None without one)"""
     b = mod.bias
-    if b is None:
-        return None
-    key = (id(b), b.data_ptr(), b._version)
-    hit = mod.__dict__.get("_b32")
-    if hit is None or hit[0] != key:
-        hit = (key, b.detach().float())
-        mod.__dict__["_b32"] = hit
-    return hit[1]
+    return None if b is None else _derived(mod, "bias32", (b,), lambda: b.detach().float())
 
 
 def group_norm_act(norm, x, silu=False, tokens=False, chan_bias=None, conv_bias=None):
@@ -85,58 +88,47 @@ def group_norm_act(norm, x, silu=False, tokens=False, chan_bias=None, conv_bias=
     bias of the (bias-free) convolution that produced x and the time-embedding add of ResnetBlock2D, folded into the
     kernel.  HIP: ed_groupnorm / ed_groupnorm_nhwc; torch otherwise."""
     N, C, H, W = x.shape
-    if _stream32(x, norm.weight.dtype):   # fp32 residual stream: statistics and affine in fp32, the result in the model dtype
-        dt = norm.weight.dtype
-        if conv_bias is not None:
-            x = x + conv_bias[None, :, None, None]
-        if chan_bias is not None:
-            x = x + chan_bias[:, :, None, None]
-        cpg32 = C // norm.num_groups
-        if (FUSED_KERNELS and x.is_cuda and C % 8 == 0 and cpg32 >= 8 and C <= 4096 and norm.num_groups <= 256
-                and not x.is_contiguous() and x.is_contiguous(memory_format=torch.channels_last)):
-            from . import ops      # HIP: ed_groupnorm_nhwc_s32 (fp32 stream in, model dtype out; the 16-bit kernel's three launches)
-            y = ops.groupnorm_nhwc_s32(x, norm.weight, norm.bias, norm.num_groups, norm.eps, silu=silu)
-            return y.permute(0, 2, 3, 1).reshape(N, H * W, C) if tokens else y
-        w32, b32 = _f32_params(norm)
-        y = F.group_norm(x, norm.num_groups, w32, b32, norm.eps)
-        if silu:
-            y = F.silu(y)
-        y = y.to(dt)
-        if CHANNELS_LAST and y.is_cuda:
-            y = y.contiguous(memory_format=torch.channels_last)
-        return y.permute(0, 2, 3, 1).reshape(N, H * W, C) if tokens else y
-    cpg = C // norm.num_groups
-    nhwc = _fusable_nhwc(x) and C % 8 == 0 and cpg >= 8
-    if (chan_bias is not None or conv_bias is not None) and not (
-            FUSED_TEMB_ADD and (nhwc or (_fusable(x) and (H * W) % 8 == 0 and not tokens))):
+    G = norm.num_groups
+    cpg = C // G
+    s32 = _stream32(x, norm.weight.dtype)
+    nhwc = not s32 and _fusable_nhwc(x) and C % 8 == 0 and cpg >= 8
+    if (chan_bias is not None or conv_bias is not None) and (
+            s32 or not (FUSED_TEMB_ADD and (nhwc or (_fusable(x) and (H * W) % 8 == 0 and not tokens)))):
+        # no kernel on this path folds the biases in
         if conv_bias is not None:
             x = x + conv_bias[None, :, None, None]
         if chan_bias is not None:
             x = x + chan_bias[:, :, None, None]
         chan_bias = conv_bias = None
-        nhwc = _fusable_nhwc(x) and C % 8 == 0 and cpg >= 8
-    if nhwc:
-        from . import ops
-        y = ops.groupnorm_nhwc(x, norm.weight, norm.bias, norm.num_groups, norm.eps, silu=silu,
-                               chan_bias=None if chan_bias is None else chan_bias.contiguous(), conv_bias=conv_bias)
+        nhwc = not s32 and _fusable_nhwc(x) and C % 8 == 0 and cpg >= 8
+    if s32 or nhwc:
+        if nhwc:
+            y = ops.groupnorm_nhwc(x, norm.weight, norm.bias, G, norm.eps, silu=silu,
+                                   chan_bias=None if chan_bias is None else chan_bias.contiguous(), conv_bias=conv_bias)
+        elif FUSED_KERNELS and x.is_cuda and C % 8 == 0 and cpg >= 8 and C <= 4096 and G <= 256 and ops.is_nhwc(x):
+            # HIP: ed_groupnorm_nhwc_s32 (fp32 stream in, model dtype out; the 16-bit kernel's three launches)
+            y = ops.groupnorm_nhwc_s32(x, norm.weight, norm.bias, G, norm.eps, silu=silu)
+        else:   # fp32 residual stream: statistics and affine in fp32, the result in the model dtype
+            y = F.group_norm(x, G, *_f32_params(norm), norm.eps)
+            if silu:
+                y = F.silu(y)
+            y = y.to(norm.weight.dtype)
+            if CHANNELS_LAST and y.is_cuda:
+                y = y.contiguous(memory_format=torch.channels_last)
         return y.permute(0, 2, 3, 1).reshape(N, H * W, C) if tokens else y  # a view: NHWC memory is the token layout
     if chan_bias is not None or conv_bias is not None:
-        from . import ops
-        return ops.groupnorm(x, norm.weight, norm.bias, norm.num_groups, norm.eps, silu=silu,
+        return ops.groupnorm(x, norm.weight, norm.bias, G, norm.eps, silu=silu,
                              chan_bias=None if chan_bias is None else chan_bias.contiguous(), conv_bias=conv_bias)
     if _fusable(x) and (H * W) % 8 == 0 and (not tokens or cpg % 4 == 0):
-        from . import ops
-        return ops.groupnorm(x, norm.weight, norm.bias, norm.num_groups, norm.eps, silu=silu, tokens=tokens)
-    if (VAE_SPLIT_CONV and FUSED_KERNELS and x.is_cuda and x.dtype == torch.float32 and not tokens and not x.is_contiguous()
-            and x.is_contiguous(memory_format=torch.channels_last) and norm.weight.dtype == torch.float32):
-        from . import ops  # the channels-last fp32 VAE (VAE_SPLIT_CONV): the normalisation layers that do not feed a split convolution
-        if ops.groupnorm_nhwc_f32_ok(C, norm.num_groups):
-            return ops.groupnorm_nhwc_f32(x, norm.weight, norm.bias, norm.num_groups, norm.eps, silu=silu)
-    if (VAE_HIP_GROUPNORM and FUSED_KERNELS and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and not tokens
-            and (H * W) % 4 == 0 and norm.weight.dtype == torch.float32 and N * norm.num_groups <= 65535):
-        from . import ops  # the fp32 VAE: split statistics + apply (+SiLU) instead of torch's one-block-per-group moments
-        return ops.groupnorm_f32(x, norm.weight, norm.bias, norm.num_groups, norm.eps, silu=silu)
-    y = F.group_norm(x, norm.num_groups, norm.weight, norm.bias, norm.eps)
+        return ops.groupnorm(x, norm.weight, norm.bias, G, norm.eps, silu=silu, tokens=tokens)
+    if FUSED_KERNELS and x.is_cuda and x.dtype == torch.float32 and not tokens and norm.weight.dtype == torch.float32:
+        # the channels-last fp32 VAE (VAE_SPLIT_CONV): the normalisation layers that do not feed a split convolution
+        if VAE_SPLIT_CONV and ops.is_nhwc(x) and ops.groupnorm_nhwc_f32_ok(C, G):
+            return ops.groupnorm_nhwc_f32(x, norm.weight, norm.bias, G, norm.eps, silu=silu)
+        # the fp32 VAE: split statistics + apply (+SiLU) instead of torch's one-block-per-group moments
+        if VAE_HIP_GROUPNORM and x.is_contiguous() and (H * W) % 4 == 0 and N * G <= 65535:
+            return ops.groupnorm_f32(x, norm.weight, norm.bias, G, norm.eps, silu=silu)
+    y = F.group_norm(x, G, norm.weight, norm.bias, norm.eps)
     if silu:
         y = F.silu(y)
     return y.permute(0, 2, 3, 1).reshape(N, H * W, C) if tokens else y
@@ -206,10 +198,9 @@ def fused_unet_entry_points():
 
 def linear_(x, weight, bias=None):
     """F.linear, through ed_linear for the 16-bit shapes it measured faster on (ops.linear_wins), hipBLASLt otherwise."""
-    if HIP_LINEAR and FUSED_KERNELS and _fusable(x) and weight.dtype == x.dtype and weight.is_contiguous():
-        from . import ops
-        if ops.linear_wins(x.numel() // x.shape[-1], x.shape[-1], weight.shape[0]):
-            return ops.linear(x, weight, bias)
+    if (HIP_LINEAR and FUSED_KERNELS and _fusable(x) and weight.dtype == x.dtype and weight.is_contiguous()
+            and ops.linear_wins(x.numel() // x.shape[-1], x.shape[-1], weight.shape[0])):
+        return ops.linear(x, weight, bias)
     return F.linear(x, weight, bias)
 
 
@@ -219,24 +210,42 @@ def linear_res_(x, weight, bias, residual):
     the add inside the projection, the LayerNorm that follows reads and writes 2 units of traffic instead of ed_add_layernorm's 4."""
     if (FUSED_RESIDUAL_LINEAR and residual is not None and HIP_LINEAR and FUSED_KERNELS and _fusable(x) and _fusable(residual)
             and weight.dtype == x.dtype == residual.dtype and weight.is_contiguous()
-            and residual.shape == x.shape[:-1] + (weight.shape[0],)):
-        from . import ops
-        if ops.linear_wins(x.numel() // x.shape[-1], x.shape[-1], weight.shape[0]):
-            return ops.linear(x, weight, bias, residual=residual), True
+            and residual.shape == x.shape[:-1] + (weight.shape[0],)
+            and ops.linear_wins(x.numel() // x.shape[-1], x.shape[-1], weight.shape[0])):
+        return ops.linear(x, weight, bias, residual=residual), True
     return linear_(x, weight, bias), False
 
 
-def _hip_conv3x3(x, conv, shape_only=False):
-    """Can ``conv`` (3x3, stride 1, padding 1) on the channels-last 16-bit activation ``x`` run as ed_conv3x3_nhwc?
-    ``shape_only``: ``x`` only stands for the shape / dtype of an activation that does not exist yet."""
-    if not (HIP_CONV3X3 and (shape_only or _fusable_nhwc(x))):
-        return False
+def _hip_conv3x3(conv, like, cin):
+    """Can ``conv`` (3x3, stride 1, padding 1) run as ed_conv3x3_nhwc on a channels-last activation of ``cin`` channels with the batch,
+    size and dtype of ``like`` (which may be the activation itself, or stand for one that does not exist yet)?"""
     w = conv.weight
-    if w.dtype != x.dtype or not w.is_contiguous(memory_format=torch.channels_last):
+    if not (HIP_CONV3X3 and w.dtype == like.dtype and w.is_contiguous(memory_format=torch.channels_last)):
         return False
-    from . import ops
-    B, C, H, W = x.shape
-    return ops.conv3x3_wins(B, H, W, C, w.shape[0])
+    B, _, H, W = like.shape
+    return ops.conv3x3_wins(B, H, W, cin, w.shape[0])
+
+
+def _hip_conv_pair(blk, like, cin):
+    """Do BOTH 3x3 convolutions of the ResnetBlock2D ``blk`` run as ed_conv3x3_nhwc, with norm2 through the channels-last HIP kernel
+    between them (its torch fallback hands back an NCHW tensor the convolution wrapper rejects)?  ``like``: a 16-bit channels-last
+    tensor with the batch, size and dtype of conv1's input, ``cin`` that input's channels; conv2's Cin is cout.  How
+    norm1 runs is the caller's own condition."""
+    cout = blk.conv1.out_channels
+    return (_fusable_nhwc(like) and cout % 8 == 0 and cout // blk.norm2.num_groups >= 8
+            and _hip_conv3x3(blk.conv1, like, cin) and _hip_conv3x3(blk.conv2, like, cout))
+
+
+def _shortcut_nhwc(sc, x):
+    """the 1x1 shortcut convolution of a channels-last ``x`` as a plain GEMM over its token view: no layout change"""
+    return linear_(x.permute(0, 2, 3, 1), sc.weight.reshape(sc.out_channels, -1), sc.bias).permute(0, 3, 1, 2)
+
+
+def _sliced(x, nb, fn):
+    """``fn`` on slices of at most ``nb`` samples of the channels-last batch ``x`` (one launch must stay inside the kernels' 32-bit
+    offsets), concatenated channels-last"""
+    outs = [fn(x[i:i + nb]) for i in range(0, x.shape[0], nb)]
+    return outs[0] if len(outs) == 1 else torch.cat(outs).contiguous(memory_format=torch.channels_last)
 
 
 def _to_nchw(x):
@@ -251,7 +260,6 @@ def _vae_split_ok(x, blk):
     if not (VAE_SPLIT_CONV and FUSED_KERNELS and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
             and blk.time_emb_proj is None and blk.conv1.weight.dtype == torch.float32):
         return False
-    from . import ops
     B, cin, H, W = x.shape
     cout = blk.conv1.out_channels
     return (ops.groupnorm_nhwc_f32_ok(cin, blk.norm1.num_groups) and ops.groupnorm_nhwc_f32_ok(cout, blk.norm2.num_groups)
@@ -259,23 +267,23 @@ def _vae_split_ok(x, blk):
 
 
 def _split_weight(conv):
-    """(split fp16 weight, 2^-k) of a Conv2d for ops.conv3x3_f32out, rebuilt when the weight changes"""
-    w = conv.weight
-    # id(w): a fresh Parameter the caching allocator placed at the freed address (same data_ptr, version 0) must not hit (ADVICE r5)
-    key = (id(w), w.data_ptr(), w._version, str(w.device))
-    hit = conv.__dict__.get("_split_w")
-    if hit is None or hit[0] != key:
-        from . import ops
-        hit = (key,) + ops.split_conv_weight(w)
-        conv.__dict__["_split_w"] = hit
-    return hit[1], hit[2]
+    """(split fp16 weight, 2^-k) of a Conv2d for ops.conv3x3_f32out"""
+    return _derived(conv, "split", (conv.weight,), lambda: ops.split_conv_weight(conv.weight))
+
+
+def _split_shortcut(sc, C1):
+    """the 1x1 shortcut's weight [cout, C1 + C2, 1, 1] as two contiguous matrices [cout, C1], [cout, C2]"""
+    def build():
+        w2d = sc.weight.detach().reshape(sc.weight.shape[0], -1)
+        return w2d[:, :C1].contiguous(), w2d[:, C1:].contiguous()
+    return _derived(sc, ("ksplit", C1), (sc.weight,), build)
 
 
 def prepare_vae_split(vae):
     """Build the split fp16 weights of every convolution of an fp32 VAE that can take the split-operand path NOW (model load), so that
     the one host synchronisation of ``ops.split_conv_weight`` (the weight's absolute maximum) never falls into a forward -- or a stream
     capture -- later.  A no-op for a CPU / 16-bit VAE or with the switch off; a weight that changes afterwards is re-split
-    on its next use (``_split_weight``'s key)."""
+    on its next use (``_derived``'s key)."""
     if not (VAE_SPLIT_CONV and FUSED_KERNELS):
         return 0
     n = 0
@@ -300,12 +308,9 @@ def layer_norm(norm, x):
     D = x.shape[-1]
     if norm.elementwise_affine and _stream32(x, norm.weight.dtype):   # fp32 residual stream -> model dtype
         if FUSED_LAYERNORM and FUSED_KERNELS and x.is_cuda and x.is_contiguous() and D % 8 == 0 and D <= 2048:
-            from . import ops
             return ops.layernorm_s32(x, norm.weight, norm.bias, norm.eps)
-        w32, b32 = _f32_params(norm)
-        return F.layer_norm(x, (D,), w32, b32, norm.eps).to(norm.weight.dtype)
+        return F.layer_norm(x, (D,), *_f32_params(norm), norm.eps).to(norm.weight.dtype)
     if FUSED_LAYERNORM and _fusable(x) and D % 8 == 0 and D <= 2048 and norm.elementwise_affine:
-        from . import ops
         return ops.layernorm(x, norm.weight, norm.bias, norm.eps)
     return norm(x)
 
@@ -315,11 +320,10 @@ def add_layer_norm(norm, a, b):
     D = a.shape[-1]
     if (FUSED_ADD_LAYERNORM and _fusable(a) and _fusable(b) and a.shape == b.shape and D % 8 == 0 and D <= 2048
             and norm.elementwise_affine):
-        from . import ops
         return ops.add_layernorm(a, b, norm.weight, norm.bias, norm.eps)
     if (FUSED_ADD_LAYERNORM and FUSED_KERNELS and norm.elementwise_affine and _fusable(a) and _stream32(b, a.dtype) and b.is_cuda
             and b.is_contiguous() and a.shape == b.shape and D % 8 == 0 and D <= 2048 and norm.weight.dtype == a.dtype):
-        from . import ops      # fp32 residual stream: 16-bit branch result + fp32 stream -> (fp32 stream, 16-bit LayerNorm)
+        # fp32 residual stream: 16-bit branch result + fp32 stream -> (fp32 stream, 16-bit LayerNorm)
         return ops.add_layernorm_s32(a, b, norm.weight, norm.bias, norm.eps)
     s = a + b          # (fp32 residual stream: a 16-bit branch result + the fp32 stream -> fp32)
     return s, layer_norm(norm, s)
@@ -371,151 +375,112 @@ class ResnetBlock2D(nn.Module):
         if _vae_split_ok(x, self):
             return self._forward_split(x)
         tb = self.time_emb_proj(F.silu(temb)) if self.time_emb_proj is not None else None
-        sc = self.conv_shortcut
-        cout = self.conv1.out_channels
-        if _stream32(x, self.conv1.weight.dtype):
+        sc, c1, c2 = self.conv_shortcut, self.conv1, self.conv2
+        cout = c1.out_channels
+        if _stream32(x, c1.weight.dtype):
             # fp32 residual stream (UNet2DConditionModel.residual_fp32): both branches in the model dtype -- the same GroupNorm -> convolution
             # kernels from norm1's output on -- and ONE fp32 add onto the stream
-            a = group_norm_act(self.norm1, x, silu=True)
-            if _hip_conv3x3(a, self.conv1) and _hip_conv3x3(a[:, :1].expand(-1, cout, -1, -1), self.conv2, shape_only=True) \
-                    and cout % 8 == 0 and cout // self.norm2.num_groups >= 8:
-                from . import ops
-                h = ops.conv3x3_nhwc(a, self.conv1.weight, self.conv1.bias, sample_bias=None if tb is None else tb.contiguous())
-                a2 = group_norm_act(self.norm2, h, silu=True)
-                B_, _, H_, W_ = a2.shape
-                if a2.dtype == torch.float16 and ops.conv3x3_f32out_ok(B_, H_, W_, cout, cout):
+            def add_to_stream(h):
+                if sc is None:
+                    return x + h
+                xs = x.to(h.dtype)
+                return (_shortcut_nhwc(sc, xs) if ops.is_nhwc(xs) else sc(xs)).float() + h
+
+            def close(a2):
+                B, _, H, W = a2.shape
+                if a2.dtype == torch.float16 and ops.conv3x3_f32out_ok(B, H, W, cout, cout):
                     # conv2 through the fp32-output epilogue (ed_conv3x3_nhwc_f32out: fp16 operands, fp32 bias / residual / result): the
                     # branch result is never rounded to 16 bits and the add onto the stream costs no pass of its own
-                    res = x if sc is None else linear_(x.to(h.dtype).permute(0, 2, 3, 1), sc.weight.reshape(cout, -1), sc.bias).permute(0, 3, 1, 2).float()
+                    res = x if sc is None else _shortcut_nhwc(sc, x.to(a2.dtype)).float()
                     res = res.contiguous(memory_format=torch.channels_last)
-                    return ops.conv3x3_f32out(a2, self.conv2.weight, _f32_bias(self.conv2), res, 1.0)
-                h = ops.conv3x3_nhwc(a2, self.conv2.weight, self.conv2.bias)
-            else:
-                h = self.conv1(a)
-                h = self.conv2(group_norm_act(self.norm2, h, silu=True, chan_bias=tb))
-            if sc is None:
-                return x + h
-            xs = x.to(h.dtype)
-            res = (linear_(xs.permute(0, 2, 3, 1), sc.weight.reshape(cout, -1), sc.bias).permute(0, 3, 1, 2)
-                   if xs.is_contiguous(memory_format=torch.channels_last) and not xs.is_contiguous() else sc(xs))
-            return res.float() + h
+                    return ops.conv3x3_f32out(a2, c2.weight, _f32_bias(c2), res, 1.0)
+                return add_to_stream(ops.conv3x3_nhwc(a2, c2.weight, c2.bias))
+
+            a = group_norm_act(self.norm1, x, silu=True)
+            if _hip_conv_pair(self, a, a.shape[1]):
+                return self._hip_convs(a, tb, close)
+            return add_to_stream(c2(group_norm_act(self.norm2, c1(a), silu=True, chan_bias=tb)))
         cl = _fusable_nhwc(x) and cout % 8 == 0 and cout // self.norm2.num_groups >= 8
-        # both norms must take the channels-last HIP kernel (its torch fallback hands back an NCHW tensor the convolution
-        # wrapper rejects) and BOTH convolutions must be shapes the kernel takes: conv2's Cin is cout
-        if (cl and x.shape[1] // self.norm1.num_groups >= 8 and _hip_conv3x3(x, self.conv1)
-                and _hip_conv3x3(x[:, :1].expand(-1, cout, -1, -1), self.conv2, shape_only=True)):
-            # both convolutions as ed_conv3x3_nhwc: conv1's epilogue adds its bias and the time embedding, conv2's its bias and
-            # the block's residual -- the two broadcast adds and the closing add never exist as separate passes
-            from . import ops
-            h = ops.conv3x3_nhwc(group_norm_act(self.norm1, x, silu=True), self.conv1.weight, self.conv1.bias,
-                                 sample_bias=None if tb is None else tb.contiguous())
-            a = group_norm_act(self.norm2, h, silu=True)
-            res = x if sc is None else linear_(x.permute(0, 2, 3, 1), sc.weight.reshape(cout, -1), sc.bias).permute(0, 3, 1, 2)
-            return ops.conv3x3_nhwc(a, self.conv2.weight, self.conv2.bias, residual=res)
+        # norm1 must take the channels-last HIP kernel as well
+        if x.shape[1] // self.norm1.num_groups >= 8 and _hip_conv_pair(self, x, x.shape[1]):
+            return self._hip_convs(group_norm_act(self.norm1, x, silu=True), tb, lambda a2: ops.conv3x3_nhwc(
+                a2, c2.weight, c2.bias, residual=x if sc is None else _shortcut_nhwc(sc, x)))
         if FUSED_CONV_BIAS and FUSED_TEMB_ADD and (cl or (_fusable(x) and (x.shape[2] * x.shape[3]) % 8 == 0)):
             # MIOpen adds a convolution's bias with a separate broadcast kernel: run the convolutions bias-free and fold
             # conv1's bias (+ temb) into norm2's passes, conv2's and the shortcut's into the closing residual add
-            from . import ops
-            h = F.conv2d(group_norm_act(self.norm1, x, silu=True), self.conv1.weight, None, padding=1)
-            a = group_norm_act(self.norm2, h, silu=True, chan_bias=tb, conv_bias=self.conv1.bias)
-            h = F.conv2d(a, self.conv2.weight, None, padding=1)
+            h = F.conv2d(group_norm_act(self.norm1, x, silu=True), c1.weight, None, padding=1)
+            a = group_norm_act(self.norm2, h, silu=True, chan_bias=tb, conv_bias=c1.bias)
+            h = F.conv2d(a, c2.weight, None, padding=1)
             if sc is None:
-                return ops.bias_residual_add(h, self.conv2.bias, x)
+                return ops.bias_residual_add(h, c2.bias, x)
             if cl:  # channels-last: the 1x1 shortcut is a plain GEMM over the token view, no layout change
-                w = sc.weight.reshape(cout, -1)
-                res = F.linear(x.permute(0, 2, 3, 1), w).permute(0, 3, 1, 2)
+                res = F.linear(x.permute(0, 2, 3, 1), sc.weight.reshape(cout, -1)).permute(0, 3, 1, 2)
             else:
                 res = F.conv2d(x, sc.weight, None)
-            return ops.bias_residual_add(h, self.conv2.bias, res, sc.bias)
-        h = self.conv1(group_norm_act(self.norm1, x, silu=True))
+            return ops.bias_residual_add(h, c2.bias, res, sc.bias)
+        h = c1(group_norm_act(self.norm1, x, silu=True))
         a = group_norm_act(self.norm2, h, silu=True, chan_bias=tb)  # GroupNorm(h + temb) (+SiLU)
         if sc is not None and SHORTCUT_AS_GEMM and _fusable(x):
             # out = W_sc x + (conv2(a) + b_conv2 + b_sc): the shortcut bias rides on conv2's bias, the residual sum is
             # the GEMM's C operand
             N, C, H, W = x.shape
-            h = F.conv2d(a, self.conv2.weight, self.conv2.bias + sc.bias, padding=1)
-            cout = h.shape[1]
+            h = F.conv2d(a, c2.weight, c2.bias + sc.bias, padding=1)
             w = sc.weight.view(1, cout, C).expand(N, -1, -1)
             return torch.baddbmm(h.view(N, cout, H * W), w, x.view(N, C, H * W)).view(N, cout, H, W)
-        h = self.conv2(a)
-        return (x if sc is None else sc(x)) + h
+        return (x if sc is None else sc(x)) + c2(a)
 
+    def _hip_convs(self, a, tb, close):
+        """Both convolutions as ed_conv3x3_nhwc from ``a`` = SiLU(norm1(.)) on (``_hip_conv_pair``): conv1's epilogue adds its bias and the
+        time embedding, norm2 is the channels-last kernel, and ``close(SiLU(norm2(.)))`` is the caller's conv2, whose epilogue adds its
+        bias and the block's residual -- the two broadcast adds and the closing add never exist as separate passes"""
+        h = ops.conv3x3_nhwc(a, self.conv1.weight, self.conv1.bias, sample_bias=None if tb is None else tb.contiguous())
+        return close(group_norm_act(self.norm2, h, silu=True))
 
-def _resnet_forward_cat(self, x, skip, temb=None):
-    """``self(torch.cat([x, skip], 1), temb)`` -- the up blocks' call -- without writing the concatenation (round 6): norm1 reads the two
-    channels-last sources in place (ed_groupnorm_nhwc_cat, bit-identical to the kernel on the materialised cat) and the 1x1 shortcut is
-    split along K, W_sc [x | skip] = W_1 x + W_2 skip: the second product accumulates onto the first (ed_linear's residual epilogue or
-    the library's beta = 1), which rounds the first partial sum to 16 bits once -- the only arithmetic difference from the cat path.
-    Everything else is ``forward``'s channels-last HIP path; any shape / layout it does not take falls back to the concatenation."""
-    sc = self.conv_shortcut
-    if FUSED_SKIP_CAT and FUSED_KERNELS and sc is not None and _fusable_nhwc(x) and _fusable_nhwc(skip) and x.dtype == skip.dtype:
-        from . import ops
+    def forward_cat(self, x, skip, temb=None):
+        """``self(torch.cat([x, skip], 1), temb)`` -- the up blocks' call -- without writing the concatenation (round 6): norm1 reads the two
+        channels-last sources in place (ed_groupnorm_nhwc_cat, bit-identical to the kernel on the materialised cat) and the 1x1 shortcut is
+        split along K, W_sc [x | skip] = W_1 x + W_2 skip: the second product accumulates onto the first (ed_linear's residual epilogue or
+        the library's beta = 1), which rounds the first partial sum to 16 bits once -- the only arithmetic difference from the cat path.
+        Everything else is ``forward``'s channels-last HIP path; any shape / layout it does not take falls back to the concatenation."""
+        sc, c2 = self.conv_shortcut, self.conv2
         C1, C = x.shape[1], x.shape[1] + skip.shape[1]
-        cout = self.conv1.out_channels
-        like = x[:, :1]
-        if (ops.groupnorm_nhwc_cat_ok(x, skip, self.norm1.num_groups) and cout % 8 == 0 and cout // self.norm2.num_groups >= 8
-                and self.conv1.weight.shape[1] == C and sc.weight.dtype == x.dtype
-                and _hip_conv3x3(like.expand(-1, C, -1, -1), self.conv1, shape_only=True)
-                and _hip_conv3x3(like.expand(-1, cout, -1, -1), self.conv2, shape_only=True)):
+        if (FUSED_SKIP_CAT and FUSED_KERNELS and sc is not None and _fusable_nhwc(skip) and x.dtype == skip.dtype
+                and _hip_conv_pair(self, x, C) and ops.groupnorm_nhwc_cat_ok(x, skip, self.norm1.num_groups)
+                and self.conv1.weight.shape[1] == C and sc.weight.dtype == x.dtype):
+            def close(a2):
+                w1, w2 = _split_shortcut(sc, C1)
+                xt, st = x.permute(0, 2, 3, 1), skip.permute(0, 2, 3, 1)          # contiguous [N, H, W, C] views of channels-last memory
+                y = linear_(xt, w1, sc.bias)
+                M, cout = st.numel() // st.shape[-1], w2.shape[0]
+                if HIP_LINEAR and ops.linear_wins(M, st.shape[-1], cout):
+                    y = ops.linear(st, w2, None, residual=y)
+                else:
+                    y = torch.addmm(y.reshape(M, cout), st.reshape(M, -1), w2.t()).view(y.shape)
+                return ops.conv3x3_nhwc(a2, c2.weight, c2.bias, residual=y.permute(0, 3, 1, 2))
+
             tb = self.time_emb_proj(F.silu(temb)) if self.time_emb_proj is not None else None
-            a = ops.groupnorm_nhwc_cat(x, skip, self.norm1.weight, self.norm1.bias, self.norm1.num_groups, self.norm1.eps, silu=True)
-            h = ops.conv3x3_nhwc(a, self.conv1.weight, self.conv1.bias, sample_bias=None if tb is None else tb.contiguous())
-            a = group_norm_act(self.norm2, h, silu=True)
-            w1, w2 = _split_shortcut(sc, C1)
-            xt, st = x.permute(0, 2, 3, 1), skip.permute(0, 2, 3, 1)          # contiguous [N, H, W, C] views of channels-last memory
-            y = linear_(xt, w1, sc.bias)
-            M = st.numel() // st.shape[-1]
-            if HIP_LINEAR and ops.linear_wins(M, st.shape[-1], cout):
-                y = ops.linear(st, w2, None, residual=y)
-            else:
-                y = torch.addmm(y.reshape(M, cout), st.reshape(M, -1), w2.t()).view(y.shape)
-            return ops.conv3x3_nhwc(a, self.conv2.weight, self.conv2.bias, residual=y.permute(0, 3, 1, 2))
-    return self(torch.cat([x, skip], dim=1), temb)
+            n1 = self.norm1
+            return self._hip_convs(ops.groupnorm_nhwc_cat(x, skip, n1.weight, n1.bias, n1.num_groups, n1.eps, silu=True), tb, close)
+        return self(torch.cat([x, skip], dim=1), temb)
 
+    def _forward_split(self, x):
+        """The fp32 VAE block with both 3x3 convolutions on the MFMA pipe (VAE_SPLIT_CONV): GroupNorm + SiLU write the split fp16 operand,
+        the convolution's fp32 epilogue adds the bias and (conv2) the block's residual.  Batches whose operand would exceed the kernel's
+        32-bit offsets are processed in slices (GroupNorm is per sample)."""
+        n1, n2, sc = self.norm1, self.norm2, self.conv_shortcut
+        _, cin, H, W = x.shape
 
-def _split_shortcut(sc, C1):
-    """the 1x1 shortcut's weight [cout, C1 + C2, 1, 1] as two contiguous matrices [cout, C1], [cout, C2]; rebuilt when the weight changes"""
-    w = sc.weight
-    key = (id(w), w.data_ptr(), w._version, C1)
-    hit = sc.__dict__.get("_ksplit")
-    if hit is None or hit[0] != key:
-        w2d = w.detach().reshape(w.shape[0], -1)
-        hit = (key, w2d[:, :C1].contiguous(), w2d[:, C1:].contiguous())
-        sc.__dict__["_ksplit"] = hit
-    return hit[1], hit[2]
+        def block(xs):
+            w1, s1 = _split_weight(self.conv1)
+            w2, s2 = _split_weight(self.conv2)
+            a = ops.groupnorm_nhwc_f32(xs, n1.weight, n1.bias, n1.num_groups, n1.eps, silu=True, split=True)
+            h = ops.conv3x3_f32out(a, w1, self.conv1.bias, None, s1)
+            a = ops.groupnorm_nhwc_f32(h, n2.weight, n2.bias, n2.num_groups, n2.eps, silu=True, split=True)
+            res = xs if sc is None else _shortcut_nhwc(sc, xs)    # 1x1 convolution = an fp32 GEMM over the NHWC view
+            return ops.conv3x3_f32out(a, w2, self.conv2.bias, res, s2)
 
-
-ResnetBlock2D.forward_cat = _resnet_forward_cat
-
-
-def _resnet_forward_split(self, x):
-    """The fp32 VAE block with both 3x3 convolutions on the MFMA pipe (VAE_SPLIT_CONV): GroupNorm + SiLU write the split fp16 operand,
-    the convolution's fp32 epilogue adds the bias and (conv2) the block's residual.  Batches whose operand would exceed the kernel's
-    32-bit offsets are processed in slices (GroupNorm is per sample)."""
-    from . import ops
-    cl = torch.channels_last
-    if not x.is_contiguous(memory_format=cl):
-        x = x.contiguous(memory_format=cl)
-    B, cin, H, W = x.shape
-    cout = self.conv1.out_channels
-    per = H * W * 3 * max(cin, cout) * 2
-    nb = max(1, (2 ** 31 - 16) // per)
-    if B > nb:
-        return torch.cat([_resnet_forward_split(self, x[i:i + nb]) for i in range(0, B, nb)]).contiguous(memory_format=cl)
-    w1, s1 = _split_weight(self.conv1)
-    w2, s2 = _split_weight(self.conv2)
-    a = ops.groupnorm_nhwc_f32(x, self.norm1.weight, self.norm1.bias, self.norm1.num_groups, self.norm1.eps, silu=True, split=True)
-    h = ops.conv3x3_f32out(a, w1, self.conv1.bias, None, s1)
-    a = ops.groupnorm_nhwc_f32(h, self.norm2.weight, self.norm2.bias, self.norm2.num_groups, self.norm2.eps, silu=True, split=True)
-    sc = self.conv_shortcut
-    if sc is None:
-        res = x
-    else:   # 1x1 convolution = an fp32 GEMM over the NHWC view
-        res = F.linear(x.permute(0, 2, 3, 1), sc.weight.reshape(cout, cin), sc.bias).permute(0, 3, 1, 2)
-    return ops.conv3x3_f32out(a, w2, self.conv2.bias, res, s2)
-
-
-ResnetBlock2D._forward_split = _resnet_forward_split
+        per = H * W * 3 * max(cin, self.conv1.out_channels) * 2
+        return _sliced(x.contiguous(memory_format=torch.channels_last), max(1, (2 ** 31 - 16) // per), block)
 
 
 class Attention(nn.Module):
@@ -529,30 +494,18 @@ class Attention(nn.Module):
         self.to_out = nn.ModuleList([nn.Linear(inner, dim), nn.Dropout(0.0)])
 
     def _fused_weight(self, names, q_scale=None):
-        """cat of the projection weights (bias-free in every SD / SDXL attention), rebuilt when a weight changes.
+        """cat of the projection weights (bias-free in every SD / SDXL attention).
         ``q_scale``: factor folded into the first (query) weight -- softmax scale * log2 e for the exponent-domain attention
         kernel (ops.flash_prescale): the product is formed in fp32 and rounded once, so the scaled 16-bit weight is as close
         to c * W as the stored one is to W."""
-        mods = [getattr(self, n) for n in names]
-        key = tuple((m.weight.data_ptr(), m.weight._version, m.weight.dtype, str(m.weight.device)) for m in mods)
-        cache = self.__dict__.setdefault("_fused", {})
-        slot = (names, q_scale)
-        if cache.get(slot, (None, None))[0] != key:
-            ws = [m.weight.detach() for m in mods]
-            if q_scale is not None:
-                ws[0] = (ws[0].float() * q_scale).to(ws[0].dtype)
-            cache[slot] = (key, torch.cat(ws, dim=0).contiguous())
-        return cache[slot][1]
+        ws = [getattr(self, n).weight for n in names]
 
-    def _out_proj(self, o):
-        """to_out[0], with the block's residual in its epilogue when one is pending (forward(residual=...)) and ed_linear runs this shape"""
-        res = self.__dict__.get("_res")
-        if res is not None:
-            y, fused = linear_res_(o, self.to_out[0].weight, self.to_out[0].bias, res)
-            if fused:
-                self.__dict__.pop("_res", None)
-            return y
-        return linear_(o, self.to_out[0].weight, self.to_out[0].bias)
+        def build():
+            parts = [w.detach() for w in ws]
+            if q_scale is not None:
+                parts[0] = (parts[0].float() * q_scale).to(parts[0].dtype)
+            return torch.cat(parts, dim=0).contiguous()
+        return _derived(self, (names, q_scale), ws, build)
 
     def project_kv(self, context, out=None):
         """k, v of a cross-attention as ONE [B, Nk, 2 inner] tensor (fused weight).  They depend on the text rows only -- not on
@@ -567,19 +520,16 @@ class Attention(nn.Module):
     def forward(self, x, context=None, kv=None, residual=None):
         """``residual`` given: -> (out, fused) -- out = residual + attention(...) when the output projection took the add (fused), else the
         plain attention output and the caller adds."""
-        if residual is not None:
-            self.__dict__["_res"] = residual
-            try:
-                out = self.forward(x, context, kv)
-            finally:
-                res_state = self.__dict__.pop("_res", None)
-            return out, res_state is None          # _out_proj consumed the residual
+        out, fused = self._attend(x, context, kv, residual)
+        return out if residual is None else (out, fused)
+
+    def _attend(self, x, context, kv, residual):
+        """-> (attention output, did to_out[0] add ``residual`` in its epilogue?)"""
         B, N, _ = x.shape
         inner = self.to_q.out_features
         if (FLASH_ATTENTION and _fusable(x) and inner % self.heads == 0 and inner // self.heads in (40, 64, 80, 160)
                 and self.to_q.bias is None
                 and (context is None or (_fusable(context) and context.dtype == x.dtype))):
-            from . import ops
             if context is None:
                 # exponent-domain kernel: softmax scale * log2 e lives in the query weights (None: natural-domain q)
                 c = ops.flash_prescale(N, N, 3 * inner if FUSED_QKV else inner) if inner == self.heads * 64 else None
@@ -590,7 +540,6 @@ class Attention(nn.Module):
                     q = linear_(x, self.to_q.weight if c is None else self._fused_weight(("to_q",), c))
                     k, v = self.to_k(x), self.to_v(x)
                 o = ops.flash_attention(q, k, v, self.heads, prescaled=c is not None)
-                return self._out_proj(o)
             else:
                 q = linear_(x, self.to_q.weight)
                 if kv is not None or FUSED_QKV:
@@ -599,7 +548,9 @@ class Attention(nn.Module):
                     k, v = kv[..., :inner], kv[..., inner:]
                 else:
                     k, v = self.to_k(context), self.to_v(context)
-            return self._out_proj(ops.flash_attention(q, k, v, self.heads))
+                o = ops.flash_attention(q, k, v, self.heads)
+            # the block's residual in to_out[0]'s epilogue when one is given and ed_linear runs this shape
+            return linear_res_(o, self.to_out[0].weight, self.to_out[0].bias, residual)
         ctx = x if context is None else context
         q = self.to_q(x).view(B, N, self.heads, -1).transpose(1, 2)
         if kv is not None:
@@ -608,7 +559,7 @@ class Attention(nn.Module):
             k = self.to_k(ctx).view(B, ctx.shape[1], self.heads, -1).transpose(1, 2)
             v = self.to_v(ctx).view(B, ctx.shape[1], self.heads, -1).transpose(1, 2)
         o = F.scaled_dot_product_attention(q, k, v)
-        return self.to_out[0](o.transpose(1, 2).reshape(B, N, -1))
+        return self.to_out[0](o.transpose(1, 2).reshape(B, N, -1)), False
 
 
 class GEGLU(nn.Module):
@@ -617,13 +568,11 @@ class GEGLU(nn.Module):
         self.proj = nn.Linear(dim, inner * 2)
 
     def forward(self, x):
-        if HIP_GEGLU_GEMM and FUSED_KERNELS and _fusable(x) and self.proj.weight.dtype == x.dtype:
-            from . import ops
-            if ops.geglu_gemm_wins(x.numel() // x.shape[-1], x.shape[-1], self.proj.out_features // 2):
-                return ops.geglu_gemm(x, self.proj.weight, self.proj.bias)
+        if (HIP_GEGLU_GEMM and FUSED_KERNELS and _fusable(x) and self.proj.weight.dtype == x.dtype
+                and ops.geglu_gemm_wins(x.numel() // x.shape[-1], x.shape[-1], self.proj.out_features // 2)):
+            return ops.geglu_gemm(x, self.proj.weight, self.proj.bias)
         y = self.proj(x)
         if _fusable(y) and (y.shape[-1] // 2) % 8 == 0:
-            from . import ops
             return ops.geglu(y, y.shape[-1] // 2)
         h, gate = y.chunk(2, dim=-1)
         return h * F.gelu(gate)
@@ -695,16 +644,13 @@ class Transformer2DModel(nn.Module):
             h = h.to(self.proj_out.weight.dtype)
         if self.linear_proj:
             if (FUSED_PROJ_OUT_ADD and HIP_LINEAR and FUSED_KERNELS and _fusable_nhwc(x) and _fusable(h) and self.proj_out.weight.dtype == x.dtype == h.dtype
-                    and self.proj_out.weight.is_contiguous()):
-                from . import ops
-                if ops.linear_wins(B * H * W, C, C):
-                    # channels-last: x's memory IS the token layout, so the block's closing `x + proj_out(h)` rides in ed_linear's residual
-                    # epilogue (one rounding of bias + product + residual instead of two) -- no separate add pass
-                    y = ops.linear(h, self.proj_out.weight, self.proj_out.bias, residual=x.permute(0, 2, 3, 1).reshape(B, H * W, C))
-                    return y.view(B, H, W, C).permute(0, 3, 1, 2)
+                    and self.proj_out.weight.is_contiguous() and ops.linear_wins(B * H * W, C, C)):
+                # channels-last: x's memory IS the token layout, so the block's closing `x + proj_out(h)` rides in ed_linear's residual
+                # epilogue (one rounding of bias + product + residual instead of two) -- no separate add pass
+                y = ops.linear(h, self.proj_out.weight, self.proj_out.bias, residual=x.permute(0, 2, 3, 1).reshape(B, H * W, C))
+                return y.view(B, H, W, C).permute(0, 3, 1, 2)
             h = linear_(h, self.proj_out.weight, self.proj_out.bias)
             if (FUSED_TOKENS_ADD and _fusable(x) and _fusable(h) and C % 64 == 0 and (H * W) % 64 == 0):
-                from . import ops
                 return ops.tokens_add_nchw(x, h)  # x + h^T in one pass through an LDS tile
             h = h.view(B, H, W, C).permute(0, 3, 1, 2)
         else:
@@ -719,34 +665,28 @@ class Downsample2D(nn.Module):
         self.conv = nn.Conv2d(ch, ch, 3, stride=2, padding=padding)
 
     def forward(self, x):
+        if _stream32(x, self.conv.weight.dtype):   # fp32 residual stream: the convolution in the model dtype, its result widened (exact)
+            return self.forward(x.to(self.conv.weight.dtype)).float()
         if self.padding == 0 and VAE_SPLIT_CONV and VAE_SPLIT_DOWNSAMPLE and FUSED_KERNELS and x.is_cuda and x.dtype == torch.float32 \
                 and x.dim() == 4 and self.conv.weight.dtype == torch.float32:
             # the VAE encoder's downsampler on the MFMA pipe (round 6): the raw stream is split like the decoder's upsampler input (per-tensor
             # power-of-two scale from its absolute maximum), the pad-(0, 1, 0, 1) stride-2 convolution is template value CONV = 4 of the
             # split-operand main loop; channels-last in and out -- no NCHW copies around the library call
-            from . import ops
             B, C, H, W = x.shape
             if C % 64 == 0 and ops.conv3x3_f32out_s2_ok(1, H, W, 3 * C, self.conv.weight.shape[0]):
                 w, sc = _split_weight(self.conv)
-                x = x.contiguous(memory_format=torch.channels_last)
-                nb = max(1, (2 ** 31 - 16) // (H * W * 3 * C * 2))
-                outs = []
-                for i in range(0, B, nb):
-                    xs = x[i:i + nb]
+
+                def conv(xs):
                     am = ops.absmax_f32(xs)
-                    outs.append(ops.conv3x3_f32out_s2(ops.split_f32(xs, absmax=am), w, self.conv.bias, sc, act_absmax=am))
-                return outs[0] if len(outs) == 1 else torch.cat(outs).contiguous(memory_format=torch.channels_last)
+                    return ops.conv3x3_f32out_s2(ops.split_f32(xs, absmax=am), w, self.conv.bias, sc, act_absmax=am)
+                return _sliced(x.contiguous(memory_format=torch.channels_last), max(1, (2 ** 31 - 16) // (H * W * 3 * C * 2)), conv)
         if self.padding == 0:  # VAE encoder: asymmetric pad (diffusers Downsample2D)
             x = F.pad(_to_nchw(x), (0, 1, 0, 1))
-        if _stream32(x, self.conv.weight.dtype):   # fp32 residual stream: the convolution in the model dtype, its result widened (exact)
-            return self.forward(x.to(self.conv.weight.dtype)).float()
         if HIP_DOWNSAMPLE_CONV and HIP_CONV3X3 and self.padding == 1 and _fusable_nhwc(x) and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0:
             w = self.conv.weight
-            if w.dtype == x.dtype and w.is_contiguous(memory_format=torch.channels_last):
-                from . import ops
-                B, C, H, W = x.shape
-                if ops.conv3x3_s2_wins(B, H // 2, W // 2, C, w.shape[0]):
-                    return ops.conv3x3_nhwc_s2(x, w, self.conv.bias)       # the stride-2 convolution on the MFMA main loop
+            B, C, H, W = x.shape
+            if w.dtype == x.dtype and w.is_contiguous(memory_format=torch.channels_last) and ops.conv3x3_s2_wins(B, H // 2, W // 2, C, w.shape[0]):
+                return ops.conv3x3_nhwc_s2(x, w, self.conv.bias)       # the stride-2 convolution on the MFMA main loop
         return self.conv(x)
 
 
@@ -772,29 +712,21 @@ class Upsample2D(nn.Module):
             if self._split_ok(x):
                 # the VAE decoder's upsampler on the MFMA pipe (VAE_SPLIT_CONV): the raw stream is split (scaled by a per-tensor power of
                 # two taken from its absolute maximum on the device: the real decoder stream leaves fp16's range) and upsampled in one pass, the convolution is the same split-operand main loop as the ResnetBlocks'; channels-last in and out
-                from . import ops
                 w, sc = _split_weight(self.conv)
-                cl = torch.channels_last
-                x = x.contiguous(memory_format=cl)
                 B, C, H, W = x.shape
-                nb = max(1, (2 ** 31 - 16) // (4 * H * W * 3 * C * 2))
-                outs = []
-                for i in range(0, B, nb):
-                    xs = x[i:i + nb]
+
+                def conv(xs):
                     am = ops.absmax_f32(xs)     # per-slice power-of-two scale: the split is exact over the whole fp32 range
-                    outs.append(ops.conv3x3_f32out(ops.split_f32(xs, upsample2x=True, absmax=am), w, self.conv.bias, None, sc, act_absmax=am))
-                return outs[0] if len(outs) == 1 else torch.cat(outs).contiguous(memory_format=cl)
+                    return ops.conv3x3_f32out(ops.split_f32(xs, upsample2x=True, absmax=am), w, self.conv.bias, None, sc, act_absmax=am)
+                return _sliced(x.contiguous(memory_format=torch.channels_last), max(1, (2 ** 31 - 16) // (4 * H * W * 3 * C * 2)), conv)
             x = _to_nchw(x)  # NCHW for MIOpen's fp32 solvers (the UNet's 16-bit activations stay channels-last)
         if FUSED_UPSAMPLE_CONV and HIP_CONV3X3 and _fusable_nhwc(x):
             w = self.conv.weight
-            if w.dtype == x.dtype and w.is_contiguous(memory_format=torch.channels_last):
-                from . import ops
-                B, C, H, W = x.shape
-                if ops.conv3x3_up2x_wins(B, 2 * H, 2 * W, C, w.shape[0]):
-                    return ops.conv3x3_nhwc_up2x(x, w, self.conv.bias)   # the upsampled tensor (4x the source) is never written
+            B, C, H, W = x.shape
+            if w.dtype == x.dtype and w.is_contiguous(memory_format=torch.channels_last) and ops.conv3x3_up2x_wins(B, 2 * H, 2 * W, C, w.shape[0]):
+                return ops.conv3x3_nhwc_up2x(x, w, self.conv.bias)   # the upsampled tensor (4x the source) is never written
         up = F.interpolate(x, scale_factor=2.0, mode="nearest")
-        if _hip_conv3x3(up, self.conv):
-            from . import ops
+        if _fusable_nhwc(up) and _hip_conv3x3(self.conv, up, up.shape[1]):
             return ops.conv3x3_nhwc(up, self.conv.weight, self.conv.bias)
         return self.conv(up)
 
@@ -1060,11 +992,10 @@ class _VaeAttention(nn.Module):
     def forward(self, x):
         B, C, H, W = x.shape
         h = group_norm_act(self.group_norm, x)
-        cl = not h.is_contiguous() and h.is_contiguous(memory_format=torch.channels_last)   # channels-last VAE (VAE_SPLIT_CONV)
+        cl = ops.is_nhwc(h)   # channels-last VAE (VAE_SPLIT_CONV)
         h = h.permute(0, 2, 3, 1).reshape(B, H * W, C) if cl else h.view(B, C, H * W).transpose(1, 2)
         if VAE_HIP_ATTENTION and h.is_cuda and h.dtype == torch.float32 and (H * W) % 4 == 0:
             # two fp32 library GEMMs around ed_softmax_rows: no AOTriton (Triton) kernel on the path
-            from . import ops
             o = ops.vae_attention(self.to_q(h), self.to_k(h), self.to_v(h))
         else:
             q, k, v = (f(h).unsqueeze(1) for f in (self.to_q, self.to_k, self.to_v))

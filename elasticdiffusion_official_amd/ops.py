@@ -105,6 +105,12 @@ def _opt(t, dtype=None, name="tensor"):
     return None if t is None else _dev(t, dtype, name)
 
 
+def is_nhwc(x):
+    """is ``x`` [N,C,H,W] in channels-last memory and NOT NCHW-contiguous as well (a tensor with C = 1 or H = W = 1 is both: every path
+    treats it as NCHW)?  The one spelling of the layout test, for the wrappers here and the dispatch rules of models.py."""
+    return x.dim() == 4 and not x.is_contiguous() and x.is_contiguous(memory_format=torch.channels_last)
+
+
 def _code(t, name):
     try:
         return _DTYPE[t.dtype]
@@ -614,8 +620,7 @@ def groupnorm_nhwc(x, gamma, beta, groups, eps, silu=False, chan_bias=None, conv
 def groupnorm_nhwc_cat_ok(x1, x2, groups):
     """can ed_groupnorm_nhwc_cat normalise cat([x1, x2], 1) of these two tensors in place?"""
     def cl16(x):
-        return (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.dtype in (torch.float16, torch.bfloat16)
-                and not x.is_contiguous() and x.is_contiguous(memory_format=torch.channels_last))
+        return isinstance(x, torch.Tensor) and x.is_cuda and x.dtype in (torch.float16, torch.bfloat16) and is_nhwc(x)
     if not (cl16(x1) and cl16(x2) and x1.dtype == x2.dtype and x1.device == x2.device and x1.shape[0] == x2.shape[0]
             and x1.shape[2:] == x2.shape[2:]):
         return False
@@ -717,7 +722,7 @@ def bias_residual_add(h, h_bias, res, res_bias=None):
     assert res.shape == h.shape and res.dtype == h.dtype
     if not (h.is_cuda and res.is_cuda):
         _reject("bias_residual_add: h and res must be tensors on the MI355X; no CPU fallback")
-    cl = (not h.is_contiguous()) and h.is_contiguous(memory_format=torch.channels_last) and C % 8 == 0
+    cl = is_nhwc(h) and C % 8 == 0
     fmt = torch.channels_last if cl else torch.contiguous_format
     # mixed layouts only arise on fallback paths (a torch GroupNorm returning NCHW inside a channels-last model): follow
     # the convolution output's layout, re-laying-out the other operand

@@ -435,6 +435,12 @@ def test_round6_host_policies_and_cpu_fallbacks():
         down = M.Downsample2D(16, padding=0).eval()
         y = torch.randn(2, 16, 8, 6)
         assert torch.equal(down(y), F.conv2d(F.pad(y, (0, 1, 0, 1)), down.conv.weight, down.conv.bias, stride=2))
+        # an fp32 stream into a 16-bit padding-0 downsampler is padded ONCE: only odd sizes read the pad's last row / column
+        down16 = M.Downsample2D(16, padding=0).bfloat16().eval()
+        y = torch.randn(2, 16, 7, 9)
+        want = F.conv2d(F.pad(y.bfloat16(), (0, 1, 0, 1)), down16.conv.weight, down16.conv.bias, stride=2).float()
+        got = down16(y)
+        assert tuple(got.shape) == (2, 16, 3, 4) and got.dtype == torch.float32 and torch.equal(got, want)
     assert not ops.groupnorm_nhwc_cat_ok(x, skip, 8)                                  # CPU tensors
     w1, w2 = M._split_shortcut(blk.conv_shortcut, 24)
     assert torch.equal(torch.cat([w1, w2], 1), blk.conv_shortcut.weight.reshape(32, 40)) and w1.is_contiguous() and w2.is_contiguous()

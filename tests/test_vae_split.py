@@ -323,6 +323,30 @@ def test_split_weight_cache_key_tells_a_replaced_parameter_apart():
     conv.weight = torch.nn.Parameter(w0.detach().clone())
     w1 = conv.weight
     assert (id(w1), w1.data_ptr(), w1._version, str(w1.device)) != k0
-    import inspect
-    assert "id(w)" in inspect.getsource(M._split_weight)
     assert M.prepare_vae_split(torch.nn.Sequential(conv)) == 0     # CPU weights: nothing to pre-split, no error
+
+    def rebuilt_after_replacing(module, name, derive):
+        """the behaviour itself: the same storage and version under a NEW Parameter object must give a newly built value"""
+        def tensors():
+            v = derive()
+            return [t for t in (v if isinstance(v, tuple) else (v,)) if isinstance(t, torch.Tensor)]
+        first = tensors()
+        assert first and all(a is b for a, b in zip(tensors(), first))          # unchanged parameter: a hit
+        old = getattr(module, name)
+        new = torch.nn.Parameter(old.detach(), requires_grad=old.requires_grad)
+        assert new.data_ptr() == old.data_ptr() and new._version == old._version and id(new) != id(old)
+        setattr(module, name, new)
+        assert all(a is not b for a, b in zip(tensors(), first)), (type(module).__name__, name)
+
+    # every user of the shared derived-tensor cache
+    rebuilt_after_replacing(conv, "weight", lambda: M._split_weight(conv))
+    sc = torch.nn.Conv2d(40, 32, 1)
+    rebuilt_after_replacing(sc, "weight", lambda: M._split_shortcut(sc, 24))
+    norm = torch.nn.GroupNorm(8, 32).bfloat16()
+    for name in ("weight", "bias"):                                # the fp32 residual stream's fp32 affine parameters
+        rebuilt_after_replacing(norm, name, lambda: M._f32_params(norm))
+    rebuilt_after_replacing(norm, "bias", lambda: M._f32_bias(norm))
+    attn = M.Attention(64, 1, 64)
+    for names, q_scale in ((("to_q", "to_k", "to_v"), 0.18), (("to_q", "to_k", "to_v"), None), (("to_k", "to_v"), None)):
+        for name in names:                                         # the fused QKV / KV weight of every attention in the UNet
+            rebuilt_after_replacing(getattr(attn, name), "weight", lambda: attn._fused_weight(names, q_scale))
