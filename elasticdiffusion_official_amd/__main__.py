@@ -7,7 +7,10 @@ elastic_diffusion_w_controlnet.py:1342-1433): same flags and defaults, PNGs + ar
 Differences: needs a ROCm device (no CPU fallback); ``--weights DIR`` points at a local HF snapshot (unet/, vae/,
 text_encoder*/ ...); without it the architecture is randomly initialised and the text embeddings are synthetic
 (this build image has neither checkpoints nor network).  Boolean flags take true/false (the reference's
-``type=bool`` treats every non-empty string as True).
+``type=bool`` treats every non-empty string as True).  ``--condition_image FILE`` selects the ControlNet pipeline and is
+the already extracted condition by default; ``--process_condition true`` treats it as a raw photo like the reference's
+flag of the same name (resize to the reduced resolution, canny on the device / injected depth estimator) and saves the
+extracted condition as ``condition.png``.
 """
 import argparse
 import os
@@ -49,7 +52,10 @@ def main(argv=None):
     ap.add_argument("--log_freq", type=int, default=5)
     ap.add_argument("--verbose", type=_bool, default=False)
     ap.add_argument("--weights", type=str, default=None, help="local HF snapshot directory (optional)")
-    ap.add_argument("--condition_image", type=str, default=None, help="pre-processed condition image => ControlNet path")
+    ap.add_argument("--condition_image", type=str, default=None, help="condition image => ControlNet path (pre-processed "
+                    "unless --process_condition true)")
+    ap.add_argument("--process_condition", type=_bool, default=False, help="true: --condition_image is a raw photo; resize it "
+                    "and extract the canny / depth condition from it as the reference command line does (EDC:1390-1393)")
     ap.add_argument("--controlnet_conditioning_scale", type=float, default=0.2)
     ap.add_argument("--controlnet_model", type=str, default="depth")
     opt = ap.parse_args(argv)
@@ -69,8 +75,10 @@ def main(argv=None):
         sd = ElasticDiffusionControlNet(device, opt.sd_version, opt.controlnet_model, verbose=opt.verbose,
                                         log_freq=opt.log_freq, view_batch_size=opt.view_batch_size,
                                         low_vram=opt.low_vram, **kw)
-        extra = dict(condition_image=Image.open(opt.condition_image),
-                     controlnet_conditioning_scale=opt.controlnet_conditioning_scale)
+        condition_image = Image.open(opt.condition_image)
+        if opt.process_condition:
+            condition_image = sd.prepare_condition_image(condition_image, opt.H, opt.W)
+        extra = dict(condition_image=condition_image, controlnet_conditioning_scale=opt.controlnet_conditioning_scale)
     else:
         sd = ElasticDiffusion(device, opt.sd_version, verbose=opt.verbose, log_freq=opt.log_freq,
                               view_batch_size=opt.view_batch_size, low_vram=opt.low_vram, **kw)
@@ -93,6 +101,8 @@ def main(argv=None):
     os.makedirs(save_dir, exist_ok=True)
     for i, img in enumerate(imgs):
         img.save(f"{save_dir}/{i}.png")
+    if opt.condition_image and opt.process_condition:
+        extra["condition_image"].save(f"{save_dir}/condition.png")  # the extracted condition, next to the images
     for key, logged in image_log.items():  # ED:1201-1205: the verbose image log next to the images
         if isinstance(logged, dict):
             for label, img in logged.items():

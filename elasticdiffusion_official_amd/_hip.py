@@ -13,11 +13,12 @@ import torch  # noqa: F401  (must be imported before the .so so libamdhip64 is a
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT_DIR = os.path.dirname(PKG_DIR)
-SOURCES = [os.path.join(PKG_DIR, "csrc", n) for n in ("elastic_kernels.hip", "unet_kernels.hip", "attention_kernels.hip", "gemm_kernels.hip", "vae_kernels.hip")]
+SOURCES = [os.path.join(PKG_DIR, "csrc", n) for n in ("elastic_kernels.hip", "unet_kernels.hip", "attention_kernels.hip", "gemm_kernels.hip", "vae_kernels.hip",
+                                                       "canny_kernels.hip")]
 SRC = SOURCES[0]
 INCLUDE = os.path.join(ROOT_DIR, "include")
 SO_PATH = os.path.join(PKG_DIR, "libelastic_hip.so")
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
 
@@ -72,6 +73,10 @@ SIGNATURES = {
     "ed_groupnorm_nhwc_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp],
     "ed_conv3x3_nhwc_f32out": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp],
     "ed_conv3x3_nhwc_f32out_s2": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp],
+    "ed_canny_workspace": [_i, _i, _i],
+    "ed_canny_map": [_vp, _i, _i, _i, _i, _i, _vp, _vp],
+    "ed_canny_hysteresis": [_vp, _i, _i, _vp, _vp, _vp],
+    "ed_canny_edges": [_vp, _i, _i, _vp, _vp, _vp],
 }
 
 _LIB = None
@@ -82,7 +87,7 @@ def build_library(force=False, verbose=False):
     deps = SOURCES + [os.path.join(INCLUDE, "elastic_hip.h")]
     if not force and os.path.isfile(SO_PATH) and os.path.getmtime(SO_PATH) >= max(os.path.getmtime(d) for d in deps):
         return SO_PATH
-    # one hipcc per translation unit, side by side (the five files are independent; ~25 s instead of ~60 s), then one link
+    # one hipcc per translation unit, side by side (the files are independent; ~25 s instead of ~60 s), then one link
     import tempfile
     flags = [f for f in HIPCC_FLAGS if f != "-shared"]
     with tempfile.TemporaryDirectory(prefix="ed_build_") as tmp:

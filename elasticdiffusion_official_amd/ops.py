@@ -1022,3 +1022,87 @@ def flash_attention(q, k, v, heads, v_path=None, prescaled=False):
           hd, q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0), out.stride(1),
           hd ** -0.5, variant, _stream())
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Canny condition extraction (csrc/canny_kernels.hip): pre-processing of one image before the loop, never graph-captured
+# ---------------------------------------------------------------------------------------------------------------------
+CANNY_MAX_DIM = 8192
+
+
+def _canny_dims(t, name, channels):
+    """(H, W, C) of a uint8 image tensor [H,W,C] / [H,W] (``channels``: the allowed C), rejected outside the kernels' bounds."""
+    if t.dim() == 2 and 1 in channels:
+        H, W, C = t.shape[0], t.shape[1], 1
+    elif t.dim() == 3 and t.shape[2] in channels:
+        H, W, C = t.shape
+    else:
+        _reject(f"{name} must be uint8 [H,W,C] with C in {sorted(channels)}{' or [H,W]' if 1 in channels else ''}, got {tuple(t.shape)}")
+    if not (1 <= H <= CANNY_MAX_DIM and 1 <= W <= CANNY_MAX_DIM):
+        _reject(f"{name}: H and W must be in 1..{CANNY_MAX_DIM}, got {H} x {W}")
+    return H, W, C
+
+
+def _canny_threshold(v, name):
+    import math
+    if not math.isfinite(v):
+        _reject(f"canny: {name} threshold must be finite, got {v}")
+    return max(-2 ** 31, min(2 ** 31 - 1, int(math.floor(v))))
+
+
+def canny_map(img, low=100, high=200):
+    """img uint8 [H,W,C] (C = 1 or 3; [H,W] = one channel), HWC contiguous -> uint8 map [H,W]: 1 = not an edge, 0 = candidate,
+    2 = strong (OpenCV's coding).  Thresholds are floored, and swapped when low > high.  See ed_canny_map."""
+    p_img = _dev(img, torch.uint8, "img")
+    H, W, C = _canny_dims(img, "img", (1, 3))
+    lo, hi = _canny_threshold(low, "low"), _canny_threshold(high, "high")
+    cmap = torch.empty((H, W), dtype=torch.uint8, device=img.device)
+    TIMER.note_work("ed_canny_map", nbytes=float(H * W * (C + 1)))
+    _call("ed_canny_map", p_img, H, W, C, lo, hi, _dev(cmap, torch.uint8, "map"), _stream())
+    return cmap
+
+
+def canny_hysteresis(cmap):
+    """In place on a uint8 map [H,W]: candidates (0) that are 8-connected through candidates to a strong pixel (2) become 2.
+    -> (cmap, global passes).  Synchronises the stream once per pass (see ed_canny_hysteresis): not for graph capture."""
+    import ctypes
+    p_map = _dev(cmap, torch.uint8, "map")
+    H, W, _ = _canny_dims(cmap, "map", (1,))
+    if cmap.dim() != 2:
+        _reject(f"map must be [H,W], got {tuple(cmap.shape)}")
+    if torch.cuda.is_current_stream_capturing():
+        _reject("canny_hysteresis reads a device flag between passes and cannot be captured into a graph")
+    ws = torch.empty(_hip.lib().ed_canny_workspace(H, W, 1) // 4, dtype=torch.int32, device=cmap.device)
+    passes = ctypes.c_int32(0)
+    TIMER.note_work("ed_canny_hysteresis", nbytes=float(H * W))    # per pass: the map is read once, promoted bytes written
+    _call("ed_canny_hysteresis", p_map, H, W, _dev(ws, torch.int32, "workspace"), ctypes.addressof(passes), _stream())
+    return cmap, int(passes.value)
+
+
+def canny_edges(cmap, out="u8"):
+    """uint8 map [H,W] -> ``out="u8"``: uint8 [H,W,3], 255 where the map is 2, else 0; ``out="cond"``: fp32 [1,3,H,W] with 1.0 / 0.0
+    (the ControlNet condition tensor of that image).  See ed_canny_edges."""
+    if out not in ("u8", "cond"):
+        raise ValueError(f"out must be 'u8' or 'cond', got {out!r}")
+    p_map = _dev(cmap, torch.uint8, "map")
+    H, W, _ = _canny_dims(cmap, "map", (1,))
+    if cmap.dim() != 2:
+        _reject(f"map must be [H,W], got {tuple(cmap.shape)}")
+    if out == "u8":
+        res = torch.empty((H, W, 3), dtype=torch.uint8, device=cmap.device)
+        TIMER.note_work("ed_canny_edges", nbytes=float(4 * H * W))
+        _call("ed_canny_edges", p_map, H, W, _dev(res, torch.uint8, "edges"), None, _stream())
+    else:
+        res = torch.empty((1, 3, H, W), dtype=torch.float32, device=cmap.device)
+        TIMER.note_work("ed_canny_edges", nbytes=float(13 * H * W))
+        _call("ed_canny_edges", p_map, H, W, None, _dev(res, torch.float32, "cond"), _stream())
+    return res
+
+
+def canny(img, low=100, high=200, out="u8"):
+    """cv2.Canny(img, low, high) (aperture 3, L1 gradient) of a uint8 HWC image on the device, replicated to three channels:
+    ``out="u8"`` -> uint8 [H,W,3] (255 / 0), ``out="cond"`` -> fp32 [1,3,H,W] (1.0 / 0.0).  EDC:1105-1108."""
+    if out not in ("u8", "cond"):
+        raise ValueError(f"out must be 'u8' or 'cond', got {out!r}")
+    cmap, _ = canny_hysteresis(canny_map(img, low, high))
+    return canny_edges(cmap, out)

@@ -966,13 +966,19 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
     ``controlnet_model`` is the third positional constructor argument and ``condition_image`` /
     ``controlnet_conditioning_scale`` sit where the reference has them in ``generate_image``.
 
-    ``condition_image`` is the already pre-processed condition (float tensor (1,3,8h,8w) in [0,1] at the reduced
-    resolution, EDC:1183-1193; a PIL image / numpy array of that size is converted).  The canny / depth extraction of
-    ``process_condition_image`` (EDC:1102-1117: cv2 / a HF depth pipeline) is pre-processing outside the loop and out
-    of scope; ``process_condition_image`` raises with that explanation."""
+    ``generate_image(condition_image=...)`` takes the already pre-processed condition (float tensor (1,3,8h,8w) in [0,1]
+    at the reduced resolution, EDC:1183-1193; a PIL image / numpy array of that size is converted).  A raw photo goes
+    through ``prepare_condition_image`` (the reference command line's three lines, EDC:1391-1393) or, already resized,
+    through ``process_condition_image`` (EDC:1102-1117) first:
+
+    * ``'canny'`` is ``cv2.Canny(img, 100, 200)`` replicated to three channels, computed on the device by the HIP
+      kernels of csrc/canny_kernels.hip (``ops.canny``; the algorithm is written out in DESIGN.md);
+    * ``'depth'`` calls the ``depth_estimator=`` callable given to the constructor (the reference builds a HF
+      ``pipeline('depth-estimation')`` there, EDC:186); without one it raises ``NotImplementedError``.
+    """
 
     def __init__(self, device, sd_version="2.0", controlnet_model="canny", verbose=False, log_freq=5,
-                 view_batch_size=1, low_vram=False, *, controlnet=None, **kw):
+                 view_batch_size=1, low_vram=False, *, controlnet=None, depth_estimator=None, **kw):
         if controlnet is None:
             from .models import build_models
             dev = torch.device(device)
@@ -982,10 +988,43 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
             kw.setdefault("vae", vae)
         super().__init__(device, sd_version, verbose, log_freq, view_batch_size, low_vram, controlnet=controlnet, **kw)
         self.controlnet_model = controlnet_model
+        self.depth_estimator = depth_estimator
 
-    def process_condition_image(self, condition_image, controlnet_model):
-        raise NotImplementedError("canny / depth extraction (EDC:1102-1117) is pre-processing outside the hot path; "
-                                  "pass the processed condition image to generate_image")
+    def process_condition_image(self, condition_image, controlnet_model, *, output_type="pil"):
+        """EDC:1102-1117: a PIL image (or HWC uint8 array) at the reduced resolution -> the ControlNet condition, a PIL RGB
+        image with three identical channels.  ``output_type="pt"`` (extra) returns the fp32 (1,3,H,W) condition tensor on
+        the pipeline's device instead, without the PIL round trip."""
+        assert controlnet_model in ["canny", "depth"], f"processing for ControlNet: {controlnet_model} is not implemented"
+        if output_type not in ("pil", "pt"):
+            raise ValueError(f"output_type must be 'pil' or 'pt', got {output_type!r}")
+        from PIL import Image
+        if controlnet_model == "canny":
+            if hasattr(condition_image, "convert") and condition_image.mode not in ("L", "RGB"):
+                condition_image = condition_image.convert("RGB")
+            arr = np.array(condition_image)
+            if arr.dtype != np.uint8 or arr.ndim not in (2, 3):
+                raise TypeError(f"canny needs an 8-bit image (PIL, or uint8 [H,W,C] / [H,W] array), got {arr.dtype} {arr.shape}")
+            img = torch.from_numpy(np.ascontiguousarray(arr)).to(self.device)
+            if output_type == "pt":
+                return ops.canny(img, 100, 200, out="cond")
+            return Image.fromarray(ops.canny(img, 100, 200, out="u8").cpu().numpy())
+        if self.depth_estimator is None:
+            raise NotImplementedError(
+                "depth extraction needs a depth estimator: construct with depth_estimator=<callable>, called as "
+                "depth_estimator(image)['depth'] -> single-channel image, e.g. transformers.pipeline('depth-estimation') "
+                "as the reference does (EDC:186, 1112)")
+        depth = np.array(self.depth_estimator(condition_image)["depth"])[:, :, None]
+        depth_image = Image.fromarray(np.concatenate([depth, depth, depth], axis=2))
+        if output_type == "pt":
+            return self._to_condition_tensor(depth_image, depth_image.size[1], depth_image.size[0]).to(self.device)
+        return depth_image
+
+    def prepare_condition_image(self, image, height, width):
+        """EDC:1391-1393, what the reference command line does with ``--condition_image``: resize the photo to the reduced
+        resolution of a ``height`` x ``width`` run (PIL's default filter, on the host), RGB, then ``process_condition_image``."""
+        ds = self.get_downsample_size(height, width)
+        image = image.resize((ds[1] * self.vae_scale_factor, ds[0] * self.vae_scale_factor)).convert("RGB")
+        return self.process_condition_image(image, self.controlnet_model)
 
     def _to_condition_tensor(self, image, h_px, w_px):
         if isinstance(image, torch.Tensor):

@@ -8,7 +8,8 @@
  * replaces.  INTEGRATION.md shows the ctypes stub a reference maintainer would add.
  *
  * Conventions (all entry points):
- *   - return value: hipError_t as int (0 == hipSuccess); never throws, never allocates, never synchronises;
+ *   - return value: hipError_t as int (0 == hipSuccess); never throws, never allocates, never synchronises (one exception:
+ *     ed_canny_hysteresis, pre-processing outside the loop, see there);
  *   - every pointer is a DEVICE pointer owned by the caller (torch tensors), NCHW contiguous unless stated;
  *   - `stream` is a hipStream_t passed as void* (torch.cuda.current_stream().cuda_stream); NULL = default stream;
  *   - "dtype" arguments: ED_F32 / ED_F16 / ED_BF16 select the element type of the buffer crossing the torch model
@@ -450,6 +451,29 @@ int ed_conv3x3_nhwc_f32out(const void* x, const void* w, const float* bias, cons
  */
 int ed_conv3x3_nhwc_f32out_s2(const void* x, const void* w, const float* bias, float* out, int dtype, int B, int H, int W, int Cin, int N,
                               float out_scale, const float* act_absmax, void* stream);
+
+/*
+ * ---- Canny condition extraction (csrc/canny_kernels.hip): EDC:1102-1110, cv2.Canny(img, 100, 200) of the ControlNet variant's
+ * process_condition_image.  The algorithm is OpenCV 4.x cv::Canny(apertureSize = 3, L2gradient = false) for 8-bit input (DESIGN.md
+ * "Canny condition extraction"); all arithmetic is integer, the result is exact.  C in {1, 3}, 1 <= H, W <= 8192, anything else is
+ * hipErrorInvalidValue without a launch.  Three stages, separate so that each can be tested alone:
+ *
+ * ed_canny_map -- img uint8 [H, W, C] -> map uint8 [H, W]: Sobel 3x3 (replicated border), |dx| + |dy|, the channel of the largest
+ *   magnitude (lowest index on ties), non-maximum suppression, thresholds low / high (already floored; swapped when low > high).
+ *   Map codes as in OpenCV: 1 = not an edge, 0 = candidate (low < m <= high), 2 = strong (m > high).
+ * ed_canny_hysteresis -- in place: every candidate that is 8-connected through candidates to a strong pixel becomes 2.  One launch
+ *   floods each 64 x 32 tile inside LDS; the host relaunches until a pass promotes nothing and reports the number of passes in
+ *   *passes_out (a HOST int32).  THIS ENTRY POINT SYNCHRONISES THE STREAM once per pass to read the "changed" word: it is pre-processing
+ *   of one image before the loop starts and must not be called while the stream is being captured into a graph.  workspace:
+ *   ed_canny_workspace bytes of device memory.  More than H W + 1 passes (impossible for a monotone flood: every pass but the last
+ *   promotes a pixel) returns hipErrorUnknown rather than a truncated result.
+ * ed_canny_edges -- map -> edges uint8 [H, W, 3] (255 where map == 2, else 0) and / or cond fp32 [1, 3, H, W] (1.0 / 0.0: what the
+ *   pipeline makes of that image); either may be NULL, not both.
+ */
+int64_t ed_canny_workspace(int H, int W, int C);
+int ed_canny_map(const uint8_t* img, int H, int W, int C, int low, int high, uint8_t* map, void* stream);
+int ed_canny_hysteresis(uint8_t* map, int H, int W, void* workspace, int32_t* passes_out, void* stream);
+int ed_canny_edges(const uint8_t* map, int H, int W, uint8_t* edges, float* cond, void* stream);
 
 #ifdef __cplusplus
 }
