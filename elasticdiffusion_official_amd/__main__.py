@@ -10,7 +10,9 @@ text_encoder*/ ...); without it the architecture is randomly initialised and the
 ``type=bool`` treats every non-empty string as True).  ``--condition_image FILE`` selects the ControlNet pipeline and is
 the already extracted condition by default; ``--process_condition true`` treats it as a raw photo like the reference's
 flag of the same name (resize to the reduced resolution, canny on the device / injected depth estimator) and saves the
-extracted condition as ``condition.png``.
+extracted condition as ``condition.png``.  ``--prediction_type``, ``--timestep_spacing`` and
+``--rescale_betas_zero_snr`` override what the snapshot's ``scheduler/scheduler_config.json`` says (or the SD defaults
+without ``--weights``); the reference takes these from the hub config only.
 """
 import argparse
 import os
@@ -58,6 +60,12 @@ def main(argv=None):
                     "and extract the canny / depth condition from it as the reference command line does (EDC:1390-1393)")
     ap.add_argument("--controlnet_conditioning_scale", type=float, default=0.2)
     ap.add_argument("--controlnet_model", type=str, default="depth")
+    ap.add_argument("--prediction_type", type=str, default=None, choices=["epsilon", "v_prediction"],
+                    help="what the UNet predicts; default: the snapshot's scheduler_config.json, else epsilon")
+    ap.add_argument("--timestep_spacing", type=str, default=None, choices=["leading", "linspace", "trailing"],
+                    help="default: the snapshot's scheduler_config.json, else leading")
+    ap.add_argument("--rescale_betas_zero_snr", type=_bool, default=None,
+                    help="zero terminal SNR betas; default: the snapshot's scheduler_config.json, else false")
     opt = ap.parse_args(argv)
 
     from . import ElasticDiffusion, ElasticDiffusionControlNet
@@ -69,6 +77,11 @@ def main(argv=None):
         from .text import load_clip
         kw["weights"] = opt.weights
         kw["text_encoder"] = load_clip(opt.weights, opt.sd_version.startswith("XL"), device)
+    sched = dict(prediction_type=opt.prediction_type, timestep_spacing=opt.timestep_spacing,
+                 rescale_betas_zero_snr=opt.rescale_betas_zero_snr)
+    if any(v is not None for v in sched.values()):  # a given flag overrides the snapshot's value / the default
+        from .schedule import DDIMSchedule
+        kw["scheduler"] = DDIMSchedule.from_config_dir(opt.weights, **sched)
     extra = {}
     if opt.condition_image:
         from PIL import Image

@@ -18,7 +18,7 @@ SOURCES = [os.path.join(PKG_DIR, "csrc", n) for n in ("elastic_kernels.hip", "un
 SRC = SOURCES[0]
 INCLUDE = os.path.join(ROOT_DIR, "include")
 SO_PATH = os.path.join(PKG_DIR, "libelastic_hip.so")
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
 
@@ -77,6 +77,11 @@ SIGNATURES = {
     "ed_canny_map": [_vp, _i, _i, _i, _i, _i, _vp, _vp],
     "ed_canny_hysteresis": [_vp, _i, _i, _vp, _vp, _vp],
     "ed_canny_edges": [_vp, _i, _i, _vp, _vp, _vp],
+    "ed_cfg_ddim_step_pt": [_vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i64, _i, _vp],
+    "ed_rrg_update_pt": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "ed_phase_epilogue_pt": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                             _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f,
+                             _f, _f, _i, _vp],
 }
 
 _LIB = None

@@ -15,7 +15,7 @@
 
 #include "elastic_hip.h"
 
-#define ED_ABI_VERSION 10
+#define ED_ABI_VERSION 11
 #define ED_BLOCK 256
 
 namespace {
@@ -424,13 +424,26 @@ k_fill_directions(const float* __restrict__ dirs, const int8_t* __restrict__ sta
 }
 
 // ---- ed_cfg_ddim_step ------------------------------------------------------------------------------
+// VP = the scheduler's prediction_type is "v_prediction": the guided model output m = l + g*d (formed in model-output
+// space either way, ED:1031) is a velocity, x0 = sa*x - sb*m and eps = sa*m + sb*x (every product rounded on its own, in
+// diffusers' order); otherwise m is the noise and x0 = (x - sb*m) / sa.  A compile-time variant: the epsilon
+// instantiations are the code they were before the variant existed.
+template <bool VP>
+__device__ __forceinline__ float pred_x0(float m, float xv, float sb, float sa) {
+  if (VP) return __fsub_rn(__fmul_rn(sa, xv), __fmul_rn(sb, m));
+  return __fdiv_rn(__fsub_rn(xv, __fmul_rn(sb, m)), sa);
+}
+
+template <bool VP>
 __device__ __forceinline__ void ddim_one(float l, float d, float xv, float g, float sb, float sa, float sp, float sd,
                                          float& prev, float& x0) {
-  float eps = __fadd_rn(l, __fmul_rn(g, d));
-  x0 = __fdiv_rn(__fsub_rn(xv, __fmul_rn(sb, eps)), sa);
+  float m = __fadd_rn(l, __fmul_rn(g, d));
+  x0 = pred_x0<VP>(m, xv, sb, sa);
+  float eps = VP ? __fadd_rn(__fmul_rn(sa, m), __fmul_rn(sb, xv)) : m;
   prev = __fadd_rn(__fmul_rn(sp, x0), __fmul_rn(sd, eps));
 }
 
+template <bool VP>
 __global__ void __launch_bounds__(ED_BLOCK)
 k_cfg_ddim_v4(const float4* __restrict__ local, const float4* __restrict__ dir, const float4* __restrict__ x,
               float4* __restrict__ prev, float4* __restrict__ x0, float g, float sb, float sa, float sp, float sd,
@@ -438,14 +451,15 @@ k_cfg_ddim_v4(const float4* __restrict__ local, const float4* __restrict__ dir, 
   int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
   if (t >= n4) return;
   float4 l = local[t], d = dir[t], xv = x[t], p, o;
-  ddim_one(l.x, d.x, xv.x, g, sb, sa, sp, sd, p.x, o.x);
-  ddim_one(l.y, d.y, xv.y, g, sb, sa, sp, sd, p.y, o.y);
-  ddim_one(l.z, d.z, xv.z, g, sb, sa, sp, sd, p.z, o.z);
-  ddim_one(l.w, d.w, xv.w, g, sb, sa, sp, sd, p.w, o.w);
+  ddim_one<VP>(l.x, d.x, xv.x, g, sb, sa, sp, sd, p.x, o.x);
+  ddim_one<VP>(l.y, d.y, xv.y, g, sb, sa, sp, sd, p.y, o.y);
+  ddim_one<VP>(l.z, d.z, xv.z, g, sb, sa, sp, sd, p.z, o.z);
+  ddim_one<VP>(l.w, d.w, xv.w, g, sb, sa, sp, sd, p.w, o.w);
   prev[t] = p;
   x0[t] = o;
 }
 
+template <bool VP>
 __global__ void __launch_bounds__(ED_BLOCK)
 k_cfg_ddim_s(const float* __restrict__ local, const float* __restrict__ dir, const float* __restrict__ x,
              float* __restrict__ prev, float* __restrict__ x0, float g, float sb, float sa, float sp, float sd,
@@ -453,7 +467,7 @@ k_cfg_ddim_s(const float* __restrict__ local, const float* __restrict__ dir, con
   int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
   if (t >= n) return;
   float p, o;
-  ddim_one(local[t], dir[t], x[t], g, sb, sa, sp, sd, p, o);
+  ddim_one<VP>(local[t], dir[t], x[t], g, sb, sa, sp, sd, p, o);
   prev[t] = p;
   x0[t] = o;
 }
@@ -529,7 +543,7 @@ __device__ __forceinline__ float direction_at(const EpilogueArgs& a, int b, int 
   return __fsub_rn(cd, u);
 }
 
-template <typename Tag>
+template <typename Tag, bool VP>
 __global__ void __launch_bounds__(ED_BLOCK)
 k_phase_epilogue(const EpilogueArgs a) {
   const int64_t nfull = (int64_t)a.B * a.C * a.H * a.W;
@@ -578,7 +592,7 @@ k_phase_epilogue(const EpilogueArgs a) {
   }
   float d = direction_at<Tag>(a, b, c, Y, X);
   float pv, z0;
-  ddim_one(loc, d, a.x[t], a.g, a.sb, a.sa, a.sp, a.sd, pv, z0);
+  ddim_one<VP>(loc, d, a.x[t], a.g, a.sb, a.sa, a.sp, a.sd, pv, z0);
   a.prev[t] = pv;
   a.x0[t] = z0;
   if (a.direction) a.direction[t] = d;
@@ -589,8 +603,8 @@ k_phase_epilogue(const EpilogueArgs a) {
     int64_t e = ((int64_t)c * a.gPH + (i + a.g_off_y)) * a.gPW + (j + a.g_off_x);
     float lu = ld<Tag>(a.g_out, (((int64_t)(a.K - 1) * 2 + 0) * a.B + b) * a.C * plane + e);
     float ldir = direction_at<Tag>(a, b, c, a.down_row[i], a.down_col[j]);
-    float eps = __fadd_rn(lu, __fmul_rn(a.g, ldir));
-    float up = __fdiv_rn(__fsub_rn(a.low_latent[(((int64_t)b * a.C + c) * a.h + i) * a.w + j], __fmul_rn(a.sb, eps)), a.sa);
+    float m = __fadd_rn(lu, __fmul_rn(a.g, ldir));
+    float up = pred_x0<VP>(m, a.low_latent[(((int64_t)b * a.C + c) * a.h + i) * a.w + j], a.sb, a.sa);
     float grad = __fmul_rn(__fmul_rn(a.rrg_norm, __fsub_rn(z0, up)), a.rrg_weight);
     a.x_next[t] = __fadd_rn(pv, -grad);
   }
@@ -641,6 +655,7 @@ k_undo_s(const float* __restrict__ x_in, const float* __restrict__ noise, const 
 }
 
 // ---- ed_rrg_update ---------------------------------------------------------------------------------
+template <bool VP>
 __global__ void __launch_bounds__(ED_BLOCK)
 k_rrg_update(const float* __restrict__ prev, const float* __restrict__ x0, const float* __restrict__ low_latent,
              const float* __restrict__ low_uncond, const float* __restrict__ low_dir,
@@ -654,12 +669,13 @@ k_rrg_update(const float* __restrict__ prev, const float* __restrict__ x0, const
   int Y = (int)(r % H);
   int64_t bc = r / H;
   int64_t s = (bc * h + up_row[Y]) * w + up_col[X];
-  float eps = __fadd_rn(low_uncond[s], __fmul_rn(g, low_dir[s]));
-  float up = __fdiv_rn(__fsub_rn(low_latent[s], __fmul_rn(sb, eps)), sa);
+  float m = __fadd_rn(low_uncond[s], __fmul_rn(g, low_dir[s]));
+  float up = pred_x0<VP>(m, low_latent[s], sb, sa);
   float grad = __fmul_rn(__fmul_rn(norm, __fsub_rn(x0[t], up)), weight);  // d/dx0 of weight*mse(up, x0)
   out[t] = __fadd_rn(prev[t], -grad);
 }
 
+template <bool VP>
 __global__ void __launch_bounds__(ED_BLOCK)
 k_rrg_update_x4(const float* __restrict__ prev, const float* __restrict__ x0, const float* __restrict__ low_latent,
                 const float* __restrict__ low_uncond, const float* __restrict__ low_dir,
@@ -680,8 +696,8 @@ k_rrg_update_x4(const float* __restrict__ prev, const float* __restrict__ x0, co
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     int64_t s = base + up_col[X + e];
-    float eps = __fadd_rn(low_uncond[s], __fmul_rn(g, low_dir[s]));
-    float up = __fdiv_rn(__fsub_rn(low_latent[s], __fmul_rn(sb, eps)), sa);
+    float m = __fadd_rn(low_uncond[s], __fmul_rn(g, low_dir[s]));
+    float up = pred_x0<VP>(m, low_latent[s], sb, sa);
     float grad = __fmul_rn(__fmul_rn(norm, __fsub_rn(zv[e], up)), weight);
     o[e] = __fadd_rn(pv[e], -grad);
   }
@@ -757,6 +773,12 @@ k_tile_accumulate(const void* __restrict__ dec, float* __restrict__ image, int B
     default: return (int)hipErrorInvalidValue;                                                   \
   }
 #define ED_LAUNCH(KERNEL, n, ...) KERNEL<<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(__VA_ARGS__)
+// prediction-type variants: <false> = epsilon, <true> = v_prediction
+#define ED_LAUNCH_VP(vp, KERNEL, n, ...)                                               \
+  do {                                                                                 \
+    if (vp) KERNEL<true><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(__VA_ARGS__);   \
+    else KERNEL<false><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(__VA_ARGS__);     \
+  } while (0)
 
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
@@ -851,7 +873,7 @@ int ed_assemble_rows(const float* latent, int B, int C, int H, int W, const uint
   return done();
 }
 
-int ed_phase_epilogue(const void* g_out, const void* v_out, int dtype, const float* x, const int8_t* stamp,
+static int phase_epilogue_launch(bool vp, const void* g_out, const void* v_out, int dtype, const float* x, const int8_t* stamp,
                       const int32_t* inv_row, const int32_t* inv_col, const int32_t* up_row, const int32_t* up_col,
                       const int32_t* down_row, const int32_t* down_col, const int32_t* row_blk, const int32_t* row_src,
                       const int32_t* col_blk, const int32_t* col_src, const float* low_latent, float* prev, float* x0,
@@ -872,8 +894,49 @@ int ed_phase_epilogue(const void* g_out, const void* v_out, int dtype, const flo
   a.g_off_x = g_off_x, a.vPH = vPH, a.vPW = vPW, a.ncb = n_col_blocks;
   a.g = g, a.sb = sqrt_beta_t, a.sa = sqrt_alpha_t, a.sp = sqrt_alpha_prev, a.sd = sqrt_1m_alpha_prev;
   a.rrg_norm = rrg_norm, a.rrg_weight = rrg_weight;
-  ED_LAUNCH_T(dtype, k_phase_epilogue, n, a);
+#define ED_EPI(T)                                                                           \
+  if (vp) k_phase_epilogue<T, true><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(a);  \
+  else k_phase_epilogue<T, false><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(a);
+  switch (dtype) {
+    case ED_F32: ED_EPI(F32) break;
+    case ED_F16: ED_EPI(F16) break;
+    case ED_BF16: ED_EPI(BF16) break;
+    default: return (int)hipErrorInvalidValue;
+  }
+#undef ED_EPI
   return done();
+}
+
+static inline bool bad_prediction_type(int pt) { return pt != ED_PRED_EPSILON && pt != ED_PRED_V; }
+
+int ed_phase_epilogue(const void* g_out, const void* v_out, int dtype, const float* x, const int8_t* stamp,
+                      const int32_t* inv_row, const int32_t* inv_col, const int32_t* up_row, const int32_t* up_col,
+                      const int32_t* down_row, const int32_t* down_col, const int32_t* row_blk, const int32_t* row_src,
+                      const int32_t* col_blk, const int32_t* col_src, const float* low_latent, float* prev, float* x0,
+                      float* x_next, float* low_dir, float* uncond_last, float* direction, float* local, int K, int B,
+                      int C, int H, int W, int h, int w, int gPH, int gPW, int g_off_y, int g_off_x, int vPH, int vPW,
+                      int n_col_blocks, float g, float sqrt_beta_t, float sqrt_alpha_t, float sqrt_alpha_prev,
+                      float sqrt_1m_alpha_prev, float rrg_norm, float rrg_weight, void* stream) {
+  return phase_epilogue_launch(false, g_out, v_out, dtype, x, stamp, inv_row, inv_col, up_row, up_col, down_row, down_col,
+                               row_blk, row_src, col_blk, col_src, low_latent, prev, x0, x_next, low_dir, uncond_last,
+                               direction, local, K, B, C, H, W, h, w, gPH, gPW, g_off_y, g_off_x, vPH, vPW, n_col_blocks, g,
+                               sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev, sqrt_1m_alpha_prev, rrg_norm, rrg_weight, stream);
+}
+
+int ed_phase_epilogue_pt(const void* g_out, const void* v_out, int dtype, const float* x, const int8_t* stamp,
+                         const int32_t* inv_row, const int32_t* inv_col, const int32_t* up_row, const int32_t* up_col,
+                         const int32_t* down_row, const int32_t* down_col, const int32_t* row_blk, const int32_t* row_src,
+                         const int32_t* col_blk, const int32_t* col_src, const float* low_latent, float* prev, float* x0,
+                         float* x_next, float* low_dir, float* uncond_last, float* direction, float* local, int K, int B,
+                         int C, int H, int W, int h, int w, int gPH, int gPW, int g_off_y, int g_off_x, int vPH, int vPW,
+                         int n_col_blocks, float g, float sqrt_beta_t, float sqrt_alpha_t, float sqrt_alpha_prev,
+                         float sqrt_1m_alpha_prev, float rrg_norm, float rrg_weight, int prediction_type, void* stream) {
+  if (bad_prediction_type(prediction_type)) return (int)hipErrorInvalidValue;
+  return phase_epilogue_launch(prediction_type == ED_PRED_V, g_out, v_out, dtype, x, stamp, inv_row, inv_col, up_row, up_col,
+                               down_row, down_col, row_blk, row_src, col_blk, col_src, low_latent, prev, x0, x_next, low_dir,
+                               uncond_last, direction, local, K, B, C, H, W, h, w, gPH, gPW, g_off_y, g_off_x, vPH, vPW,
+                               n_col_blocks, g, sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev, sqrt_1m_alpha_prev, rrg_norm,
+                               rrg_weight, stream);
 }
 
 int ed_unpad_direction(const void* unet_out, int dtype, float* dirs, float* uncond_last, int K, int B, int C, int h,
@@ -900,18 +963,33 @@ int ed_fill_directions(const float* dirs, const int8_t* stamp, const int32_t* in
   return done();
 }
 
+static int cfg_ddim_launch(bool vp, const float* local, const float* direction, const float* x, float* prev, float* x0, float g,
+                           float sqrt_beta_t, float sqrt_alpha_t, float sqrt_alpha_prev, float sqrt_one_minus_alpha_prev,
+                           int64_t n, void* stream) {
+  if (n == 0) return 0;
+  if ((n & 3) == 0 && aligned16(local) && aligned16(direction) && aligned16(x) && aligned16(prev) && aligned16(x0)) {
+    ED_LAUNCH_VP(vp, k_cfg_ddim_v4, n / 4, (const float4*)local, (const float4*)direction, (const float4*)x, (float4*)prev,
+                 (float4*)x0, g, sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev, sqrt_one_minus_alpha_prev, n / 4);
+  } else {
+    ED_LAUNCH_VP(vp, k_cfg_ddim_s, n, local, direction, x, prev, x0, g, sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev,
+                 sqrt_one_minus_alpha_prev, n);
+  }
+  return done();
+}
+
 int ed_cfg_ddim_step(const float* local, const float* direction, const float* x, float* prev, float* x0, float g,
                      float sqrt_beta_t, float sqrt_alpha_t, float sqrt_alpha_prev, float sqrt_one_minus_alpha_prev,
                      int64_t n, void* stream) {
-  if (n == 0) return 0;
-  if ((n & 3) == 0 && aligned16(local) && aligned16(direction) && aligned16(x) && aligned16(prev) && aligned16(x0)) {
-    ED_LAUNCH(k_cfg_ddim_v4, n / 4, (const float4*)local, (const float4*)direction, (const float4*)x, (float4*)prev, (float4*)x0, g,
-                       sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev, sqrt_one_minus_alpha_prev, n / 4);
-  } else {
-    ED_LAUNCH(k_cfg_ddim_s, n, local, direction, x,
-                       prev, x0, g, sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev, sqrt_one_minus_alpha_prev, n);
-  }
-  return done();
+  return cfg_ddim_launch(false, local, direction, x, prev, x0, g, sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev,
+                         sqrt_one_minus_alpha_prev, n, stream);
+}
+
+int ed_cfg_ddim_step_pt(const float* local, const float* direction, const float* x, float* prev, float* x0, float g,
+                        float sqrt_beta_t, float sqrt_alpha_t, float sqrt_alpha_prev, float sqrt_one_minus_alpha_prev,
+                        int64_t n, int prediction_type, void* stream) {
+  if (bad_prediction_type(prediction_type)) return (int)hipErrorInvalidValue;
+  return cfg_ddim_launch(prediction_type == ED_PRED_V, local, direction, x, prev, x0, g, sqrt_beta_t, sqrt_alpha_t,
+                         sqrt_alpha_prev, sqrt_one_minus_alpha_prev, n, stream);
 }
 
 int ed_undo_step(const float* x_in, const float* noise, const float* coef, float* x_out, int n_sub, int64_t n,
@@ -927,22 +1005,38 @@ int ed_undo_step(const float* x_in, const float* noise, const float* coef, float
   return done();
 }
 
-int ed_rrg_update(const float* prev, const float* x0, const float* low_latent, const float* low_uncond,
-                  const float* low_dir, const int32_t* up_row, const int32_t* up_col, float* out, float g,
-                  float sqrt_beta_t, float sqrt_alpha_t, float norm, float weight, int B, int C, int H, int W, int h,
-                  int w, void* stream) {
+static int rrg_update_launch(bool vp, const float* prev, const float* x0, const float* low_latent, const float* low_uncond,
+                             const float* low_dir, const int32_t* up_row, const int32_t* up_col, float* out, float g,
+                             float sqrt_beta_t, float sqrt_alpha_t, float norm, float weight, int B, int C, int H, int W,
+                             int h, int w, void* stream) {
   int64_t n = (int64_t)B * C * H * W;
   if (n == 0) return 0;
   if ((W & 3) == 0 && aligned16(prev) && aligned16(x0) && aligned16(out)) {
     n >>= 2;
-    ED_LAUNCH(k_rrg_update_x4, n, prev, x0, low_latent, low_uncond, low_dir, up_row, up_col, out, g, sqrt_beta_t,
+    ED_LAUNCH_VP(vp, k_rrg_update_x4, n, prev, x0, low_latent, low_uncond, low_dir, up_row, up_col, out, g, sqrt_beta_t,
               sqrt_alpha_t, norm, weight, B, C, H, W, h, w);
     return done();
   }
-  ED_LAUNCH(k_rrg_update, n, prev, x0, low_latent,
-                     low_uncond, low_dir, up_row, up_col, out, g, sqrt_beta_t, sqrt_alpha_t, norm, weight, B, C, H, W,
-                     h, w);
+  ED_LAUNCH_VP(vp, k_rrg_update, n, prev, x0, low_latent, low_uncond, low_dir, up_row, up_col, out, g, sqrt_beta_t,
+               sqrt_alpha_t, norm, weight, B, C, H, W, h, w);
   return done();
+}
+
+int ed_rrg_update(const float* prev, const float* x0, const float* low_latent, const float* low_uncond,
+                  const float* low_dir, const int32_t* up_row, const int32_t* up_col, float* out, float g,
+                  float sqrt_beta_t, float sqrt_alpha_t, float norm, float weight, int B, int C, int H, int W, int h,
+                  int w, void* stream) {
+  return rrg_update_launch(false, prev, x0, low_latent, low_uncond, low_dir, up_row, up_col, out, g, sqrt_beta_t,
+                           sqrt_alpha_t, norm, weight, B, C, H, W, h, w, stream);
+}
+
+int ed_rrg_update_pt(const float* prev, const float* x0, const float* low_latent, const float* low_uncond,
+                     const float* low_dir, const int32_t* up_row, const int32_t* up_col, float* out, float g,
+                     float sqrt_beta_t, float sqrt_alpha_t, float norm, float weight, int B, int C, int H, int W, int h,
+                     int w, int prediction_type, void* stream) {
+  if (bad_prediction_type(prediction_type)) return (int)hipErrorInvalidValue;
+  return rrg_update_launch(prediction_type == ED_PRED_V, prev, x0, low_latent, low_uncond, low_dir, up_row, up_col, out, g,
+                           sqrt_beta_t, sqrt_alpha_t, norm, weight, B, C, H, W, h, w, stream);
 }
 
 int ed_gather2d(const void* in, int in_dtype, void* out, int out_dtype, int C, int H, int W, const int32_t* src_n,

@@ -191,12 +191,23 @@ def assemble_rows(latent, idx, src_row, src_col, g_rows, h, w, g_off_y, g_off_x,
           _dev(v_rows, None, "v_rows"), V, Sh, Sw, vPH, vPW, v_off_y, v_off_x, _code(g_rows, "g_rows"), _stream())
 
 
+PREDICTION_TYPES = {"epsilon": 0, "v_prediction": 1}  # ED_PRED_EPSILON / ED_PRED_V
+
+
+def _pred_code(prediction_type):
+    if prediction_type not in PREDICTION_TYPES:
+        _reject(f"prediction_type must be one of {sorted(PREDICTION_TYPES)}, got {prediction_type!r}")
+    return PREDICTION_TYPES[prediction_type]
+
+
 def phase_epilogue(g_out, v_out, x, stamp, pick_tables, view_tables, n_col_blocks, g_off, K, h, w, g, coef, prev, x0,
                    low_dir=None, uncond_last=None, direction=None, local=None, x_next=None, low_latent=None,
-                   rrg_norm=0.0, rrg_weight=0.0):
+                   rrg_norm=0.0, rrg_weight=0.0, prediction_type="epsilon"):
     """unpad_direction + fill_directions + scatter_centres + cfg_ddim_step (+ rrg_update when ``x_next`` is given) in
-    one launch (see ed_phase_epilogue).  pick_tables = (inv_row, inv_col, up_row, up_col, down_row, down_col);
-    view_tables = (row_blk, row_src, col_blk, col_src); coef = DDIMSchedule.step_coefficients(t)."""
+    one launch (see ed_phase_epilogue / ed_phase_epilogue_pt).  pick_tables = (inv_row, inv_col, up_row, up_col,
+    down_row, down_col); view_tables = (row_blk, row_src, col_blk, col_src); coef = DDIMSchedule.step_coefficients(t);
+    prediction_type = the scheduler's ("epsilon" or "v_prediction")."""
+    pt = _pred_code(prediction_type)
     B, C, H, W = x.shape
     gr, C2, gPH, gPW = g_out.shape
     vr, C3, vPH, vPW = v_out.shape
@@ -213,13 +224,14 @@ def phase_epilogue(g_out, v_out, x, stamp, pick_tables, view_tables, n_col_block
     if x_next is not None and low_latent is None:
         _reject("phase_epilogue: x_next (fused RRG) needs low_latent")
     f32 = torch.float32
-    _call("ed_phase_epilogue", _dev(g_out, None, "g_out"), _dev(v_out, None, "v_out"), _code(g_out, "g_out"),
+    _call("ed_phase_epilogue_pt" if pt else "ed_phase_epilogue",
+          _dev(g_out, None, "g_out"), _dev(v_out, None, "v_out"), _code(g_out, "g_out"),
           _dev(x, f32, "x"), _dev(stamp, torch.int8, "stamp"), *(_dev(t_, torch.int32) for t_ in pick_tables),
           *(_dev(t_, torch.int32) for t_ in view_tables), _opt(low_latent, f32, "low_latent"), _dev(prev, f32, "prev"),
           _dev(x0, f32, "x0"), _opt(x_next, f32, "x_next"), _opt(low_dir, f32, "low_dir"),
           _opt(uncond_last, f32, "uncond_last"), _opt(direction, f32, "direction"), _opt(local, f32, "local"),
           K, B, C, H, W, h, w, gPH, gPW, g_off[0], g_off[1], vPH, vPW, n_col_blocks, float(g), *(float(c) for c in coef),
-          float(rrg_norm), float(rrg_weight), _stream())
+          float(rrg_norm), float(rrg_weight), *((pt,) if pt else ()), _stream())
     return prev, x0
 
 
@@ -252,13 +264,16 @@ def fill_directions(dirs, stamp, inv_row, inv_col, up_row, up_col, down_row, dow
     return target
 
 
-def cfg_ddim_step(local, direction, x, prev, x0, g, sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev, sqrt_1m_alpha_prev):
+def cfg_ddim_step(local, direction, x, prev, x0, g, sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev, sqrt_1m_alpha_prev,
+                  prediction_type="epsilon"):
+    pt = _pred_code(prediction_type)
     n = x.numel()
     for t in (local, direction, prev, x0):
         assert t.numel() == n
-    _call("ed_cfg_ddim_step", _dev(local, torch.float32), _dev(direction, torch.float32), _dev(x, torch.float32),
+    _call("ed_cfg_ddim_step_pt" if pt else "ed_cfg_ddim_step",
+          _dev(local, torch.float32), _dev(direction, torch.float32), _dev(x, torch.float32),
           _dev(prev, torch.float32), _dev(x0, torch.float32), float(g), float(sqrt_beta_t),
-          float(sqrt_alpha_t), float(sqrt_alpha_prev), float(sqrt_1m_alpha_prev), n, _stream())
+          float(sqrt_alpha_t), float(sqrt_alpha_prev), float(sqrt_1m_alpha_prev), n, *((pt,) if pt else ()), _stream())
     return prev, x0
 
 
@@ -272,16 +287,19 @@ def undo_step(x_in, noise, coef, x_out):
     return x_out
 
 
-def rrg_update(prev, x0, low_latent, low_uncond, low_dir, up_row, up_col, out, g, sqrt_beta_t, sqrt_alpha_t, norm, weight):
+def rrg_update(prev, x0, low_latent, low_uncond, low_dir, up_row, up_col, out, g, sqrt_beta_t, sqrt_alpha_t, norm, weight,
+               prediction_type="epsilon"):
+    pt = _pred_code(prediction_type)
     B, C, H, W = prev.shape
     h, w = low_latent.shape[-2:]
     assert tuple(low_latent.shape) == (B, C, h, w) == tuple(low_uncond.shape) == tuple(low_dir.shape)
     assert up_row.numel() == H and up_col.numel() == W
-    _call("ed_rrg_update", _dev(prev, torch.float32), _dev(x0, torch.float32), _dev(low_latent, torch.float32),
+    _call("ed_rrg_update_pt" if pt else "ed_rrg_update",
+          _dev(prev, torch.float32), _dev(x0, torch.float32), _dev(low_latent, torch.float32),
           _dev(low_uncond, torch.float32), _dev(low_dir, torch.float32),
           _dev(up_row, torch.int32), _dev(up_col, torch.int32), _dev(out, torch.float32),
           float(g), float(sqrt_beta_t), float(sqrt_alpha_t), float(norm), float(weight),
-          B, C, H, W, h, w, _stream())
+          B, C, H, W, h, w, *((pt,) if pt else ()), _stream())
     return out
 
 

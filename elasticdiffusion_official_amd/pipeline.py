@@ -532,7 +532,8 @@ class ElasticDiffusion(nn.Module):
                                (P.gpad.top, P.gpad.left), K, P.h, P.w, np.float32(g), self._step_coef[ti], prev, x0,
                                low_dir=low_dir, uncond_last=uncond_last, direction=direction, local=local, x_next=x_next,
                                low_latent=low[K - 1] if rrg_w is not None else None, rrg_norm=rrg_norm,
-                               rrg_weight=0.0 if rrg_w is None else np.float32(rrg_w))
+                               rrg_weight=0.0 if rrg_w is None else np.float32(rrg_w),
+                               prediction_type=self.scheduler.config.prediction_type)
         else:
             dirs = torch.empty(K, B, C, P.h, P.w, device=dev, dtype=torch.float32)
             ops.unpad_direction(g_out, dirs, uncond_last, P.gpad.top, P.gpad.left)
@@ -541,7 +542,8 @@ class ElasticDiffusion(nn.Module):
                                 low_dir)
             local = torch.empty_like(x)
             ops.scatter_centres(v_out, local, P.views.n_col_blocks, P.row_blk, P.row_src, P.col_blk, P.col_src)
-            ops.cfg_ddim_step(local, direction, x, prev, x0, np.float32(g), *self._step_coef[ti])
+            ops.cfg_ddim_step(local, direction, x, prev, x0, np.float32(g), *self._step_coef[ti],
+                              prediction_type=self.scheduler.config.prediction_type)
         self.host_s["phase_total"] += time.perf_counter() - h0
         info = {"low_latent": low[K - 1], "uncond_score": uncond_last, "low_direction": low_dir,
                 "direction": direction, "local": local, "init_low": low[0], "x_next": x_next}
@@ -697,15 +699,19 @@ class ElasticDiffusion(nn.Module):
                     logs["x0"].append(x0.clone())
                     if rrg_w is not None:  # the reduced-resolution x0 the guidance pulls towards (ED:909-921)
                         sb, sa = self._step_coef[i][0], self._step_coef[i][1]
-                        eps = info["uncond_score"] + np.float32(cfg) * info["low_direction"]
-                        logs["rrg_x0"].append((info["low_latent"] - np.float32(sb) * eps) / np.float32(sa))
+                        out = info["uncond_score"] + np.float32(cfg) * info["low_direction"]
+                        if self.scheduler.config.prediction_type == "v_prediction":
+                            logs["rrg_x0"].append(np.float32(sa) * info["low_latent"] - np.float32(sb) * out)
+                        else:
+                            logs["rrg_x0"].append((info["low_latent"] - np.float32(sb) * out) / np.float32(sa))
             if info["x_next"] is not None:  # RRG already applied inside the fused epilogue
                 x = info["x_next"]
             elif rrg_w is not None:  # ED:1061-1078
                 sb, sa = self._step_coef[i][0], self._step_coef[i][1]
                 nxt = torch.empty_like(prev)
                 ops.rrg_update(prev, x0, info["low_latent"], info["uncond_score"], info["low_direction"], P.up_row,
-                               P.up_col, nxt, np.float32(cfg), sb, sa, S.norm, np.float32(w_i))
+                               P.up_col, nxt, np.float32(cfg), sb, sa, S.norm, np.float32(w_i),
+                               prediction_type=self.scheduler.config.prediction_type)
                 x = nxt
             else:
                 x = prev
@@ -870,7 +876,8 @@ class ElasticDiffusion(nn.Module):
             uncond, cnd = out[:B].contiguous(), out[B:].contiguous()
             prev, x0 = torch.empty_like(x), torch.empty_like(x)
             ops.cfg_ddim_step(uncond, (cnd - uncond).contiguous(), x, prev, x0, np.float32(guidance_scale),
-                              *self.scheduler.step_coefficients(t))
+                              *self.scheduler.step_coefficients(t),
+                              prediction_type=self.scheduler.config.prediction_type)
             x = prev
             if i % self.log_freq == 0:
                 inter.append(x0.cpu())

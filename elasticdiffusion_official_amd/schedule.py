@@ -5,6 +5,10 @@
 Only *scalars* are produced here -- every per-element operation of ``scheduler.step`` / ``add_noise`` /
 ``undo_step`` runs in libelastic_hip.so.  Scalars are computed with fp32 torch ops in the same order diffusers uses
 (``alphas_cumprod[t] ** 0.5`` etc.) so that the kernels reproduce the reference's torch-CPU results bit for bit.
+
+What a ``scheduler_config.json`` may say and is honoured (DESIGN.md section 14 writes the definitions out):
+``prediction_type`` epsilon / v_prediction, ``timestep_spacing`` leading / linspace / trailing and
+``rescale_betas_zero_snr``.  ``clip_sample``, thresholding and ``sample`` prediction are refused.
 """
 from types import SimpleNamespace
 
@@ -12,44 +16,68 @@ import numpy as np
 import torch
 
 
+PREDICTION_TYPES = ("epsilon", "v_prediction")
+TIMESTEP_SPACINGS = ("leading", "linspace", "trailing")
+
+
+def rescale_zero_terminal_snr(betas):
+    """diffusers' ``rescale_zero_terminal_snr`` (Lin et al. 2023, algorithm 1) in its fp32 operation order: shift and
+    scale sqrt(alpha_bar) so that the last timestep has exactly zero SNR and the first keeps its value."""
+    alphas_bar_sqrt = torch.cumprod(1.0 - betas, dim=0).sqrt()
+    first = alphas_bar_sqrt[0].clone()
+    last = alphas_bar_sqrt[-1].clone()
+    alphas_bar_sqrt -= last
+    alphas_bar_sqrt *= first / (first - last)
+    alphas_bar = alphas_bar_sqrt ** 2
+    alphas = torch.cat([alphas_bar[0:1], alphas_bar[1:] / alphas_bar[:-1]])
+    return 1 - alphas
+
+
 class DDIMSchedule:
     def __init__(self, num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
                  set_alpha_to_one=False, steps_offset=1, prediction_type="epsilon", timestep_spacing="leading",
-                 clip_sample=False):
-        if prediction_type != "epsilon":
-            raise NotImplementedError("the HIP DDIM kernel implements epsilon prediction (SD1.x/2.x-base/SDXL)")
+                 clip_sample=False, rescale_betas_zero_snr=False):
+        if prediction_type not in PREDICTION_TYPES:
+            raise NotImplementedError(f"prediction_type {prediction_type!r}: the HIP DDIM kernels implement "
+                                      f"{' / '.join(PREDICTION_TYPES)}")
         if clip_sample:
             raise NotImplementedError("clip_sample=True is not used by any SD / SDXL scheduler config")
-        if timestep_spacing != "leading":
-            raise NotImplementedError(timestep_spacing)
+        if timestep_spacing not in TIMESTEP_SPACINGS:
+            raise NotImplementedError(f"timestep_spacing {timestep_spacing!r}: one of {' / '.join(TIMESTEP_SPACINGS)}")
         self.config = SimpleNamespace(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
                                       beta_schedule=beta_schedule, set_alpha_to_one=set_alpha_to_one,
                                       steps_offset=steps_offset, prediction_type=prediction_type,
-                                      timestep_spacing=timestep_spacing, clip_sample=clip_sample)
+                                      timestep_spacing=timestep_spacing, clip_sample=clip_sample,
+                                      rescale_betas_zero_snr=bool(rescale_betas_zero_snr))
         if beta_schedule == "scaled_linear":
             self.betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=torch.float32) ** 2
         elif beta_schedule == "linear":
             self.betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=torch.float32)
         else:
             raise NotImplementedError(beta_schedule)
+        if rescale_betas_zero_snr:  # betas, alphas_cumprod and final_alpha_cumprod all come from the rescaled betas
+            self.betas = rescale_zero_terminal_snr(self.betas)
         self.alphas_cumprod = torch.cumprod(1.0 - self.betas, dim=0)
         self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
         self.num_inference_steps = None
         self.timesteps = None
 
     @classmethod
-    def from_config_dir(cls, model_dir):
+    def from_config_dir(cls, model_dir, **overrides):
         """``DDIMScheduler.from_pretrained(model_key, subfolder="scheduler")`` (ED:153) for a local HF snapshot: reads
         ``<model_dir>/scheduler/scheduler_config.json`` when present (keys this class does not know are ignored, values
-        it cannot honour -- v-prediction, trailing spacing -- raise NotImplementedError), defaults otherwise."""
+        it cannot honour -- clip_sample, sample prediction -- raise NotImplementedError), defaults otherwise.
+        ``overrides`` replace single keys of the file / the defaults (the command line's --prediction_type etc.); None
+        values are dropped."""
         import json
         import os
-        path = os.path.join(model_dir, "scheduler", "scheduler_config.json")
-        if not os.path.isfile(path):
-            return cls()
-        cfg = json.load(open(path))
+        path = None if model_dir is None else os.path.join(model_dir, "scheduler", "scheduler_config.json")
+        overrides = {k: v for k, v in overrides.items() if v is not None}
+        if model_dir is None or not os.path.isfile(path):
+            return cls(**overrides)
+        cfg = dict(json.load(open(path)), **overrides)
         known = ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "set_alpha_to_one", "steps_offset",
-                 "prediction_type", "timestep_spacing", "clip_sample")
+                 "prediction_type", "timestep_spacing", "clip_sample", "rescale_betas_zero_snr")
         return cls(**{k: cfg[k] for k in known if k in cfg})
 
     def set_timesteps(self, num_inference_steps):
@@ -57,17 +85,29 @@ class DDIMSchedule:
         if num_inference_steps > n:
             raise ValueError(f"num_inference_steps {num_inference_steps} > num_train_timesteps {n}")
         self.num_inference_steps = num_inference_steps
-        ratio = n // num_inference_steps
-        ts = (np.arange(0, num_inference_steps) * ratio).round()[::-1].copy().astype(np.int64)
-        self.timesteps = torch.from_numpy(ts + self.config.steps_offset)  # int64: str(t) == "tensor(981)"
+        spacing = self.config.timestep_spacing
+        if spacing == "linspace":
+            ts = np.linspace(0, n - 1, num_inference_steps).round()[::-1].copy().astype(np.int64)
+        elif spacing == "leading":
+            ratio = n // num_inference_steps
+            ts = (np.arange(0, num_inference_steps) * ratio).round()[::-1].copy().astype(np.int64)
+            ts = ts + self.config.steps_offset
+        else:  # trailing
+            ts = np.round(np.arange(n, 0, -n / num_inference_steps)).astype(np.int64) - 1
+        self.timesteps = torch.from_numpy(ts)  # int64: str(t) == "tensor(981)"
         return self.timesteps
 
     # ---- scalar tables ---------------------------------------------------------------------------
     def step_coefficients(self, t):
         """(sqrt(1-abar_t), sqrt(abar_t), sqrt(abar_prev), sqrt(1-abar_prev)) as python floats holding fp32 values."""
         t = int(t)
-        prev_t = t - self.config.num_train_timesteps // self.num_inference_steps
+        prev_t = t - self.config.num_train_timesteps // self.num_inference_steps  # for every spacing, as diffusers
         a_t = self.alphas_cumprod[t]
+        if self.config.prediction_type == "epsilon" and float(a_t) == 0.0:
+            raise ValueError(
+                f"timestep {t} has alpha_bar = 0 (rescale_betas_zero_snr) and the model predicts epsilon: the DDIM step "
+                "divides by sqrt(alpha_bar_t) = 0.  A zero-terminal-SNR schedule needs prediction_type='v_prediction' "
+                "(or a timestep spacing that does not visit the last training timestep)")
         a_prev = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
         sqrt_beta_t = (1 - a_t) ** 0.5
         sqrt_alpha_t = a_t ** 0.5

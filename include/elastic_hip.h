@@ -33,6 +33,9 @@ extern "C" {
 
 enum { ED_F32 = 0, ED_F16 = 1, ED_BF16 = 2 };
 
+/* "prediction_type" arguments of the *_pt entry points: what the scheduler config says the UNet predicts. */
+enum { ED_PRED_EPSILON = 0, ED_PRED_V = 1 };
+
 /* ABI version, bumped on any signature change. */
 int ed_version(void);
 
@@ -127,6 +130,19 @@ int ed_cfg_ddim_step(const float* local, const float* direction, const float* x,
                      float sqrt_one_minus_alpha_prev, int64_t n, void* stream);
 
 /*
+ * ed_cfg_ddim_step_pt -- ed_cfg_ddim_step with the scheduler's prediction type as an argument.  ED_PRED_EPSILON is
+ * ed_cfg_ddim_step itself (same kernels); ED_PRED_V reads the guided model output m = local + g * direction (formed in
+ * model-output space either way, ED:1031) as a velocity, diffusers' v_prediction branch, every product rounded on its own:
+ *   x0   = sqrt_alpha_t * x - sqrt_beta_t * m          eps = sqrt_alpha_t * m + sqrt_beta_t * x
+ *   prev = sqrt_alpha_prev * x0 + sqrt_one_minus_alpha_prev * eps
+ * No division by sqrt_alpha_t, so a zero-terminal-SNR timestep (alpha_bar_t = 0) is well defined.  Any other
+ * prediction_type value returns hipErrorInvalidValue.
+ */
+int ed_cfg_ddim_step_pt(const float* local, const float* direction, const float* x, float* prev, float* x0,
+                        float g, float sqrt_beta_t, float sqrt_alpha_t, float sqrt_alpha_prev,
+                        float sqrt_one_minus_alpha_prev, int64_t n, int prediction_type, void* stream);
+
+/*
  * ed_undo_step -- ED:692-704 RePaint re-noising: n_sub sequential x <- a_k * x + b_k * noise_k in registers.
  *   noise f32 [n_sub, n] (drawn on the host generator, parity);  coef f32 [n_sub,2] = (sqrt(1-beta), sqrt(beta))
  */
@@ -144,6 +160,16 @@ int ed_rrg_update(const float* prev, const float* x0, const float* low_latent, c
                   const float* low_dir, const int32_t* up_row, const int32_t* up_col, float* out,
                   float g, float sqrt_beta_t, float sqrt_alpha_t, float norm, float weight,
                   int B, int C, int H, int W, int h, int w, void* stream);
+
+/*
+ * ed_rrg_update_pt -- ed_rrg_update with the prediction type as an argument; with ED_PRED_V the reduced-resolution x0 is
+ *   x0_low = sqrt_alpha_t * low_latent - sqrt_beta_t * (low_uncond + g * low_dir)
+ * (scheduler.step's pred_original_sample at ED:920), the rest is unchanged.
+ */
+int ed_rrg_update_pt(const float* prev, const float* x0, const float* low_latent, const float* low_uncond,
+                     const float* low_dir, const int32_t* up_row, const int32_t* up_col, float* out,
+                     float g, float sqrt_beta_t, float sqrt_alpha_t, float norm, float weight,
+                     int B, int C, int H, int W, int h, int w, int prediction_type, void* stream);
 
 /*
  * ed_gather2d -- generic table-driven 2-D gather used for ED:868-883 nearest_interpolate, the ControlNet
@@ -306,6 +332,20 @@ int ed_phase_epilogue(const void* g_out, const void* v_out, int dtype, const flo
                       int C, int H, int W, int h, int w, int gPH, int gPW, int g_off_y, int g_off_x, int vPH, int vPW,
                       int n_col_blocks, float g, float sqrt_beta_t, float sqrt_alpha_t, float sqrt_alpha_prev,
                       float sqrt_1m_alpha_prev, float rrg_norm, float rrg_weight, void* stream);
+
+/*
+ * ed_phase_epilogue_pt -- ed_phase_epilogue with the prediction type as an argument (still one launch): the DDIM update
+ * is ed_cfg_ddim_step_pt's and the fused RRG term ed_rrg_update_pt's; bit-identical to that chain.  ED_PRED_EPSILON
+ * launches the kernels ed_phase_epilogue launches.
+ */
+int ed_phase_epilogue_pt(const void* g_out, const void* v_out, int dtype, const float* x, const int8_t* stamp,
+                         const int32_t* inv_row, const int32_t* inv_col, const int32_t* up_row, const int32_t* up_col,
+                         const int32_t* down_row, const int32_t* down_col, const int32_t* row_blk, const int32_t* row_src,
+                         const int32_t* col_blk, const int32_t* col_src, const float* low_latent, float* prev, float* x0,
+                         float* x_next, float* low_dir, float* uncond_last, float* direction, float* local, int K, int B,
+                         int C, int H, int W, int h, int w, int gPH, int gPW, int g_off_y, int g_off_x, int vPH, int vPW,
+                         int n_col_blocks, float g, float sqrt_beta_t, float sqrt_alpha_t, float sqrt_alpha_prev,
+                         float sqrt_1m_alpha_prev, float rrg_norm, float rrg_weight, int prediction_type, void* stream);
 
 /*
  * ed_flash_attention -- fused attention forward of the UNet's transformer blocks (what diffusers' AttnProcessor2_0
