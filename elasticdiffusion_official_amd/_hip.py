@@ -14,11 +14,11 @@ import torch  # noqa: F401  (must be imported before the .so so libamdhip64 is a
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT_DIR = os.path.dirname(PKG_DIR)
 SOURCES = [os.path.join(PKG_DIR, "csrc", n) for n in ("elastic_kernels.hip", "unet_kernels.hip", "attention_kernels.hip", "gemm_kernels.hip", "vae_kernels.hip",
-                                                       "canny_kernels.hip")]
+                                                       "canny_kernels.hip", "resize_kernels.hip")]
 SRC = SOURCES[0]
 INCLUDE = os.path.join(ROOT_DIR, "include")
 SO_PATH = os.path.join(PKG_DIR, "libelastic_hip.so")
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
 
@@ -82,6 +82,8 @@ SIGNATURES = {
     "ed_phase_epilogue_pt": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                              _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f,
                              _f, _f, _i, _vp],
+    "ed_resize_rows_u8": [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp],
+    "ed_resize_cols_u8": [_vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
 }
 
 _LIB = None

@@ -15,7 +15,7 @@
 
 #include "elastic_hip.h"
 
-#define ED_ABI_VERSION 11
+#define ED_ABI_VERSION 12
 #define ED_BLOCK 256
 
 namespace {

@@ -1124,3 +1124,87 @@ def canny(img, low=100, high=200, out="u8"):
         raise ValueError(f"out must be 'u8' or 'cond', got {out!r}")
     cmap, _ = canny_hysteresis(canny_map(img, low, high))
     return canny_edges(cmap, out)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Pillow-exact resize of 8-bit images (csrc/resize_kernels.hip): the condition image before the loop, never graph-captured
+# ---------------------------------------------------------------------------------------------------------------------
+RESIZE_MAX_DIM = 8192
+_RESIZE_TABLES = {}
+
+
+def _resize_tables(device, key, make):
+    """Device copies of one axis' (coeff int32 [out, ksize], bounds int32 [out, 2]), cached per device and ``key``."""
+    hit = _RESIZE_TABLES.get((device, key))
+    if hit is None:
+        if len(_RESIZE_TABLES) >= 64:
+            _RESIZE_TABLES.clear()
+        coeff, bounds = make()
+        hit = (torch.from_numpy(coeff.copy()).to(device), torch.from_numpy(bounds.copy()).to(device))
+        _RESIZE_TABLES[(device, key)] = hit
+    return hit
+
+
+def _identity_tables(n):
+    import numpy as np
+    from . import resample
+    coeff = np.full((n, 1), 1 << resample.PRECISION_BITS, np.int32)     # (2^21 + v 2^22) >> 22 == v
+    bounds = np.stack([np.arange(n, dtype=np.int32), np.ones(n, np.int32)], axis=1)
+    return coeff, bounds
+
+
+def resize_u8(img, size, filter="bicubic", out="u8"):
+    """``PIL.Image.resize((W_out, H_out), BICUBIC | LANCZOS)`` of an L / RGB image, bit for bit, on the device.
+
+    img uint8 [H,W,C] (C = 1 or 3) or [H,W], contiguous; ``size = (H_out, W_out)``.  ``out="u8"`` -> uint8 of the input's rank;
+    ``out="cond"`` -> fp32 [1,3,H_out,W_out] = bytes / 255 (one channel replicated), the ControlNet condition tensor of that image.
+    Horizontal pass (ed_resize_rows_u8) into a uint8 intermediate, then vertical pass (ed_resize_cols_u8); a pass whose size does
+    not change is skipped.  See include/elastic_hip.h and resample.py."""
+    from . import resample
+    if out not in ("u8", "cond"):
+        raise ValueError(f"out must be 'u8' or 'cond', got {out!r}")
+    if filter not in resample.FILTERS:
+        raise ValueError(f"filter must be one of {sorted(resample.FILTERS)}, got {filter!r}")
+    p_img = _dev(img, torch.uint8, "img")
+    H, W, C = _canny_dims(img, "img", (1, 3))
+    try:
+        Ho, Wo = (int(v) for v in size)
+    except (TypeError, ValueError):
+        _reject(f"size must be (H_out, W_out), got {size!r}")
+    if not (1 <= Ho <= RESIZE_MAX_DIM and 1 <= Wo <= RESIZE_MAX_DIM):
+        _reject(f"size: H_out and W_out must be in 1..{RESIZE_MAX_DIM}, got {Ho} x {Wo}")
+    dev = img.device
+    if (Ho, Wo) == (H, W) and out == "u8":
+        _LAUNCH["device"] = None
+        return img.clone()
+    passes = resample.plan((H, W), (Ho, Wo), filter)
+    src, rows, pitch = p_img, H, W * C
+    mid = None
+    if passes and passes[0][0] == "rows":
+        _, kh, _, y0, y1 = passes[0]
+        coeff, bounds = _resize_tables(dev, (W, Wo, filter), lambda: resample.coefficients(W, Wo, filter))
+        rows, mid_pitch = y1 - y0, (Wo * C + 3) // 4 * 4
+        mid = torch.empty((rows, mid_pitch), dtype=torch.uint8, device=dev)
+        TIMER.note_work("ed_resize_rows_u8", flops=2.0 * rows * Wo * C * kh.shape[1], nbytes=float(rows * (W * C + mid_pitch)))
+        _call("ed_resize_rows_u8", p_img + y0 * pitch, rows, W, C, pitch, _dev(coeff, torch.int32, "coeff"),
+              _dev(bounds, torch.int32, "bounds"), kh.shape[1], Wo, _dev(mid, torch.uint8, "intermediate"), mid_pitch, _stream())
+        src, pitch = _dev(mid, torch.uint8, "intermediate"), mid_pitch
+    if passes and passes[-1][0] == "cols":
+        _, kv, bv = passes[-1]
+        shift = int(bv[0, 0]) if len(passes) == 2 else None            # two passes: bounds are relative to the intermediate's first row
+        coeff, bounds = _resize_tables(dev, (H, Ho, filter, shift), lambda: (kv, bv))
+        ksz = kv.shape[1]
+    else:                                                               # width only (or a plain copy into "cond"): one tap of weight 1
+        coeff, bounds = _resize_tables(dev, (Ho, "identity"), lambda: _identity_tables(Ho))
+        ksz = 1
+    if out == "u8":
+        res = torch.empty((Ho, Wo) if img.dim() == 2 else (Ho, Wo, C), dtype=torch.uint8, device=dev)
+        p_u8, p_cond = _dev(res, torch.uint8, "out"), None
+    else:
+        res = torch.empty((1, 3, Ho, Wo), dtype=torch.float32, device=dev)
+        p_u8, p_cond = None, _dev(res, torch.float32, "out")
+    TIMER.note_work("ed_resize_cols_u8", flops=2.0 * Ho * Wo * C * ksz,
+                    nbytes=float(rows * Wo * C + Ho * Wo * (C if out == "u8" else 12)))
+    _call("ed_resize_cols_u8", src, rows, Wo * C, pitch, _dev(coeff, torch.int32, "coeff"), _dev(bounds, torch.int32, "bounds"),
+          ksz, Ho, C, p_u8, p_cond, _stream())
+    return res

@@ -975,8 +975,9 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
 
     ``generate_image(condition_image=...)`` takes the already pre-processed condition (float tensor (1,3,8h,8w) in [0,1]
     at the reduced resolution, EDC:1183-1193; a PIL image / numpy array of that size is converted).  A raw photo goes
-    through ``prepare_condition_image`` (the reference command line's three lines, EDC:1391-1393) or, already resized,
-    through ``process_condition_image`` (EDC:1102-1117) first:
+    through ``prepare_condition_image`` (the reference command line's three lines, EDC:1391-1393; its resize is Pillow's
+    bicubic, computed on the device by csrc/resize_kernels.hip) or, already resized, through ``process_condition_image``
+    (EDC:1102-1117) first:
 
     * ``'canny'`` is ``cv2.Canny(img, 100, 200)`` replicated to three channels, computed on the device by the HIP
       kernels of csrc/canny_kernels.hip (``ops.canny``; the algorithm is written out in DESIGN.md);
@@ -1006,12 +1007,15 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
             raise ValueError(f"output_type must be 'pil' or 'pt', got {output_type!r}")
         from PIL import Image
         if controlnet_model == "canny":
-            if hasattr(condition_image, "convert") and condition_image.mode not in ("L", "RGB"):
-                condition_image = condition_image.convert("RGB")
-            arr = np.array(condition_image)
-            if arr.dtype != np.uint8 or arr.ndim not in (2, 3):
-                raise TypeError(f"canny needs an 8-bit image (PIL, or uint8 [H,W,C] / [H,W] array), got {arr.dtype} {arr.shape}")
-            img = torch.from_numpy(np.ascontiguousarray(arr)).to(self.device)
+            if isinstance(condition_image, torch.Tensor):           # uint8 [H,W,C] / [H,W] already on the device (ops.canny checks it)
+                img = condition_image
+            else:
+                if hasattr(condition_image, "convert") and condition_image.mode not in ("L", "RGB"):
+                    condition_image = condition_image.convert("RGB")
+                arr = np.array(condition_image)
+                if arr.dtype != np.uint8 or arr.ndim not in (2, 3):
+                    raise TypeError(f"canny needs an 8-bit image (PIL, or uint8 [H,W,C] / [H,W] array), got {arr.dtype} {arr.shape}")
+                img = torch.from_numpy(np.ascontiguousarray(arr)).to(self.device)
             if output_type == "pt":
                 return ops.canny(img, 100, 200, out="cond")
             return Image.fromarray(ops.canny(img, 100, 200, out="u8").cpu().numpy())
@@ -1026,12 +1030,46 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
             return self._to_condition_tensor(depth_image, depth_image.size[1], depth_image.size[0]).to(self.device)
         return depth_image
 
-    def prepare_condition_image(self, image, height, width):
+    def _device_image(self, image):
+        """The source bytes of an image the resize kernels take -- an L / RGB PIL image, a uint8 [H,W,C] (C = 1 or 3) / [H,W] array
+        or such a tensor -- as a uint8 tensor on the pipeline's device (one upload), else None: every other input (RGBA / LA are
+        resampled premultiplied by Pillow, P / 1 with the nearest filter, ...) stays on the host path."""
+        if hasattr(image, "convert"):
+            if image.mode not in ("L", "RGB"):
+                return None
+            image = np.array(image)
+        if not isinstance(image, (np.ndarray, torch.Tensor)) or image.dtype not in (np.uint8, torch.uint8):
+            return None
+        if not (image.ndim == 2 or (image.ndim == 3 and image.shape[2] in (1, 3))):
+            return None
+        if not all(1 <= n <= ops.RESIZE_MAX_DIM for n in image.shape[:2]):
+            return None
+        if isinstance(image, np.ndarray):
+            image = torch.from_numpy(np.ascontiguousarray(image))
+        return image.to(self.device).contiguous()
+
+    def prepare_condition_image(self, image, height, width, *, output_type="pil"):
         """EDC:1391-1393, what the reference command line does with ``--condition_image``: resize the photo to the reduced
-        resolution of a ``height`` x ``width`` run (PIL's default filter, on the host), RGB, then ``process_condition_image``."""
+        resolution of a ``height`` x ``width`` run (PIL's default filter: bicubic), RGB, then ``process_condition_image``.
+
+        An L / RGB PIL image, a uint8 [H,W,C] / [H,W] array or such a tensor is uploaded once and resized on the device
+        (``ops.resize_u8``: Pillow's bytes exactly); the Canny detector takes the resized tensor where it is, and
+        ``output_type="pt"`` (extra) returns the fp32 (1,3,H,W) condition tensor without a host image in between.  The depth
+        estimator is a host callable and still receives a PIL image.  Any other PIL mode is resized by PIL on the host."""
+        if output_type not in ("pil", "pt"):
+            raise ValueError(f"output_type must be 'pil' or 'pt', got {output_type!r}")
         ds = self.get_downsample_size(height, width)
-        image = image.resize((ds[1] * self.vae_scale_factor, ds[0] * self.vae_scale_factor)).convert("RGB")
-        return self.process_condition_image(image, self.controlnet_model)
+        h_px, w_px = ds[0] * self.vae_scale_factor, ds[1] * self.vae_scale_factor
+        dev = self._device_image(image) if max(h_px, w_px) <= ops.RESIZE_MAX_DIM else None
+        if dev is None:
+            image = image.resize((w_px, h_px)).convert("RGB")
+        else:
+            image = ops.resize_u8(dev, (h_px, w_px), "bicubic")
+            if self.controlnet_model != "canny":
+                from PIL import Image
+                arr = image.cpu().numpy()
+                image = Image.fromarray(arr[:, :, 0] if arr.ndim == 3 and arr.shape[2] == 1 else arr).convert("RGB")
+        return self.process_condition_image(image, self.controlnet_model, output_type=output_type)
 
     def _to_condition_tensor(self, image, h_px, w_px):
         if isinstance(image, torch.Tensor):
@@ -1039,6 +1077,12 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
             t = t[None] if t.dim() == 3 else t
         else:  # PIL image or HWC uint8 array -> what VaeImageProcessor.preprocess(do_normalize=False) yields:
             # RGB, Lanczos resize to the requested size, [0,1] floats (EDC:173-175, 1017)
+            size = (image.size[1], image.size[0]) if hasattr(image, "convert") else tuple(np.shape(image)[:2])
+            rgb_array = isinstance(image, np.ndarray) and image.ndim == 3 and image.shape[2] == 3
+            if size != (h_px, w_px) and max(h_px, w_px) <= ops.RESIZE_MAX_DIM and (hasattr(image, "convert") or rgb_array):
+                dev = self._device_image(image)
+                if dev is not None:   # Lanczos on the device, written straight as the condition tensor (L: the channel replicated)
+                    return ops.resize_u8(dev, (h_px, w_px), "lanczos", out="cond")
             if hasattr(image, "convert"):
                 image = image.convert("RGB")
                 if image.size != (w_px, h_px):

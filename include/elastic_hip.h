@@ -10,6 +10,7 @@
  * Conventions (all entry points):
  *   - return value: hipError_t as int (0 == hipSuccess); never throws, never allocates, never synchronises (one exception:
  *     ed_canny_hysteresis, pre-processing outside the loop, see there);
+ *   - image pre-processing entry points (ed_canny_*, ed_resize_*): uint8 images with interleaved channels, integer arithmetic, exact;
  *   - every pointer is a DEVICE pointer owned by the caller (torch tensors), NCHW contiguous unless stated;
  *   - `stream` is a hipStream_t passed as void* (torch.cuda.current_stream().cuda_stream); NULL = default stream;
  *   - "dtype" arguments: ED_F32 / ED_F16 / ED_BF16 select the element type of the buffer crossing the torch model
@@ -514,6 +515,28 @@ int64_t ed_canny_workspace(int H, int W, int C);
 int ed_canny_map(const uint8_t* img, int H, int W, int C, int low, int high, uint8_t* map, void* stream);
 int ed_canny_hysteresis(uint8_t* map, int H, int W, void* workspace, int32_t* passes_out, void* stream);
 int ed_canny_edges(const uint8_t* map, int H, int W, uint8_t* edges, float* cond, void* stream);
+
+/*
+ * ---- Pillow-exact resize of 8-bit images (csrc/resize_kernels.hip): Image.resize with the BICUBIC (EDC:1392, PIL's default) or
+ * LANCZOS (EDC:173-175, 1017) filter on an L / RGB image, one axis per entry point.  The caller computes Pillow's fixed-point
+ * tables on the host (elasticdiffusion_official_amd/resample.py; DESIGN.md "Pillow-exact resize"): coeff int32 [n_out, ksize] with
+ * 22 fraction bits, zero-padded, and bounds int32 [n_out, 2] = (first source index, taps) per output index.  Each output byte is
+ * clamp((2^21 + sum_{x < taps} in[first + x] * coeff[x]) >> 22, 0, 255) in int32: exact, independent of the order of summation.
+ * C in {1, 3} interleaved channels, every input and output extent in 1..8192; anything else is hipErrorInvalidValue without a launch.
+ * Table entries are clamped to the source extent and to ksize before use.  A two-dimensional resize is ed_resize_rows_u8 over the
+ * source rows the vertical tables read, into a uint8 intermediate, then ed_resize_cols_u8 with the bounds shifted to that window.
+ *
+ * ed_resize_rows_u8 -- horizontal: src [H, W, C] with rows src_pitch bytes apart (any alignment) -> dst [H, W_out, C] with rows
+ *   dst_pitch bytes apart.  dst and dst_pitch must be multiples of 4 and dst_pitch >= W_out C rounded up to 4: the kernel stores
+ *   whole dwords and writes 0 into the bytes between W_out C and that bound.
+ * ed_resize_cols_u8 -- vertical: src [H, W, C] seen as H rows of WC_bytes = W C bytes, src_pitch bytes apart (any alignment) ->
+ *   dst_u8 uint8 [H_out, W, C] contiguous and / or dst_cond fp32 [1, 3, H_out, W] = byte / 255 (correctly rounded division, what
+ *   torch's .div(255.0) gives; C = 1 is replicated to the three planes); either may be NULL, not both.
+ */
+int ed_resize_rows_u8(const uint8_t* src, int H, int W, int C, int src_pitch, const int32_t* coeff, const int32_t* bounds, int ksize,
+                      int W_out, uint8_t* dst, int dst_pitch, void* stream);
+int ed_resize_cols_u8(const uint8_t* src, int H, int WC_bytes, int src_pitch, const int32_t* coeff, const int32_t* bounds, int ksize,
+                      int H_out, int C, uint8_t* dst_u8, float* dst_cond, void* stream);
 
 #ifdef __cplusplus
 }
