@@ -93,22 +93,25 @@ template <typename T>
 __device__ __forceinline__ void group_stats(const uint16_t* __restrict__ chunk, int64_t len, int HW,
                                             const uint16_t* __restrict__ kb, const uint16_t* __restrict__ cb, float eps,
                                             float& mean, float& rstd) {
-  // pass 1: per-thread sum / sum of squares over 16-byte vectors (few hundred elements per thread), then Chan merge
+  // pass 1: per-thread sum / sum of squares of x - K over 16-byte vectors (few hundred elements per thread), then Chan merge.
+  // K is the group's first element (after the folded adds): a sample of the data, so |x - K| is a few standard deviations and
+  // ss - s^2/n loses nothing to cancellation however large the group's mean is next to its spread.
   float s = 0.f, ss = 0.f, cnt = 0.f;
   const bool has_cb = cb != nullptr, has_kb = kb != nullptr;
+  const float K = biased<T>(chunk[0], has_kb ? T::to_f32(kb[0]) : 0.f, has_kb, has_cb ? T::to_f32(cb[0]) : 0.f, has_cb);
   for (int64_t i = (int64_t)threadIdx.x * 8; i < len; i += GN_THREADS * 8) {
     U16x8 v = *reinterpret_cast<const U16x8*>(chunk + i);
     const float cbv = has_cb ? T::to_f32(cb[i / HW]) : 0.f;  // HW % 8 == 0: a vector never straddles channels
     const float kbv = has_kb ? T::to_f32(kb[i / HW]) : 0.f;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      float f = biased<T>(v.v[e], kbv, has_kb, cbv, has_cb);
+      float f = biased<T>(v.v[e], kbv, has_kb, cbv, has_cb) - K;
       s += f;
       ss += f * f;
     }
     cnt += 8.f;
   }
-  Welford w;
+  Welford w;  // of x - K
   w.n = cnt;
   w.mean = cnt > 0.f ? s / cnt : 0.f;
   w.m2 = cnt > 0.f ? fmaxf(ss - s * w.mean, 0.f) : 0.f;
@@ -128,7 +131,7 @@ __device__ __forceinline__ void group_stats(const uint16_t* __restrict__ chunk, 
   if (threadIdx.x == 0) {
     Welford t = part[0];
     for (int k = 1; k < GN_THREADS / 64; ++k) t = merge(t, part[k]);
-    sh_mean = t.mean;
+    sh_mean = K + t.mean;
     sh_rstd = rsqrtf(t.m2 / t.n + eps);
   }
   __syncthreads();
@@ -199,8 +202,10 @@ k_groupnorm(const uint16_t* __restrict__ x, const uint16_t* __restrict__ gamma, 
 // One workgroup per (sample, group) leaves the chip under-filled when a group is hundreds of KB (SDXL level 1: 10-30
 // channels x 128 x 128): N*G = 640 workgroups walk 0.3-1 MB each, twice (measured 2.4 TB/s).  Here every group is cut
 // into `chunks` token ranges; k_gn_split_stats writes one Welford partial per (group, chunk), k_gn_split_apply merges the
-// partials of its group (a few dozen floats) and normalises its own range.  Same traffic (2 reads + 1 write), all of it
-// spread over thousands of workgroups.  Partials are merged in chunk order: deterministic.
+// partials of its group (a few dozen floats) and normalises its own range.  The partials are statistics of x - K, K the group's
+// first element (see group_stats), which both kernels read for themselves: every block of a group derives the same K.
+// Same traffic (2 reads + 1 write), all of it spread over thousands of workgroups.  Partials are merged in chunk order:
+// deterministic.
 #define GNS_THREADS 256
 
 template <typename T>
@@ -216,6 +221,7 @@ k_gn_split_stats(const uint16_t* __restrict__ x, const uint16_t* __restrict__ co
   const bool has_cb = cb != nullptr, has_kb = kb != nullptr;
   const int p0 = chunk * span, p1 = min(HW, p0 + span);
   const int vec_per_row = (p1 - p0) >> 3;  // span and HW are multiples of 8
+  const float K = biased<T>(base[0], has_kb ? T::to_f32(kb[0]) : 0.f, has_kb, has_cb ? T::to_f32(cb[0]) : 0.f, has_cb);
   float s = 0.f, ss = 0.f, cnt = 0.f;
   for (int it = threadIdx.x; it < cpg * vec_per_row; it += GNS_THREADS) {
     const int c = it / vec_per_row, pv = it - c * vec_per_row;
@@ -223,13 +229,13 @@ k_gn_split_stats(const uint16_t* __restrict__ x, const uint16_t* __restrict__ co
     const float cbv = has_cb ? T::to_f32(cb[c]) : 0.f, kbv = has_kb ? T::to_f32(kb[c]) : 0.f;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      float f = biased<T>(v.v[e], kbv, has_kb, cbv, has_cb);
+      float f = biased<T>(v.v[e], kbv, has_kb, cbv, has_cb) - K;
       s += f;
       ss += f * f;
     }
     cnt += 8.f;
   }
-  Welford w;
+  Welford w;  // of x - K
   w.n = cnt;
   w.mean = cnt > 0.f ? s / cnt : 0.f;
   w.m2 = cnt > 0.f ? fmaxf(ss - s * w.mean, 0.f) : 0.f;
@@ -260,20 +266,21 @@ k_gn_split_apply(const uint16_t* __restrict__ x, const uint16_t* __restrict__ ga
                  float eps) {
   const int ng = blockIdx.y, chunk = blockIdx.x;
   const int n = ng / G, g = ng % G, cpg = C / G;
+  const uint16_t* base = x + ((int64_t)n * C + (int64_t)g * cpg) * HW;
+  const uint16_t* cb = chan_bias ? chan_bias + (int64_t)n * C + (int64_t)g * cpg : nullptr;
+  const uint16_t* kb = conv_bias ? conv_bias + (int64_t)g * cpg : nullptr;
+  const bool has_cb = cb != nullptr, has_kb = kb != nullptr;
   __shared__ float sh_mean, sh_rstd;
   if (threadIdx.x == 0) {
     const float* src = partial + (int64_t)ng * chunks * 3;
     Welford t = {src[0], src[1], src[2]};
     for (int k = 1; k < chunks; ++k) t = merge(t, Welford{src[3 * k], src[3 * k + 1], src[3 * k + 2]});
-    sh_mean = t.mean;
+    const float K = biased<T>(base[0], has_kb ? T::to_f32(kb[0]) : 0.f, has_kb, has_cb ? T::to_f32(cb[0]) : 0.f, has_cb);
+    sh_mean = K + t.mean;  // the partials are statistics of x - K
     sh_rstd = rsqrtf(t.m2 / t.n + eps);
   }
   __syncthreads();
   const float mean = sh_mean, rstd = sh_rstd;
-  const uint16_t* base = x + ((int64_t)n * C + (int64_t)g * cpg) * HW;
-  const uint16_t* cb = chan_bias ? chan_bias + (int64_t)n * C + (int64_t)g * cpg : nullptr;
-  const uint16_t* kb = conv_bias ? conv_bias + (int64_t)g * cpg : nullptr;
-  const bool has_cb = cb != nullptr, has_kb = kb != nullptr;
   const int p0 = chunk * span, p1 = min(HW, p0 + span);
   if (!TOKENS) {
     uint16_t* dst = out + ((int64_t)n * C + (int64_t)g * cpg) * HW;
@@ -367,16 +374,18 @@ static inline GnPlan gn_plan(int N, int C, int HW) {
 
 template <typename T>
 __device__ __forceinline__ void gn_accumulate(const U16x8& v, const U16x8& kbv, bool has_kb, const U16x8& cbv, bool has_cb,
-                                              int split, float& s0, float& q0, float& s1, float& q1) {
+                                              int split, float k0, float k1, float& s0, float& q0, float& s1, float& q1) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const float f = biased<T>(v.v[e], has_kb ? T::to_f32(kbv.v[e]) : 0.f, has_kb, has_cb ? T::to_f32(cbv.v[e]) : 0.f, has_cb);
     if (e < split) {
-      s0 += f;
-      q0 += f * f;
+      const float d = f - k0;
+      s0 += d;
+      q0 += d * d;
     } else {
-      s1 += f;
-      q1 += f * f;
+      const float d = f - k1;
+      s1 += d;
+      q1 += d * d;
     }
   }
 }
@@ -402,22 +411,39 @@ struct Row8 {      // 8 consecutive channels of one pixel as loaded
 
 template <typename T, bool X32>
 __device__ __forceinline__ void gn_accumulate8(const Row8<X32>& v, const U16x8& kbv, bool has_kb, const U16x8& cbv, bool has_cb,
-                                               int split, float& s0, float& q0, float& s1, float& q1) {
+                                               int split, float k0, float k1, float& s0, float& q0, float& s1, float& q1) {
   if (!X32) {
-    gn_accumulate<T>(v.h, kbv, has_kb, cbv, has_cb, split, s0, q0, s1, q1);
+    gn_accumulate<T>(v.h, kbv, has_kb, cbv, has_cb, split, k0, k1, s0, q0, s1, q1);
     return;
   }
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const float f = v.f32(e);
     if (e < split) {
-      s0 += f;
-      q0 += f * f;
+      const float d = f - k0;
+      s0 += d;
+      q0 += d * d;
     } else {
-      s1 += f;
-      q1 += f * f;
+      const float d = f - k1;
+      s1 += d;
+      q1 += d * d;
     }
   }
+}
+
+// The shift K of group g of sample n: the group's first element -- pixel 0, channel c = g * cpg -- as the statistics see it (after the
+// folded adds; from the second source when c >= C1).  The sums the partial kernel forms are those of x - K and (x - K)^2: K is a sample
+// of the group, so they stay a few standard deviations in size and qq/n - (ss/n)^2 is well-conditioned whatever the mean (DESIGN.md
+// section 16).  Every block of a sample, and the finalize launch, read the same element: one K per group, bit for bit.
+template <typename T, bool X32>
+__device__ __forceinline__ float gn_shift(const void* __restrict__ x, const void* __restrict__ x2, int C1, int C, int HW,
+                                          const uint16_t* __restrict__ conv_bias, const uint16_t* __restrict__ cbn, int n, int c) {
+  const bool second = c >= C1;
+  const void* xs = second ? x2 : x;
+  const int64_t idx = (int64_t)n * HW * (second ? C - C1 : C1) + (second ? c - C1 : c);
+  if (X32) return reinterpret_cast<const float*>(xs)[idx];
+  return biased<T>(reinterpret_cast<const uint16_t*>(xs)[idx], conv_bias ? T::to_f32(conv_bias[c]) : 0.f, conv_bias != nullptr,
+                   cbn ? T::to_f32(cbn[c]) : 0.f, cbn != nullptr);
 }
 
 template <typename T, bool X32 = false>
@@ -425,7 +451,7 @@ __global__ void __launch_bounds__(GNL_THREADS)
 k_gn_nhwc_partial(const void* __restrict__ x, const void* __restrict__ x2, int C1, const uint16_t* __restrict__ conv_bias,
                   const uint16_t* __restrict__ chan_bias, float* __restrict__ partial, int C, int HW, int G,
                   int rows_per_block) {
-  extern __shared__ float sh[];  // [lanes][VC][4]: (sum, sumsq) of the column's first / second group part
+  extern __shared__ float sh[];  // [lanes][VC][4]: (sum, sumsq) of x - K over the column's first / second group part (K: gn_shift)
   const int n = blockIdx.y, chunk = blockIdx.x;
   const int VC = C >> 3, cpg = C / G;
   const int NT = blockDim.x;                                  // gn_plan: a multiple of 64, <= GNL_THREADS
@@ -448,6 +474,8 @@ k_gn_nhwc_partial(const void* __restrict__ x, const void* __restrict__ x2, int C
       if (has_kb) kbv = *reinterpret_cast<const U16x8*>(conv_bias + c0);
       if (has_cb) cbv = *reinterpret_cast<const U16x8*>(cbn + c0);
       float s0 = 0.f, q0 = 0.f, s1 = 0.f, q1 = 0.f;
+      const float k0 = gn_shift<T, X32>(x, x2, C1, C, HW, conv_bias, cbn, n, c0 + split - cpg);
+      const float k1 = split < 8 ? gn_shift<T, X32>(x, x2, C1, C, HW, conv_bias, cbn, n, c0 + split) : 0.f;
       // two sources (ed_groupnorm_nhwc_cat: the normalised tensor is cat([x, x2], channels), which is never materialised): channels
       // [0, C1) are columns of x (C1 per pixel), [C1, C) of x2 (C - C1 per pixel); one source: C1 == C
       const bool second = c0 >= C1;
@@ -462,12 +490,12 @@ k_gn_nhwc_partial(const void* __restrict__ x, const void* __restrict__ x2, int C
 #pragma unroll
         for (int u = 0; u < GNL_UNROLL; ++u) v[u].load(xs, p0 + u * step);
 #pragma unroll
-        for (int u = 0; u < GNL_UNROLL; ++u) gn_accumulate8<T, X32>(v[u], kbv, has_kb, cbv, has_cb, split, s0, q0, s1, q1);
+        for (int u = 0; u < GNL_UNROLL; ++u) gn_accumulate8<T, X32>(v[u], kbv, has_kb, cbv, has_cb, split, k0, k1, s0, q0, s1, q1);
       }
       for (; row < r1; row += R) {
         Row8<X32> v;
         v.load(xs, col + (int64_t)row * cs);
-        gn_accumulate8<T, X32>(v, kbv, has_kb, cbv, has_cb, split, s0, q0, s1, q1);
+        gn_accumulate8<T, X32>(v, kbv, has_kb, cbv, has_cb, split, k0, k1, s0, q0, s1, q1);
       }
       float* slot = sh + ((int64_t)my_r * VC + vc) * 4;
       slot[0] = s0, slot[1] = q0, slot[2] = s1, slot[3] = q1;
@@ -494,10 +522,14 @@ k_gn_nhwc_partial(const void* __restrict__ x, const void* __restrict__ x2, int C
 
 // Finalize: one block per sample reduces its partial sums [nchunks, G, 2] to (mean, rstd) per group -- thread (g, part) adds every
 // parts-th chunk in double, then one thread per group adds the parts in ascending order (deterministic; the arithmetic of the round-3
-// apply prologue, now run once per sample instead of once per apply block).
+// apply prologue, now run once per sample instead of once per apply block).  The sums are those of x - K (gn_shift, read again here):
+// mean = K + ss/n, var = qq/n - (ss/n)^2.
 #define GNL_MAXG 256
+template <typename T, bool X32>
 __global__ void __launch_bounds__(GNL_THREADS)
-k_gn_nhwc_finalize(const float* __restrict__ partial, float* __restrict__ stats_out, int G, int nchunks, double count, float eps) {
+k_gn_nhwc_finalize(const float* __restrict__ partial, float* __restrict__ stats_out, int G, int nchunks, double count, float eps,
+                   const void* __restrict__ x, const void* __restrict__ x2, int C1, int C, int HW,
+                   const uint16_t* __restrict__ conv_bias, const uint16_t* __restrict__ chan_bias) {
   __shared__ double red[2 * GNL_THREADS];
   const int n = blockIdx.x;
   const int parts = GNL_THREADS / G > 0 ? GNL_THREADS / G : 1;  // G <= 256
@@ -529,9 +561,12 @@ k_gn_nhwc_finalize(const float* __restrict__ partial, float* __restrict__ stats_
       ss += red[2 * (k * G + threadIdx.x)];
       qq += red[2 * (k * G + threadIdx.x) + 1];
     }
-    const double mean = ss / count;
-    double var = qq / count - mean * mean;
+    const double K = (double)gn_shift<T, X32>(x, x2, C1, C, HW, conv_bias, chan_bias ? chan_bias + (int64_t)n * C : nullptr, n,
+                                              (int)threadIdx.x * (C / G));
+    const double dmean = ss / count;
+    double var = qq / count - dmean * dmean;
     if (var < 0.0) var = 0.0;
+    const double mean = K + dmean;
     stats_out[((int64_t)n * G + threadIdx.x) * 2] = (float)mean;
     stats_out[((int64_t)n * G + threadIdx.x) * 2 + 1] = rsqrtf((float)var + eps);
   }
@@ -570,12 +605,16 @@ k_gn_nhwc_apply(const void* __restrict__ x, const void* __restrict__ x2, int C1,
     U16x8 kbv = {}, cbv = {};
     if (has_kb) kbv = *reinterpret_cast<const U16x8*>(conv_bias + c0);
     if (has_cb) cbv = *reinterpret_cast<const U16x8*>(chan_bias + (int64_t)n * C + c0);
-    float a[8], b[8], kb[8], cb[8];
+    // 16-bit input: y = a x + (beta - a mean).  fp32 stream: y = a (x - mean) + beta -- the stream's mean / spread ratio is not bounded by
+    // a 16-bit format, and beta - a mean, an fp32 number of the size of a mean / spread, would alone cost more than the 16-bit output's
+    // rounding from a ratio of ~1e4 on; x - mean is exact to the rounding of the mean.
+    float a[8], b[8], mu[8], kb[8], cb[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const float mean = e < split ? mean0 : mean1, rstd = e < split ? rstd0 : rstd1;
       a[e] = rstd * T::to_f32(gm.v[e]);
-      b[e] = fmaf(-a[e], mean, T::to_f32(bt.v[e]));
+      mu[e] = mean;
+      b[e] = X32 ? T::to_f32(bt.v[e]) : fmaf(-a[e], mean, T::to_f32(bt.v[e]));
       kb[e] = has_kb ? T::to_f32(kbv.v[e]) : 0.f;
       cb[e] = has_cb ? T::to_f32(cbv.v[e]) : 0.f;
     }
@@ -586,7 +625,7 @@ k_gn_nhwc_apply(const void* __restrict__ x, const void* __restrict__ x2, int C1,
         const float xin = X32 ? v.f32(e) : biased<T>(v.h.v[e], kb[e], has_kb, cb[e], has_cb);
         // 16-bit module: the normalised value is rounded before SiLU, as torch's two kernels round it; on the fp32 stream (the tolerance
         // mode) nothing asks for that intermediate rounding: one rounding, of the final result
-        const float y = X32 ? fmaf(a[e], xin, b[e]) : T::to_f32(T::from_f32(fmaf(a[e], xin, b[e])));
+        const float y = X32 ? fmaf(a[e], xin - mu[e], b[e]) : T::to_f32(T::from_f32(fmaf(a[e], xin, b[e])));
         o.v[e] = ACT ? T::from_f32(silu_fast(y)) : T::from_f32(y);
       }
       return o;
@@ -887,7 +926,9 @@ k_bias_residual_add_cl(const uint16_t* __restrict__ h, const uint16_t* __restric
 // group): 160 blocks for a [5,128,256,1024] activation on a 256-CU chip, 1.3 TB/s) + an affine kernel + a separate SiLU kernel
 // (profiles/r3_s3_bench_*: 610 ms per two images).  Here: (1) partial sums over 64 K-element chunks of every group -- all CUs
 // busy, four 16-byte loads in flight per thread -- and (2) an apply pass whose blocks first combine their group's partials in
-// double (fixed order: deterministic), then stream y = silu((x - mean) * rstd * gamma[c] + beta[c]).
+// double (fixed order: deterministic), then stream y = silu((x - mean) * rstd * gamma[c] + beta[c]).  The sums are those of x - K and
+// (x - K)^2 with K the group's first element, read by every block of the group: shifted by a sample of the data they are a few standard
+// deviations in size, so the fp32 partials and var = qq/n - (ss/n)^2 keep their digits whatever the mean.
 #define GN32_THREADS 256
 #define GN32_CHUNK 65536  // elements per block
 
@@ -899,6 +940,12 @@ k_gn32_partial(const float* __restrict__ x, float* __restrict__ partial, int64_t
   const float* base = x + ng * group_len;
   const int64_t e0 = (int64_t)chunk * GN32_CHUNK, e1 = e0 + GN32_CHUNK < group_len ? e0 + GN32_CHUNK : group_len;
   float s = 0.f, q = 0.f;
+  const float K = base[0];
+  auto add = [&](float4 v) {
+    v.x -= K, v.y -= K, v.z -= K, v.w -= K;
+    s += (v.x + v.y) + (v.z + v.w);
+    q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+  };
   int64_t i = e0 + 4 * (int64_t)threadIdx.x;
   const int64_t step = 4 * GN32_THREADS;
   for (; i + 3 * step + 3 < e1; i += 4 * step) {
@@ -906,16 +953,9 @@ k_gn32_partial(const float* __restrict__ x, float* __restrict__ partial, int64_t
 #pragma unroll
     for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const float4*>(base + i + u * step);
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      s += (v[u].x + v[u].y) + (v[u].z + v[u].w);
-      q += (v[u].x * v[u].x + v[u].y * v[u].y) + (v[u].z * v[u].z + v[u].w * v[u].w);
-    }
+    for (int u = 0; u < 4; ++u) add(v[u]);
   }
-  for (; i + 3 < e1; i += step) {
-    const float4 v = *reinterpret_cast<const float4*>(base + i);
-    s += (v.x + v.y) + (v.z + v.w);
-    q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-  }
+  for (; i + 3 < e1; i += step) add(*reinterpret_cast<const float4*>(base + i));
   double ds = (double)s, dq = (double)q;
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
@@ -945,9 +985,10 @@ k_gn32_apply(const float* __restrict__ x, const float* __restrict__ gamma, const
     double ts = 0.0, tq = 0.0;
     const float* p = partial + ng * nchunks * 2;
     for (int c = 0; c < nchunks; ++c) ts += (double)p[2 * c], tq += (double)p[2 * c + 1];
-    const double mean = ts / (double)group_len;
-    double var = tq / (double)group_len - mean * mean;
+    const double dmean = ts / (double)group_len;  // of x - K, K = the group's first element (k_gn32_partial)
+    double var = tq / (double)group_len - dmean * dmean;
     if (var < 0.0) var = 0.0;
+    const double mean = (double)x[ng * group_len] + dmean;
     st[0] = (float)mean, st[1] = (float)(1.0 / sqrt(var + (double)eps));
   }
   __syncthreads();
@@ -1150,7 +1191,8 @@ static int gn_nhwc_launch(const void* x, const void* x2, int C1, const void* gam
 #define GNL_RUN2(T, X32)                                                                                               \
   k_gn_nhwc_partial<T, X32><<<grid1, pl.threads, lds, s>>>(x, x2, C1, (const uint16_t*)conv_bias,                              \
                                                            (const uint16_t*)chan_bias, partial, C, HW, G, rows_per_block); \
-  k_gn_nhwc_finalize<<<N, GNL_THREADS, 0, s>>>(partial, stats, G, pl.nchunks, (double)HW * (C / G), eps);             \
+  k_gn_nhwc_finalize<T, X32><<<N, GNL_THREADS, 0, s>>>(partial, stats, G, pl.nchunks, (double)HW * (C / G), eps, x, x2, C1, C, HW, \
+                                                       (const uint16_t*)conv_bias, (const uint16_t*)chan_bias);       \
   if (act_silu)                                                                                                        \
     k_gn_nhwc_apply<T, true, X32><<<grid1, pl.threads, 0, s>>>(x, x2, C1, (const uint16_t*)gamma,                              \
                                                          (const uint16_t*)beta, (const uint16_t*)conv_bias,            \

@@ -38,8 +38,10 @@ __device__ __forceinline__ int split_exponent(float absmax) {
 }
 
 // ---- statistics: every thread owns one 4-channel column (cpg % 4 == 0: the column lies inside ONE group) and walks rows ----------
-// x [N, HW, C] fp32 (channels-last memory of a [N, C, H, W] tensor); partial [N, nchunks, G, 2] (sum, sum of squares), fixed summation
-// order: bit-reproducible.
+// x [N, HW, C] fp32 (channels-last memory of a [N, C, H, W] tensor); partial [N, nchunks, G, 2] (sum, sum of squares) of x - K, where K
+// is the group's first element (pixel 0, channel g * cpg), read by every block of the sample and again by the apply pass: shifted by a
+// sample of the data the sums are a few standard deviations in size, so the fp32 partials and var = qq/n - (ss/n)^2 keep their digits
+// whatever the group's mean.  Fixed summation order: bit-reproducible.
 __global__ void __launch_bounds__(GV_THREADS)
 k_gn32_nhwc_partial(const float* __restrict__ x, float* __restrict__ partial, int C, int HW, int G, int rows_per_block) {
   extern __shared__ float sh[];          // [row lanes][VC][2]
@@ -57,6 +59,12 @@ k_gn32_nhwc_partial(const float* __restrict__ x, float* __restrict__ partial, in
       const int vc = my_c + j * GV_THREADS;
       if (vc >= VC) break;
       float s = 0.f, q = 0.f;
+      const float K = base[((vc << 2) / cpg) * cpg];
+      auto add = [&](float4 v) {
+        v.x -= K, v.y -= K, v.z -= K, v.w -= K;
+        s += (v.x + v.y) + (v.z + v.w);
+        q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+      };
       const float* col = base + (vc << 2);
       const int64_t step = (int64_t)R * C;
       int row = r0 + my_r;
@@ -66,16 +74,9 @@ k_gn32_nhwc_partial(const float* __restrict__ x, float* __restrict__ partial, in
 #pragma unroll
         for (int u = 0; u < GV_UNROLL; ++u) v[u] = *reinterpret_cast<const float4*>(p0 + u * step);
 #pragma unroll
-        for (int u = 0; u < GV_UNROLL; ++u) {
-          s += (v[u].x + v[u].y) + (v[u].z + v[u].w);
-          q += (v[u].x * v[u].x + v[u].y * v[u].y) + (v[u].z * v[u].z + v[u].w * v[u].w);
-        }
+        for (int u = 0; u < GV_UNROLL; ++u) add(v[u]);
       }
-      for (; row < r1; row += R) {
-        const float4 v = *reinterpret_cast<const float4*>(col + (int64_t)row * C);
-        s += (v.x + v.y) + (v.z + v.w);
-        q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-      }
+      for (; row < r1; row += R) add(*reinterpret_cast<const float4*>(col + (int64_t)row * C));
       float* slot = sh + ((int64_t)my_r * VC + vc) * 2;
       slot[0] = s, slot[1] = q;
     }
@@ -127,9 +128,10 @@ k_gn32_nhwc_apply(const float* __restrict__ x, const float* __restrict__ gamma, 
         ss += red[2 * (k * G + threadIdx.x)];
         qq += red[2 * (k * G + threadIdx.x) + 1];
       }
-      const double mean = ss / count;
-      double var = qq / count - mean * mean;
+      const double dmean = ss / count;  // of x - K (k_gn32_nhwc_partial)
+      double var = qq / count - dmean * dmean;
       if (var < 0.0) var = 0.0;
+      const double mean = (double)x[(int64_t)n * HW * C + (int64_t)threadIdx.x * (C / G)] + dmean;
       stats[2 * threadIdx.x] = (float)mean;
       stats[2 * threadIdx.x + 1] = (float)(1.0 / sqrt(var + (double)eps));
     }

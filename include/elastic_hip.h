@@ -224,7 +224,8 @@ int ed_geglu(const void* in, void* out, int dtype, int64_t M, int I, void* strea
  *   workspace: caller-owned fp32 scratch of ed_groupnorm_workspace(N, C, HW, G) bytes, or NULL.  Groups larger than
  *   64 K elements are then normalised by two fully parallel launches (per-chunk Welford partials, merged in order --
  *   deterministic) instead of one workgroup per (sample, group); with NULL (or small groups: workspace size 0) the
- *   single-launch kernel runs.
+ *   single-launch kernel runs.  Statistics (here and in every ed_groupnorm_* below): fp32 sums of x - K and (x - K)^2 with K the
+ *   group's first element as normalised, so the variance keeps its digits when the mean is large next to the spread.
  *   HW % 8 == 0, C % G == 0 (and (C/G) % 4 == 0 for tokens_out); dtype = ED_F16 | ED_BF16.
  */
 int ed_groupnorm(const void* x, const void* gamma, const void* beta, const void* conv_bias, const void* chan_bias,
@@ -255,7 +256,8 @@ int ed_layernorm(const void* x, const void* gamma, const void* beta, void* out, 
  * block to block is fp32, every branch computes in the 16-bit model dtype.  These entry points are the memory-bound layers that READ
  * the stream: same arithmetic as their 16-bit namesakes, x (ed_layernorm_s32, ed_groupnorm_nhwc_s32) or b and sum_out
  * (ed_add_layernorm_s32: sum_out = a + b in fp32, unrounded) are fp32, everything else -- gamma, beta, a, out -- has `dtype`.
- * ed_groupnorm_nhwc_s32 takes no folded biases; workspace: ed_groupnorm_nhwc_workspace.  Same shape limits as the namesakes.
+ * ed_groupnorm_nhwc_s32 takes no folded biases and applies a (x - mean) + beta (the 16-bit namesake: a x + (beta - a mean));
+ * workspace: ed_groupnorm_nhwc_workspace.  Same shape limits as the namesakes.
  */
 int ed_layernorm_s32(const void* x, const void* gamma, const void* beta, void* out, int dtype, int64_t M, int D, float eps,
                      void* stream);
@@ -282,7 +284,7 @@ int ed_tokens_add_nchw(const void* x, const void* tokens, void* out, int dtype, 
 /*
  * ed_groupnorm_nhwc -- the same GroupNorm [+ SiLU] for channels-last activations: x / out dtype [N, HW, C] (the memory
  * of an NCHW tensor in torch.channels_last format, which is also the transformer's token layout).  Three launches
- * (partial sums, finalise in double, vectorised apply); `workspace` is caller-owned fp32 scratch of
+ * (partial sums of x - K per group, finalise in double, vectorised apply); `workspace` is caller-owned fp32 scratch of
  * ed_groupnorm_nhwc_workspace(N, C, HW, G) bytes.  conv_bias [C] / chan_bias [N,C] (optional) as in ed_groupnorm.
  * C % 8 == 0, C % G == 0, C / G >= 8, G <= 256; dtype = ED_F16 | ED_BF16.
  */
