@@ -12,7 +12,8 @@ the already extracted condition by default; ``--process_condition true`` treats 
 flag of the same name (resize to the reduced resolution, canny on the device / injected depth estimator) and saves the
 extracted condition as ``condition.png``.  ``--prediction_type``, ``--timestep_spacing`` and
 ``--rescale_betas_zero_snr`` override what the snapshot's ``scheduler/scheduler_config.json`` says (or the SD defaults
-without ``--weights``); the reference takes these from the hub config only.
+without ``--weights``); the reference takes these from the hub config only.  ``--guidance_rescale`` is diffusers' keyword of
+that name (0 = off), what such checkpoints are meant to be sampled with.
 """
 import argparse
 import os
@@ -26,7 +27,7 @@ def _bool(v):
     return str(v).lower() in ("1", "true", "yes", "y", "t")
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(prog="python -m elasticdiffusion_official_amd")
     ap.add_argument("--prompt", type=str, default="A realistic portrait of a young black woman. she has a Christmas red "
                     "hat and a red scarf. Her eyes are light brown like they're almost caramel color. Her attire, simple yet dignified.")
@@ -66,7 +67,16 @@ def main(argv=None):
                     help="default: the snapshot's scheduler_config.json, else leading")
     ap.add_argument("--rescale_betas_zero_snr", type=_bool, default=None,
                     help="zero terminal SNR betas; default: the snapshot's scheduler_config.json, else false")
-    opt = ap.parse_args(argv)
+    ap.add_argument("--guidance_rescale", type=float, default=0.0,
+                    help="std rescale of the guided prediction in [0, 1] (arXiv 2305.08891 section 3.4; diffusers' "
+                    "guidance_rescale), for zero-terminal-SNR / v-prediction checkpoints; 0 = off")
+    return ap
+
+
+def main(argv=None):
+    opt = build_parser().parse_args(argv)
+    if not 0.0 <= opt.guidance_rescale <= 1.0:
+        raise SystemExit(f"--guidance_rescale must be in [0, 1], got {opt.guidance_rescale}")
 
     from . import ElasticDiffusion, ElasticDiffusionControlNet
     if not torch.cuda.is_available():
@@ -102,7 +112,7 @@ def main(argv=None):
                                         guidance_scale=opt.guidance_scale, resampling_steps=opt.resampling_steps,
                                         new_p=opt.new_p, cosine_scale=opt.cosine_scale, rrg_init_weight=opt.rrg_scale,
                                         rrg_stop_t=opt.rrg_stop_t, repaint_sampling=opt.repaint_sampling,
-                                        tiled_decoder=opt.tiled_decoder, **extra)
+                                        tiled_decoder=opt.tiled_decoder, guidance_rescale=opt.guidance_rescale, **extra)
     torch.cuda.synchronize()
     print(f"Time taken: {time.time() - t0:.2f} seconds")
     if opt.verbose:  # the reference prints its TimeIt table here (ED:1191-1192); ours: GPU phases + host-side time

@@ -18,7 +18,7 @@ SOURCES = [os.path.join(PKG_DIR, "csrc", n) for n in ("elastic_kernels.hip", "un
 SRC = SOURCES[0]
 INCLUDE = os.path.join(ROOT_DIR, "include")
 SO_PATH = os.path.join(PKG_DIR, "libelastic_hip.so")
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
 
@@ -82,6 +82,17 @@ SIGNATURES = {
     "ed_phase_epilogue_pt": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                              _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f,
                              _f, _f, _i, _vp],
+    "ed_guidance_moments_workspace": [_i, _i64, _i64],
+    "ed_guidance_moments": [_vp, _vp, _vp, _f, _i, _i64, _vp, _vp, _vp],
+    "ed_phase_moments": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i,
+                         _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp],
+    "ed_cfg_ddim_step_gr": [_vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i64, _i, _vp, _f, _f, _i, _vp],
+    "ed_cfg_ddim_step_width": [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i],
+    "ed_rrg_update_gr": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _vp, _f, _f,
+                         _vp],
+    "ed_phase_epilogue_gr": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                             _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f,
+                             _f, _f, _i, _vp, _vp, _f, _f, _vp],
     "ed_resize_rows_u8": [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp],
     "ed_resize_cols_u8": [_vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
 }

@@ -15,7 +15,7 @@
 
 #include "elastic_hip.h"
 
-#define ED_ABI_VERSION 12
+#define ED_ABI_VERSION 13
 #define ED_BLOCK 256
 
 namespace {
@@ -434,40 +434,60 @@ __device__ __forceinline__ float pred_x0(float m, float xv, float sb, float sa) 
   return __fdiv_rn(__fsub_rn(xv, __fmul_rn(sb, m)), sa);
 }
 
-template <bool VP>
+// Guidance rescale (arXiv 2305.08891 section 3.4, the reference's rescale_noise_cfg ED:800-811) on a guided model output m
+// of sample b: m <- gr * (m * ratio[b]) + omgr * m, ratio[b] = std(m at g = 1) / std(m) over the sample (k_guidance_moments /
+// k_phase_moments below), gr / omgr = float32(guidance_rescale) / float32(1 - guidance_rescale) from the host; every product
+// and sum rounded on its own, in the reference's order.  GR is a compile-time variant: the <.., false> instantiations are the
+// code they were before it existed and never read `rs`.
+struct Rescale {
+  const float* ratio;  // [B] on the device
+  float gr, omgr;
+  int64_t per;         // elements per sample of the flat kernels (k_cfg_ddim_*)
+};
+
+template <bool GR>
+__device__ __forceinline__ float rescaled(float m, float r, float gr, float omgr) {
+  if (!GR) return m;
+  return __fadd_rn(__fmul_rn(gr, __fmul_rn(m, r)), __fmul_rn(omgr, m));
+}
+
+template <bool VP, bool GR = false>
 __device__ __forceinline__ void ddim_one(float l, float d, float xv, float g, float sb, float sa, float sp, float sd,
-                                         float& prev, float& x0) {
-  float m = __fadd_rn(l, __fmul_rn(g, d));
+                                         float& prev, float& x0, float r = 0.0f, float gr = 0.0f, float omgr = 0.0f) {
+  float m = rescaled<GR>(__fadd_rn(l, __fmul_rn(g, d)), r, gr, omgr);
   x0 = pred_x0<VP>(m, xv, sb, sa);
   float eps = VP ? __fadd_rn(__fmul_rn(sa, m), __fmul_rn(sb, xv)) : m;
   prev = __fadd_rn(__fmul_rn(sp, x0), __fmul_rn(sd, eps));
 }
 
-template <bool VP>
+// The <VP, true> instantiation is only launched with rs.per % 4 == 0 (cfg_ddim_x4), so the 4 elements of a thread belong to
+// one sample; <VP, false> never reads rs.
+template <bool VP, bool GR = false>
 __global__ void __launch_bounds__(ED_BLOCK)
 k_cfg_ddim_v4(const float4* __restrict__ local, const float4* __restrict__ dir, const float4* __restrict__ x,
               float4* __restrict__ prev, float4* __restrict__ x0, float g, float sb, float sa, float sp, float sd,
-              int64_t n4) {
+              int64_t n4, const Rescale rs) {
   int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
   if (t >= n4) return;
   float4 l = local[t], d = dir[t], xv = x[t], p, o;
-  ddim_one<VP>(l.x, d.x, xv.x, g, sb, sa, sp, sd, p.x, o.x);
-  ddim_one<VP>(l.y, d.y, xv.y, g, sb, sa, sp, sd, p.y, o.y);
-  ddim_one<VP>(l.z, d.z, xv.z, g, sb, sa, sp, sd, p.z, o.z);
-  ddim_one<VP>(l.w, d.w, xv.w, g, sb, sa, sp, sd, p.w, o.w);
+  const float r = GR ? rs.ratio[(t << 2) / rs.per] : 0.0f;
+  ddim_one<VP, GR>(l.x, d.x, xv.x, g, sb, sa, sp, sd, p.x, o.x, r, rs.gr, rs.omgr);
+  ddim_one<VP, GR>(l.y, d.y, xv.y, g, sb, sa, sp, sd, p.y, o.y, r, rs.gr, rs.omgr);
+  ddim_one<VP, GR>(l.z, d.z, xv.z, g, sb, sa, sp, sd, p.z, o.z, r, rs.gr, rs.omgr);
+  ddim_one<VP, GR>(l.w, d.w, xv.w, g, sb, sa, sp, sd, p.w, o.w, r, rs.gr, rs.omgr);
   prev[t] = p;
   x0[t] = o;
 }
 
-template <bool VP>
+template <bool VP, bool GR = false>
 __global__ void __launch_bounds__(ED_BLOCK)
 k_cfg_ddim_s(const float* __restrict__ local, const float* __restrict__ dir, const float* __restrict__ x,
              float* __restrict__ prev, float* __restrict__ x0, float g, float sb, float sa, float sp, float sd,
-             int64_t n) {
+             int64_t n, const Rescale rs) {
   int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
   if (t >= n) return;
   float p, o;
-  ddim_one<VP>(local[t], dir[t], x[t], g, sb, sa, sp, sd, p, o);
+  ddim_one<VP, GR>(local[t], dir[t], x[t], g, sb, sa, sp, sd, p, o, GR ? rs.ratio[t / rs.per] : 0.0f, rs.gr, rs.omgr);
   prev[t] = p;
   x0[t] = o;
 }
@@ -531,6 +551,8 @@ struct EpilogueArgs {
   float *prev, *x0, *x_next, *low_dir, *uncond_last, *direction, *local;  // x_next/direction/local optional
   int K, B, C, H, W, h, w, gPH, gPW, g_off_y, g_off_x, vPH, vPW, ncb;
   float g, sb, sa, sp, sd, rrg_norm, rrg_weight;
+  const float *ratio, *ratio_low;  // guidance rescale (GR variants only): [B] each, ratio_low for the fused RRG term
+  float gr, omgr;
 };
 
 template <typename Tag>
@@ -543,36 +565,9 @@ __device__ __forceinline__ float direction_at(const EpilogueArgs& a, int b, int 
   return __fsub_rn(cd, u);
 }
 
-template <typename Tag, bool VP>
-__global__ void __launch_bounds__(ED_BLOCK)
-k_phase_epilogue(const EpilogueArgs a) {
-  const int64_t nfull = (int64_t)a.B * a.C * a.H * a.W;
-  const int64_t nlow = (int64_t)a.B * a.C * a.h * a.w;
-  int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
-  if (t >= nfull + nlow) return;
-  if (t >= nfull) {  // reduced-resolution by-products for RRG / the caller: direction sampled at the nearest-downsample points
-    int64_t u = t - nfull;
-    int j = (int)(u % a.w);
-    int64_t r = u / a.w;
-    int i = (int)(r % a.h);
-    r /= a.h;
-    int c = (int)(r % a.C);
-    int b = (int)(r / a.C);
-    if (a.low_dir) a.low_dir[u] = direction_at<Tag>(a, b, c, a.down_row[i], a.down_col[j]);
-    if (a.uncond_last) {
-      int64_t plane = (int64_t)a.gPH * a.gPW;
-      int64_t e = ((int64_t)c * a.gPH + (i + a.g_off_y)) * a.gPW + (j + a.g_off_x);
-      a.uncond_last[u] = ld<Tag>(a.g_out, (((int64_t)(a.K - 1) * 2 + 0) * a.B + b) * a.C * plane + e);
-    }
-    return;
-  }
-  int X = (int)(t % a.W);
-  int64_t r = t / a.W;
-  int Y = (int)(r % a.H);
-  r /= a.H;
-  int c = (int)(r % a.C);
-  int b = (int)(r / a.C);
-  // local unconditional score: first covering view whose centre value is non-zero (ED:852-861)
+// local unconditional score: first covering view whose centre value is non-zero (ED:852-861)
+template <typename Tag>
+__device__ __forceinline__ float local_at(const EpilogueArgs& a, int b, int c, int Y, int X) {
   float loc = 0.0f;
   bool settled = false;
 #pragma unroll
@@ -590,24 +585,208 @@ k_phase_epilogue(const EpilogueArgs a) {
       if (loc != 0.0f) settled = true;
     }
   }
+  return loc;
+}
+
+// the last resampling step's unconditional output at reduced pixel (i, j) (ed_unpad_direction's uncond_last)
+template <typename Tag>
+__device__ __forceinline__ float uncond_last_at(const EpilogueArgs& a, int b, int c, int i, int j) {
+  int64_t plane = (int64_t)a.gPH * a.gPW;
+  int64_t e = ((int64_t)c * a.gPH + (i + a.g_off_y)) * a.gPW + (j + a.g_off_x);
+  return ld<Tag>(a.g_out, (((int64_t)(a.K - 1) * 2 + 0) * a.B + b) * a.C * plane + e);
+}
+
+template <typename Tag, bool VP, bool GR = false>
+__global__ void __launch_bounds__(ED_BLOCK)
+k_phase_epilogue(const EpilogueArgs a) {
+  const int64_t nfull = (int64_t)a.B * a.C * a.H * a.W;
+  const int64_t nlow = (int64_t)a.B * a.C * a.h * a.w;
+  int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
+  if (t >= nfull + nlow) return;
+  if (t >= nfull) {  // reduced-resolution by-products for RRG / the caller: direction sampled at the nearest-downsample points
+    int64_t u = t - nfull;
+    int j = (int)(u % a.w);
+    int64_t r = u / a.w;
+    int i = (int)(r % a.h);
+    r /= a.h;
+    int c = (int)(r % a.C);
+    int b = (int)(r / a.C);
+    if (a.low_dir) a.low_dir[u] = direction_at<Tag>(a, b, c, a.down_row[i], a.down_col[j]);
+    if (a.uncond_last) a.uncond_last[u] = uncond_last_at<Tag>(a, b, c, i, j);
+    return;
+  }
+  int X = (int)(t % a.W);
+  int64_t r = t / a.W;
+  int Y = (int)(r % a.H);
+  r /= a.H;
+  int c = (int)(r % a.C);
+  int b = (int)(r / a.C);
+  float loc = local_at<Tag>(a, b, c, Y, X);
   float d = direction_at<Tag>(a, b, c, Y, X);
   float pv, z0;
-  ddim_one<VP>(loc, d, a.x[t], a.g, a.sb, a.sa, a.sp, a.sd, pv, z0);
+  ddim_one<VP, GR>(loc, d, a.x[t], a.g, a.sb, a.sa, a.sp, a.sd, pv, z0, GR ? a.ratio[b] : 0.0f, a.gr, a.omgr);
   a.prev[t] = pv;
   a.x0[t] = z0;
   if (a.direction) a.direction[t] = d;
   if (a.local) a.local[t] = loc;
   if (a.x_next) {  // ED:886-940 closed form + ED:1078, as k_rrg_update
     int i = a.up_row[Y], j = a.up_col[X];
-    int64_t plane = (int64_t)a.gPH * a.gPW;
-    int64_t e = ((int64_t)c * a.gPH + (i + a.g_off_y)) * a.gPW + (j + a.g_off_x);
-    float lu = ld<Tag>(a.g_out, (((int64_t)(a.K - 1) * 2 + 0) * a.B + b) * a.C * plane + e);
+    float lu = uncond_last_at<Tag>(a, b, c, i, j);
     float ldir = direction_at<Tag>(a, b, c, a.down_row[i], a.down_col[j]);
-    float m = __fadd_rn(lu, __fmul_rn(a.g, ldir));
+    float m = rescaled<GR>(__fadd_rn(lu, __fmul_rn(a.g, ldir)), GR ? a.ratio_low[b] : 0.0f, a.gr, a.omgr);
     float up = pred_x0<VP>(m, a.low_latent[(((int64_t)b * a.C + c) * a.h + i) * a.w + j], a.sb, a.sa);
     float grad = __fmul_rn(__fmul_rn(a.rrg_norm, __fsub_rn(z0, up)), a.rrg_weight);
     a.x_next[t] = __fadd_rn(pv, -grad);
   }
+}
+
+// ---- ed_guidance_moments / ed_phase_moments: the per-sample std ratio of the guidance rescale -------------------
+// ratio[b] = std(m_text[b]) / std(m_cfg[b]) over all elements of sample b (unbiased, torch.std's default), m_cfg = l + g*d
+// and m_text = l + d as fp32 values.  Deterministic two-step reduction, no atomics: a fixed number of blocks per sample
+// (moments_blocks(n)) each write ONE partial -- Welford triples (count, mean, M2) of both quantities, 6 doubles -- into the
+// caller's workspace; k_moments_finalise merges a sample's partials in a fixed order.  Accumulation is in fp64 and
+// shifted: each thread sums x - K and (x - K)^2 with K its own first element, so nothing is lost to cancellation however
+// large the mean is next to the spread (the GroupNorm kernels' idiom, unet_kernels.hip), and the triples are merged with
+// Chan's formula like merge() there.
+#define ED_MOM_MAX_BLOCKS 256
+#define ED_MOM_PER_THREAD 4
+
+struct WelfordD {
+  double n, mean, m2;
+};
+__device__ __forceinline__ WelfordD merge_d(WelfordD a, WelfordD b) {
+  if (b.n == 0.0) return a;
+  if (a.n == 0.0) return b;
+  double n = a.n + b.n;
+  double d = b.mean - a.mean;
+  WelfordD r;
+  r.n = n;
+  r.mean = a.mean + d * (b.n / n);
+  r.m2 = a.m2 + b.m2 + d * d * (a.n * b.n / n);
+  return r;
+}
+__device__ __forceinline__ WelfordD shfl_down_d(WelfordD w, int off) {
+  WelfordD o;
+  o.n = __shfl_down(w.n, off, 64);
+  o.mean = __shfl_down(w.mean, off, 64);
+  o.m2 = __shfl_down(w.m2, off, 64);
+  return o;
+}
+
+struct PairAcc {  // one thread's shifted sums of m_cfg (c) and m_text (t)
+  double n = 0.0, kc = 0.0, kt = 0.0, sc = 0.0, ssc = 0.0, st = 0.0, sst = 0.0;
+  __device__ __forceinline__ void add(float l, float d, float g) { add_pair(__fadd_rn(l, __fmul_rn(g, d)), __fadd_rn(l, d)); }
+  __device__ __forceinline__ void add_pair(float mc, float mt) {
+    if (n == 0.0) kc = (double)mc, kt = (double)mt;
+    double a = (double)mc - kc, b = (double)mt - kt;
+    sc += a, ssc += a * a, st += b, sst += b * b, n += 1.0;
+  }
+  __device__ __forceinline__ WelfordD get(bool cfg) const {
+    WelfordD w = {n, 0.0, 0.0};
+    if (n > 0.0) {
+      double s = cfg ? sc : st, ss = cfg ? ssc : sst, mu = s / n;
+      w.mean = (cfg ? kc : kt) + mu;
+      w.m2 = fmax(ss - s * mu, 0.0);
+    }
+    return w;
+  }
+};
+
+// block-wide merge (wave shuffles, then the 4 wave results in order); thread 0 writes the block's partial
+__device__ __forceinline__ void moments_block_store(const PairAcc& acc, double* __restrict__ partial) {
+  WelfordD wc = acc.get(true), wt = acc.get(false);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    wc = merge_d(wc, shfl_down_d(wc, off));
+    wt = merge_d(wt, shfl_down_d(wt, off));
+  }
+  __shared__ WelfordD part[2][ED_BLOCK / 64];
+  int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) part[0][wave] = wc, part[1][wave] = wt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    wc = part[0][0], wt = part[1][0];
+    for (int k = 1; k < ED_BLOCK / 64; ++k) wc = merge_d(wc, part[0][k]), wt = merge_d(wt, part[1][k]);
+    partial[0] = wc.n, partial[1] = wc.mean, partial[2] = wc.m2;
+    partial[3] = wt.n, partial[4] = wt.mean, partial[5] = wt.m2;
+  }
+}
+
+// grid = B * nblk: block (b, k) strides over sample b's n elements.  text (optional): m_text given as a tensor (plain CFG,
+// where it is the conditional prediction itself) instead of local + direction.
+__global__ void __launch_bounds__(ED_BLOCK)
+k_guidance_moments(const float* __restrict__ local, const float* __restrict__ dir, const float* __restrict__ text, float g,
+                   int64_t n, int nblk, double* __restrict__ partials) {
+  const int b = blockIdx.x / nblk, k = blockIdx.x % nblk;
+  const float* l = local + (int64_t)b * n;
+  const float* d = dir + (int64_t)b * n;
+  PairAcc acc;
+  for (int64_t i = (int64_t)k * ED_BLOCK + threadIdx.x; i < n; i += (int64_t)nblk * ED_BLOCK) {
+    if (text) acc.add_pair(__fadd_rn(l[i], __fmul_rn(g, d[i])), text[(int64_t)b * n + i]);
+    else acc.add(l[i], d[i], g);
+  }
+  moments_block_store(acc, partials + (int64_t)blockIdx.x * 6);
+}
+
+// The same statistics over the gathers of k_phase_epilogue (direction / local never exist in memory): the first B * nblk_full
+// blocks reduce local + g * direction over (C,H,W), the next B * nblk_low blocks (present when ratio_low is wanted) the
+// reduced-resolution pair uncond_last + g * low_dir of the fused RRG term over (C,h,w).
+template <typename Tag>
+__global__ void __launch_bounds__(ED_BLOCK)
+k_phase_moments(const EpilogueArgs a, int nblk_full, int nblk_low, double* __restrict__ partials) {
+  PairAcc acc;
+  const int full_blocks = a.B * nblk_full;
+  if ((int)blockIdx.x < full_blocks) {
+    const int b = blockIdx.x / nblk_full, k = blockIdx.x % nblk_full;
+    const int64_t n = (int64_t)a.C * a.H * a.W;
+    for (int64_t i = (int64_t)k * ED_BLOCK + threadIdx.x; i < n; i += (int64_t)nblk_full * ED_BLOCK) {
+      int X = (int)(i % a.W);
+      int64_t r = i / a.W;
+      int Y = (int)(r % a.H), c = (int)(r / a.H);
+      acc.add(local_at<Tag>(a, b, c, Y, X), direction_at<Tag>(a, b, c, Y, X), a.g);
+    }
+  } else {
+    const int q = (int)blockIdx.x - full_blocks;
+    const int b = q / nblk_low, k = q % nblk_low;
+    const int64_t n = (int64_t)a.C * a.h * a.w;
+    for (int64_t i = (int64_t)k * ED_BLOCK + threadIdx.x; i < n; i += (int64_t)nblk_low * ED_BLOCK) {
+      int j = (int)(i % a.w);
+      int64_t r = i / a.w;
+      int ii = (int)(r % a.h), c = (int)(r / a.h);
+      acc.add(uncond_last_at<Tag>(a, b, c, ii, j), direction_at<Tag>(a, b, c, a.down_row[ii], a.down_col[j]), a.g);
+    }
+  }
+  moments_block_store(acc, partials + (int64_t)blockIdx.x * 6);
+}
+
+// grid = B (+ B for the reduced-resolution pair), one wave each: lane l merges partials l, l + 64, ... in order, then a
+// shuffle tree; ratio = fp32(std_text) / fp32(std_cfg), one fp32 division.
+__global__ void __launch_bounds__(64)
+k_moments_finalise(const double* __restrict__ partials, int B, int nblk_full, int nblk_low, float* __restrict__ ratio,
+                   float* __restrict__ ratio_low) {
+  const bool low = (int)blockIdx.x >= B;
+  const int b = low ? (int)blockIdx.x - B : (int)blockIdx.x;
+  const int nblk = low ? nblk_low : nblk_full;
+  const double* p = partials + ((low ? (int64_t)B * nblk_full : 0) + (int64_t)b * nblk) * 6;
+  WelfordD wc = {0.0, 0.0, 0.0}, wt = {0.0, 0.0, 0.0};
+  for (int k = threadIdx.x; k < nblk; k += 64) {
+    wc = merge_d(wc, WelfordD{p[k * 6 + 0], p[k * 6 + 1], p[k * 6 + 2]});
+    wt = merge_d(wt, WelfordD{p[k * 6 + 3], p[k * 6 + 4], p[k * 6 + 5]});
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    wc = merge_d(wc, shfl_down_d(wc, off));
+    wt = merge_d(wt, shfl_down_d(wt, off));
+  }
+  if (threadIdx.x == 0) {
+    float std_cfg = (float)sqrt(wc.m2 / (wc.n - 1.0)), std_text = (float)sqrt(wt.m2 / (wt.n - 1.0));
+    (low ? ratio_low : ratio)[b] = __fdiv_rn(std_text, std_cfg);
+  }
+}
+
+inline int moments_blocks(int64_t n) {
+  int64_t g = (n + (int64_t)ED_BLOCK * ED_MOM_PER_THREAD - 1) / ((int64_t)ED_BLOCK * ED_MOM_PER_THREAD);
+  return (int)(g < 1 ? 1 : (g > ED_MOM_MAX_BLOCKS ? ED_MOM_MAX_BLOCKS : g));
 }
 
 // ---- ed_undo_step ----------------------------------------------------------------------------------
@@ -655,12 +834,13 @@ k_undo_s(const float* __restrict__ x_in, const float* __restrict__ noise, const 
 }
 
 // ---- ed_rrg_update ---------------------------------------------------------------------------------
-template <bool VP>
+template <bool VP, bool GR = false>
 __global__ void __launch_bounds__(ED_BLOCK)
 k_rrg_update(const float* __restrict__ prev, const float* __restrict__ x0, const float* __restrict__ low_latent,
              const float* __restrict__ low_uncond, const float* __restrict__ low_dir,
              const int32_t* __restrict__ up_row, const int32_t* __restrict__ up_col, float* __restrict__ out,
-             float g, float sb, float sa, float norm, float weight, int B, int C, int H, int W, int h, int w) {
+             float g, float sb, float sa, float norm, float weight, int B, int C, int H, int W, int h, int w,
+             const Rescale rs) {
   int64_t n = (int64_t)B * C * H * W;
   int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
   if (t >= n) return;
@@ -669,18 +849,19 @@ k_rrg_update(const float* __restrict__ prev, const float* __restrict__ x0, const
   int Y = (int)(r % H);
   int64_t bc = r / H;
   int64_t s = (bc * h + up_row[Y]) * w + up_col[X];
-  float m = __fadd_rn(low_uncond[s], __fmul_rn(g, low_dir[s]));
+  float m = rescaled<GR>(__fadd_rn(low_uncond[s], __fmul_rn(g, low_dir[s])), GR ? rs.ratio[bc / C] : 0.0f, rs.gr, rs.omgr);
   float up = pred_x0<VP>(m, low_latent[s], sb, sa);
   float grad = __fmul_rn(__fmul_rn(norm, __fsub_rn(x0[t], up)), weight);  // d/dx0 of weight*mse(up, x0)
   out[t] = __fadd_rn(prev[t], -grad);
 }
 
-template <bool VP>
+template <bool VP, bool GR = false>
 __global__ void __launch_bounds__(ED_BLOCK)
 k_rrg_update_x4(const float* __restrict__ prev, const float* __restrict__ x0, const float* __restrict__ low_latent,
                 const float* __restrict__ low_uncond, const float* __restrict__ low_dir,
                 const int32_t* __restrict__ up_row, const int32_t* __restrict__ up_col, float* __restrict__ out,
-                float g, float sb, float sa, float norm, float weight, int B, int C, int H, int W, int h, int w) {
+                float g, float sb, float sa, float norm, float weight, int B, int C, int H, int W, int h, int w,
+                const Rescale rs) {
   int W4 = W >> 2;
   int64_t n = (int64_t)B * C * H * W4;
   int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
@@ -693,10 +874,11 @@ k_rrg_update_x4(const float* __restrict__ prev, const float* __restrict__ x0, co
   float4 p = *reinterpret_cast<const float4*>(prev + (t << 2));
   float4 z = *reinterpret_cast<const float4*>(x0 + (t << 2));
   float pv[4] = {p.x, p.y, p.z, p.w}, zv[4] = {z.x, z.y, z.z, z.w}, o[4];
+  const float rt = GR ? rs.ratio[bc / C] : 0.0f;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     int64_t s = base + up_col[X + e];
-    float m = __fadd_rn(low_uncond[s], __fmul_rn(g, low_dir[s]));
+    float m = rescaled<GR>(__fadd_rn(low_uncond[s], __fmul_rn(g, low_dir[s])), rt, rs.gr, rs.omgr);
     float up = pred_x0<VP>(m, low_latent[s], sb, sa);
     float grad = __fmul_rn(__fmul_rn(norm, __fsub_rn(zv[e], up)), weight);
     o[e] = __fadd_rn(pv[e], -grad);
@@ -779,6 +961,16 @@ k_tile_accumulate(const void* __restrict__ dec, float* __restrict__ image, int B
     if (vp) KERNEL<true><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(__VA_ARGS__);   \
     else KERNEL<false><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(__VA_ARGS__);     \
   } while (0)
+
+// ... x guidance-rescale variants: <vp, true> when a ratio buffer is given
+#define ED_LAUNCH_VP_GR(vp, gr, KERNEL, n, ...)                                               \
+  do {                                                                                        \
+    if (!(gr)) ED_LAUNCH_VP(vp, KERNEL, n, __VA_ARGS__);                                      \
+    else if (vp) KERNEL<true, true><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(__VA_ARGS__);  \
+    else KERNEL<false, true><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(__VA_ARGS__);         \
+  } while (0)
+
+static const Rescale NO_RESCALE = {nullptr, 0.0f, 0.0f, 1};
 
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 
@@ -880,11 +1072,14 @@ static int phase_epilogue_launch(bool vp, const void* g_out, const void* v_out, 
                       float* x_next, float* low_dir, float* uncond_last, float* direction, float* local, int K, int B,
                       int C, int H, int W, int h, int w, int gPH, int gPW, int g_off_y, int g_off_x, int vPH, int vPW,
                       int n_col_blocks, float g, float sqrt_beta_t, float sqrt_alpha_t, float sqrt_alpha_prev,
-                      float sqrt_1m_alpha_prev, float rrg_norm, float rrg_weight, void* stream) {
+                      float sqrt_1m_alpha_prev, float rrg_norm, float rrg_weight, void* stream,
+                      const float* ratio = nullptr, const float* ratio_low = nullptr, float gr = 0.0f, float omgr = 0.0f) {
   int64_t n = (int64_t)B * C * H * W + (int64_t)B * C * h * w;
   if ((int64_t)B * C * H * W == 0) return 0;
   if (x_next && !low_latent) return (int)hipErrorInvalidValue;
+  if (ratio && x_next && !ratio_low) return (int)hipErrorInvalidValue;
   EpilogueArgs a;
+  a.ratio = ratio, a.ratio_low = ratio_low, a.gr = gr, a.omgr = omgr;
   a.g_out = g_out, a.v_out = v_out, a.x = x, a.stamp = stamp;
   a.inv_row = inv_row, a.inv_col = inv_col, a.up_row = up_row, a.up_col = up_col, a.down_row = down_row, a.down_col = down_col;
   a.row_blk = row_blk, a.row_src = row_src, a.col_blk = col_blk, a.col_src = col_src;
@@ -894,8 +1089,10 @@ static int phase_epilogue_launch(bool vp, const void* g_out, const void* v_out, 
   a.g_off_x = g_off_x, a.vPH = vPH, a.vPW = vPW, a.ncb = n_col_blocks;
   a.g = g, a.sb = sqrt_beta_t, a.sa = sqrt_alpha_t, a.sp = sqrt_alpha_prev, a.sd = sqrt_1m_alpha_prev;
   a.rrg_norm = rrg_norm, a.rrg_weight = rrg_weight;
-#define ED_EPI(T)                                                                           \
-  if (vp) k_phase_epilogue<T, true><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(a);  \
+#define ED_EPI(T)                                                                                        \
+  if (ratio && vp) k_phase_epilogue<T, true, true><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(a);  \
+  else if (ratio) k_phase_epilogue<T, false, true><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(a);  \
+  else if (vp) k_phase_epilogue<T, true><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(a);            \
   else k_phase_epilogue<T, false><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(a);
   switch (dtype) {
     case ED_F32: ED_EPI(F32) break;
@@ -963,16 +1160,26 @@ int ed_fill_directions(const float* dirs, const int8_t* stamp, const int32_t* in
   return done();
 }
 
+// The 16-byte kernels (k_cfg_ddim_v4) take every call whose element count and buffers allow it; a ratio adds ONE condition,
+// that a sample is a whole number of float4s.  Without a ratio rs.per plays no part: the plain entry points choose as they
+// always did.
+static inline bool cfg_ddim_x4(const float* local, const float* direction, const float* x, const float* prev, const float* x0,
+                               int64_t n, const Rescale& rs) {
+  return (n & 3) == 0 && (!rs.ratio || (rs.per & 3) == 0) && aligned16(local) && aligned16(direction) && aligned16(x) &&
+         aligned16(prev) && aligned16(x0);
+}
+
 static int cfg_ddim_launch(bool vp, const float* local, const float* direction, const float* x, float* prev, float* x0, float g,
                            float sqrt_beta_t, float sqrt_alpha_t, float sqrt_alpha_prev, float sqrt_one_minus_alpha_prev,
-                           int64_t n, void* stream) {
+                           int64_t n, void* stream, const Rescale rs = NO_RESCALE) {
   if (n == 0) return 0;
-  if ((n & 3) == 0 && aligned16(local) && aligned16(direction) && aligned16(x) && aligned16(prev) && aligned16(x0)) {
-    ED_LAUNCH_VP(vp, k_cfg_ddim_v4, n / 4, (const float4*)local, (const float4*)direction, (const float4*)x, (float4*)prev,
-                 (float4*)x0, g, sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev, sqrt_one_minus_alpha_prev, n / 4);
+  if (cfg_ddim_x4(local, direction, x, prev, x0, n, rs)) {
+    ED_LAUNCH_VP_GR(vp, rs.ratio, k_cfg_ddim_v4, n / 4, (const float4*)local, (const float4*)direction, (const float4*)x,
+                    (float4*)prev, (float4*)x0, g, sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev, sqrt_one_minus_alpha_prev,
+                    n / 4, rs);
   } else {
-    ED_LAUNCH_VP(vp, k_cfg_ddim_s, n, local, direction, x, prev, x0, g, sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev,
-                 sqrt_one_minus_alpha_prev, n);
+    ED_LAUNCH_VP_GR(vp, rs.ratio, k_cfg_ddim_s, n, local, direction, x, prev, x0, g, sqrt_beta_t, sqrt_alpha_t,
+                    sqrt_alpha_prev, sqrt_one_minus_alpha_prev, n, rs);
   }
   return done();
 }
@@ -1008,17 +1215,17 @@ int ed_undo_step(const float* x_in, const float* noise, const float* coef, float
 static int rrg_update_launch(bool vp, const float* prev, const float* x0, const float* low_latent, const float* low_uncond,
                              const float* low_dir, const int32_t* up_row, const int32_t* up_col, float* out, float g,
                              float sqrt_beta_t, float sqrt_alpha_t, float norm, float weight, int B, int C, int H, int W,
-                             int h, int w, void* stream) {
+                             int h, int w, void* stream, const Rescale rs = NO_RESCALE) {
   int64_t n = (int64_t)B * C * H * W;
   if (n == 0) return 0;
   if ((W & 3) == 0 && aligned16(prev) && aligned16(x0) && aligned16(out)) {
     n >>= 2;
-    ED_LAUNCH_VP(vp, k_rrg_update_x4, n, prev, x0, low_latent, low_uncond, low_dir, up_row, up_col, out, g, sqrt_beta_t,
-              sqrt_alpha_t, norm, weight, B, C, H, W, h, w);
+    ED_LAUNCH_VP_GR(vp, rs.ratio, k_rrg_update_x4, n, prev, x0, low_latent, low_uncond, low_dir, up_row, up_col, out, g,
+                    sqrt_beta_t, sqrt_alpha_t, norm, weight, B, C, H, W, h, w, rs);
     return done();
   }
-  ED_LAUNCH_VP(vp, k_rrg_update, n, prev, x0, low_latent, low_uncond, low_dir, up_row, up_col, out, g, sqrt_beta_t,
-               sqrt_alpha_t, norm, weight, B, C, H, W, h, w);
+  ED_LAUNCH_VP_GR(vp, rs.ratio, k_rrg_update, n, prev, x0, low_latent, low_uncond, low_dir, up_row, up_col, out, g,
+                  sqrt_beta_t, sqrt_alpha_t, norm, weight, B, C, H, W, h, w, rs);
   return done();
 }
 
@@ -1070,6 +1277,106 @@ int ed_tile_accumulate_normalise(const void* decoded, int dtype, float* image, i
   ED_LAUNCH_T(dtype, k_tile_accumulate, n, decoded, image, B, Cimg, HP, WP, TP, n_col_tiles, row_tile, row_src, col_tile,
                                          col_src);
   return done();
+}
+
+// ---- guidance rescale ------------------------------------------------------------------------------
+int64_t ed_guidance_moments_workspace(int B, int64_t n_full, int64_t n_low) {
+  if (B <= 0 || n_full < 0 || n_low < 0) return 0;
+  int64_t blocks = (int64_t)B * ((n_full ? moments_blocks(n_full) : 0) + (n_low ? moments_blocks(n_low) : 0));
+  return blocks * 6 * (int64_t)sizeof(double);
+}
+
+static inline bool bad_workspace(const void* ws) { return !ws || (((uintptr_t)ws) & 7u) != 0; }
+
+int ed_guidance_moments(const float* local, const float* direction, const float* text, float g, int B, int64_t n,
+                        float* ratio, void* workspace, void* stream) {
+  if (B <= 0 || n <= 0) return B < 0 || n < 0 ? (int)hipErrorInvalidValue : 0;
+  if (bad_workspace(workspace) || !ratio) return (int)hipErrorInvalidValue;
+  int nblk = moments_blocks(n);
+  k_guidance_moments<<<B * nblk, ED_BLOCK, 0, (hipStream_t)stream>>>(local, direction, text, g, n, nblk,
+                                                                     (double*)workspace);
+  k_moments_finalise<<<B, 64, 0, (hipStream_t)stream>>>((const double*)workspace, B, nblk, 0, ratio, nullptr);
+  return done();
+}
+
+int ed_phase_moments(const void* g_out, const void* v_out, int dtype, const int8_t* stamp, const int32_t* inv_row,
+                     const int32_t* inv_col, const int32_t* up_row, const int32_t* up_col, const int32_t* down_row,
+                     const int32_t* down_col, const int32_t* row_blk, const int32_t* row_src, const int32_t* col_blk,
+                     const int32_t* col_src, float* ratio, float* ratio_low, void* workspace, int K, int B, int C, int H,
+                     int W, int h, int w, int gPH, int gPW, int g_off_y, int g_off_x, int vPH, int vPW, int n_col_blocks,
+                     float g, void* stream) {
+  int64_t n_full = (int64_t)C * H * W, n_low = (int64_t)C * h * w;
+  if (B <= 0 || n_full <= 0) return B < 0 || n_full < 0 ? (int)hipErrorInvalidValue : 0;
+  if (bad_workspace(workspace) || !ratio || K <= 0 || (ratio_low && n_low <= 0)) return (int)hipErrorInvalidValue;
+  EpilogueArgs a = {};
+  a.g_out = g_out, a.v_out = v_out, a.stamp = stamp;
+  a.inv_row = inv_row, a.inv_col = inv_col, a.up_row = up_row, a.up_col = up_col, a.down_row = down_row, a.down_col = down_col;
+  a.row_blk = row_blk, a.row_src = row_src, a.col_blk = col_blk, a.col_src = col_src;
+  a.K = K, a.B = B, a.C = C, a.H = H, a.W = W, a.h = h, a.w = w, a.gPH = gPH, a.gPW = gPW, a.g_off_y = g_off_y;
+  a.g_off_x = g_off_x, a.vPH = vPH, a.vPW = vPW, a.ncb = n_col_blocks, a.g = g;
+  int nblk_full = moments_blocks(n_full), nblk_low = ratio_low ? moments_blocks(n_low) : 0;
+  dim3 grid(B * (nblk_full + nblk_low)), block(ED_BLOCK);
+  hipStream_t st_ = (hipStream_t)stream;
+  switch (dtype) {
+    case ED_F32: k_phase_moments<F32><<<grid, block, 0, st_>>>(a, nblk_full, nblk_low, (double*)workspace); break;
+    case ED_F16: k_phase_moments<F16><<<grid, block, 0, st_>>>(a, nblk_full, nblk_low, (double*)workspace); break;
+    case ED_BF16: k_phase_moments<BF16><<<grid, block, 0, st_>>>(a, nblk_full, nblk_low, (double*)workspace); break;
+    default: return (int)hipErrorInvalidValue;
+  }
+  k_moments_finalise<<<ratio_low ? 2 * B : B, 64, 0, st_>>>((const double*)workspace, B, nblk_full, nblk_low, ratio, ratio_low);
+  return done();
+}
+
+int ed_cfg_ddim_step_gr(const float* local, const float* direction, const float* x, float* prev, float* x0, float g,
+                        float sqrt_beta_t, float sqrt_alpha_t, float sqrt_alpha_prev, float sqrt_one_minus_alpha_prev,
+                        int64_t n, int prediction_type, const float* ratio, float gr, float omgr, int B, void* stream) {
+  if (bad_prediction_type(prediction_type)) return (int)hipErrorInvalidValue;
+  Rescale rs = NO_RESCALE;
+  if (ratio) {
+    if (B <= 0 || n % B) return (int)hipErrorInvalidValue;
+    rs.ratio = ratio, rs.gr = gr, rs.omgr = omgr, rs.per = n / B;
+    if (rs.per == 0) return 0;
+  }
+  return cfg_ddim_launch(prediction_type == ED_PRED_V, local, direction, x, prev, x0, g, sqrt_beta_t, sqrt_alpha_t,
+                         sqrt_alpha_prev, sqrt_one_minus_alpha_prev, n, stream, rs);
+}
+
+int ed_cfg_ddim_step_width(const float* local, const float* direction, const float* x, const float* prev, const float* x0,
+                           int64_t n, const float* ratio, int B) {
+  Rescale rs = NO_RESCALE;
+  if (ratio) {
+    if (B <= 0 || n % B) return 0;
+    rs.ratio = ratio, rs.per = n / B;
+  }
+  return cfg_ddim_x4(local, direction, x, prev, x0, n, rs) ? 4 : 1;
+}
+
+int ed_rrg_update_gr(const float* prev, const float* x0, const float* low_latent, const float* low_uncond,
+                     const float* low_dir, const int32_t* up_row, const int32_t* up_col, float* out, float g,
+                     float sqrt_beta_t, float sqrt_alpha_t, float norm, float weight, int B, int C, int H, int W, int h,
+                     int w, int prediction_type, const float* ratio_low, float gr, float omgr, void* stream) {
+  if (bad_prediction_type(prediction_type)) return (int)hipErrorInvalidValue;
+  Rescale rs = NO_RESCALE;
+  if (ratio_low) rs.ratio = ratio_low, rs.gr = gr, rs.omgr = omgr;
+  return rrg_update_launch(prediction_type == ED_PRED_V, prev, x0, low_latent, low_uncond, low_dir, up_row, up_col, out, g,
+                           sqrt_beta_t, sqrt_alpha_t, norm, weight, B, C, H, W, h, w, stream, rs);
+}
+
+int ed_phase_epilogue_gr(const void* g_out, const void* v_out, int dtype, const float* x, const int8_t* stamp,
+                         const int32_t* inv_row, const int32_t* inv_col, const int32_t* up_row, const int32_t* up_col,
+                         const int32_t* down_row, const int32_t* down_col, const int32_t* row_blk, const int32_t* row_src,
+                         const int32_t* col_blk, const int32_t* col_src, const float* low_latent, float* prev, float* x0,
+                         float* x_next, float* low_dir, float* uncond_last, float* direction, float* local, int K, int B,
+                         int C, int H, int W, int h, int w, int gPH, int gPW, int g_off_y, int g_off_x, int vPH, int vPW,
+                         int n_col_blocks, float g, float sqrt_beta_t, float sqrt_alpha_t, float sqrt_alpha_prev,
+                         float sqrt_1m_alpha_prev, float rrg_norm, float rrg_weight, int prediction_type,
+                         const float* ratio, const float* ratio_low, float gr, float omgr, void* stream) {
+  if (bad_prediction_type(prediction_type)) return (int)hipErrorInvalidValue;
+  return phase_epilogue_launch(prediction_type == ED_PRED_V, g_out, v_out, dtype, x, stamp, inv_row, inv_col, up_row, up_col,
+                               down_row, down_col, row_blk, row_src, col_blk, col_src, low_latent, prev, x0, x_next, low_dir,
+                               uncond_last, direction, local, K, B, C, H, W, h, w, gPH, gPW, g_off_y, g_off_x, vPH, vPW,
+                               n_col_blocks, g, sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev, sqrt_1m_alpha_prev, rrg_norm,
+                               rrg_weight, stream, ratio, ratio_low, gr, omgr);
 }
 
 }  // extern "C"

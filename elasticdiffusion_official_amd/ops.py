@@ -200,13 +200,94 @@ def _pred_code(prediction_type):
     return PREDICTION_TYPES[prediction_type]
 
 
+def rescale_coefficients(guidance_rescale):
+    """(gr, omgr) = (float32(guidance_rescale), float32(1 - guidance_rescale)), the two host-side scalars of the rescale
+    m <- gr * (m * ratio) + omgr * m; ``guidance_rescale`` outside [0, 1] raises ValueError."""
+    import numpy as np
+    gr = float(guidance_rescale)
+    if not 0.0 <= gr <= 1.0:          # also refuses NaN
+        raise ValueError(f"guidance_rescale must be in [0, 1], got {guidance_rescale!r}")
+    return float(np.float32(gr)), float(np.float32(1.0 - gr))
+
+
+def _ratio_ptr(ratio, B, name):
+    if not isinstance(ratio, torch.Tensor) or tuple(ratio.shape) != (B,):
+        _reject(f"{name} must be an f32 [{B}] tensor (one ratio per sample), got {tuple(getattr(ratio, 'shape', ()))}")
+    return _dev(ratio, torch.float32, name)
+
+
+def guidance_moments_workspace(B, n_full, n_low=0, device=None):
+    """The partials buffer of guidance_moments / phase_moments for B samples of ``n_full`` elements (+ the
+    reduced-resolution pair of ``n_low`` elements): an f64 tensor, allocate once and reuse (launches on one stream)."""
+    nbytes = _hip.lib().ed_guidance_moments_workspace(int(B), int(n_full), int(n_low))
+    return torch.empty(max(1, nbytes // 8), dtype=torch.float64, device=device)
+
+
+def _workspace(ws, B, n_full, n_low):
+    need = _hip.lib().ed_guidance_moments_workspace(int(B), int(n_full), int(n_low))
+    if not isinstance(ws, torch.Tensor) or ws.numel() * ws.element_size() < need:
+        _reject(f"workspace must hold {need} bytes (guidance_moments_workspace({B}, {n_full}, {n_low}))")
+    return _dev(ws, None, "workspace")
+
+
+def guidance_moments(local, direction, g, ratio, workspace, text=None):
+    """ratio f32 [B] <- std(local + direction) / std(local + g * direction) per sample (unbiased, over everything but
+    dim 0) of two f32 tensors [B, ...]: the guidance-rescale factor of the reference's rescale_noise_cfg, computed on the
+    device (see ed_guidance_moments).  ``text`` (optional, same shape): the numerator's tensor given as is (plain CFG: the
+    conditional prediction) instead of local + direction.  workspace = guidance_moments_workspace(B, n)."""
+    B = ratio.numel()
+    if B == 0 or local.numel() % B or local.shape[0] != B or local.shape != direction.shape:
+        _reject(f"guidance_moments: local / direction must be equal-shaped [B={B}, ...] tensors, got "
+                f"{tuple(local.shape)} / {tuple(direction.shape)}")
+    if text is not None and text.shape != local.shape:
+        _reject(f"guidance_moments: text must have local's shape {tuple(local.shape)}, got {tuple(text.shape)}")
+    n = local.numel() // B
+    _call("ed_guidance_moments", _dev(local, torch.float32, "local"), _dev(direction, torch.float32, "direction"),
+          _opt(text, torch.float32, "text"), float(g), B, n, _dev(ratio, torch.float32, "ratio"), _workspace(workspace, B, n, 0), _stream())
+    TIMER.note_work("ed_guidance_moments", nbytes=(8.0 if text is None else 12.0) * B * n)
+    return ratio
+
+
+def phase_moments(g_out, v_out, shape, stamp, pick_tables, view_tables, n_col_blocks, g_off, K, h, w, g, ratio, workspace,
+                  ratio_low=None):
+    """The ratios guidance_moments would give on the ``direction`` / ``local`` (and, with ``ratio_low``, the
+    ``uncond_last`` / ``low_dir``) by-products of phase_epilogue, reduced straight from the model output rows (see
+    ed_phase_moments): same arguments as phase_epilogue, ``shape`` = (B, C, H, W) of the latent.
+    workspace = guidance_moments_workspace(B, C*H*W, C*h*w if ratio_low is given else 0)."""
+    B, C, H, W = shape
+    gr, C2, gPH, gPW = g_out.shape
+    vr, C3, vPH, vPW = v_out.shape
+    assert gr == K * 2 * B and C2 == C == C3 and vr % B == 0 and g_out.dtype == v_out.dtype
+    assert tuple(stamp.shape) == (h * w, 4)
+    inv_row, inv_col, up_row, up_col, down_row, down_col = pick_tables
+    assert inv_row.numel() == 2 * H and inv_col.numel() == 2 * W and up_row.numel() == H and up_col.numel() == W
+    assert down_row.numel() == h and down_col.numel() == w
+    row_blk, row_src, col_blk, col_src = view_tables
+    assert row_blk.numel() == H * 2 == row_src.numel() and col_blk.numel() == W * 2 == col_src.numel()
+    for t_, name in ((ratio, "ratio"), (ratio_low, "ratio_low")):
+        if t_ is not None and tuple(t_.shape) != (B,):
+            _reject(f"phase_moments: {name} must be f32 [{B}], got {tuple(t_.shape)}")
+    n_low = C * h * w if ratio_low is not None else 0
+    _call("ed_phase_moments", _dev(g_out, None, "g_out"), _dev(v_out, None, "v_out"), _code(g_out, "g_out"),
+          _dev(stamp, torch.int8, "stamp"), *(_dev(t_, torch.int32) for t_ in pick_tables),
+          *(_dev(t_, torch.int32) for t_ in view_tables), _dev(ratio, torch.float32, "ratio"),
+          _opt(ratio_low, torch.float32, "ratio_low"), _workspace(workspace, B, C * H * W, n_low),
+          K, B, C, H, W, h, w, gPH, gPW, g_off[0], g_off[1], vPH, vPW, n_col_blocks, float(g), _stream())
+    # the rows behind every output element: cond + uncond of its step and (at most a few) view centres
+    TIMER.note_work("ed_phase_moments", nbytes=3.0 * g_out.element_size() * B * (C * H * W + n_low))
+    return ratio, ratio_low
+
+
 def phase_epilogue(g_out, v_out, x, stamp, pick_tables, view_tables, n_col_blocks, g_off, K, h, w, g, coef, prev, x0,
                    low_dir=None, uncond_last=None, direction=None, local=None, x_next=None, low_latent=None,
-                   rrg_norm=0.0, rrg_weight=0.0, prediction_type="epsilon"):
+                   rrg_norm=0.0, rrg_weight=0.0, prediction_type="epsilon", ratio=None, ratio_low=None,
+                   guidance_rescale=0.0):
     """unpad_direction + fill_directions + scatter_centres + cfg_ddim_step (+ rrg_update when ``x_next`` is given) in
     one launch (see ed_phase_epilogue / ed_phase_epilogue_pt).  pick_tables = (inv_row, inv_col, up_row, up_col,
     down_row, down_col); view_tables = (row_blk, row_src, col_blk, col_src); coef = DDIMSchedule.step_coefficients(t);
-    prediction_type = the scheduler's ("epsilon" or "v_prediction")."""
+    prediction_type = the scheduler's ("epsilon" or "v_prediction").  ``ratio`` (f32 [B] from phase_moments, with
+    ``ratio_low`` when ``x_next`` is given) applies the guidance rescale ``guidance_rescale`` (ed_phase_epilogue_gr);
+    None is the plain launch."""
     pt = _pred_code(prediction_type)
     B, C, H, W = x.shape
     gr, C2, gPH, gPW = g_out.shape
@@ -224,6 +305,22 @@ def phase_epilogue(g_out, v_out, x, stamp, pick_tables, view_tables, n_col_block
     if x_next is not None and low_latent is None:
         _reject("phase_epilogue: x_next (fused RRG) needs low_latent")
     f32 = torch.float32
+    if ratio is None and (ratio_low is not None or float(guidance_rescale) != 0.0):
+        _reject("phase_epilogue: guidance_rescale / ratio_low need ratio (phase_moments)")
+    if ratio is not None:
+        if x_next is not None and ratio_low is None:
+            _reject("phase_epilogue: the fused RRG term with a rescale needs ratio_low")
+        if ratio_low is not None and tuple(ratio_low.shape) != (B,):
+            _reject(f"ratio_low must be f32 [{B}], got {tuple(ratio_low.shape)}")
+        gr_f, omgr_f = rescale_coefficients(guidance_rescale)  # ValueError before any argument of the launch is taken
+        _call("ed_phase_epilogue_gr", _dev(g_out, None, "g_out"), _dev(v_out, None, "v_out"), _code(g_out, "g_out"),
+              _dev(x, f32, "x"), _dev(stamp, torch.int8, "stamp"), *(_dev(t_, torch.int32) for t_ in pick_tables),
+              *(_dev(t_, torch.int32) for t_ in view_tables), _opt(low_latent, f32, "low_latent"), _dev(prev, f32, "prev"),
+              _dev(x0, f32, "x0"), _opt(x_next, f32, "x_next"), _opt(low_dir, f32, "low_dir"),
+              _opt(uncond_last, f32, "uncond_last"), _opt(direction, f32, "direction"), _opt(local, f32, "local"),
+              K, B, C, H, W, h, w, gPH, gPW, g_off[0], g_off[1], vPH, vPW, n_col_blocks, float(g), *(float(c) for c in coef),
+              float(rrg_norm), float(rrg_weight), pt, _ratio_ptr(ratio, B, "ratio"), _opt(ratio_low, f32, "ratio_low"), gr_f, omgr_f, _stream())
+        return prev, x0
     _call("ed_phase_epilogue_pt" if pt else "ed_phase_epilogue",
           _dev(g_out, None, "g_out"), _dev(v_out, None, "v_out"), _code(g_out, "g_out"),
           _dev(x, f32, "x"), _dev(stamp, torch.int8, "stamp"), *(_dev(t_, torch.int32) for t_ in pick_tables),
@@ -265,16 +362,43 @@ def fill_directions(dirs, stamp, inv_row, inv_col, up_row, up_col, down_row, dow
 
 
 def cfg_ddim_step(local, direction, x, prev, x0, g, sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev, sqrt_1m_alpha_prev,
-                  prediction_type="epsilon"):
+                  prediction_type="epsilon", ratio=None, guidance_rescale=0.0):
+    """``ratio`` (f32 [B] from guidance_moments; the buffers are then B equal samples) applies the guidance rescale to
+    local + g * direction before the update (ed_cfg_ddim_step_gr); None is the plain launch."""
     pt = _pred_code(prediction_type)
     n = x.numel()
     for t in (local, direction, prev, x0):
         assert t.numel() == n
+    if ratio is None and float(guidance_rescale) != 0.0:
+        _reject("cfg_ddim_step: guidance_rescale needs ratio (guidance_moments)")
+    if ratio is not None:
+        B = ratio.numel()
+        if B == 0 or n % B:
+            _reject(f"cfg_ddim_step: {n} elements are not {B} equal samples")
+        gr_f, omgr_f = rescale_coefficients(guidance_rescale)  # ValueError before any argument of the launch is taken
+        _call("ed_cfg_ddim_step_gr",
+              _dev(local, torch.float32), _dev(direction, torch.float32), _dev(x, torch.float32),
+              _dev(prev, torch.float32), _dev(x0, torch.float32), float(g), float(sqrt_beta_t),
+              float(sqrt_alpha_t), float(sqrt_alpha_prev), float(sqrt_1m_alpha_prev), n, pt,
+              _ratio_ptr(ratio, B, "ratio"), gr_f, omgr_f, B, _stream())
+        return prev, x0
     _call("ed_cfg_ddim_step_pt" if pt else "ed_cfg_ddim_step",
           _dev(local, torch.float32), _dev(direction, torch.float32), _dev(x, torch.float32),
           _dev(prev, torch.float32), _dev(x0, torch.float32), float(g), float(sqrt_beta_t),
           float(sqrt_alpha_t), float(sqrt_alpha_prev), float(sqrt_1m_alpha_prev), n, *((pt,) if pt else ()), _stream())
     return prev, x0
+
+
+def cfg_ddim_step_width(local, direction, x, prev, x0, ratio=None):
+    """Elements per thread of the kernels cfg_ddim_step launches for these buffers: 4 (16-byte accesses) or 1 (scalar), by the
+    library's own launch predicate (ed_cfg_ddim_step_width; launches nothing).  Without ``ratio`` the choice depends on the
+    element count and the alignment alone; a ratio also asks that a sample be a whole number of float4s."""
+    n = x.numel()
+    B = 0 if ratio is None else ratio.numel()
+    ptrs = [_dev(t, torch.float32) for t in (local, direction, x, prev, x0)]
+    rp = _opt(ratio, torch.float32, "ratio")
+    _LAUNCH["device"] = None  # a query, not a launch
+    return _hip.lib().ed_cfg_ddim_step_width(*ptrs, n, rp, B)
 
 
 def undo_step(x_in, noise, coef, x_out):
@@ -288,12 +412,25 @@ def undo_step(x_in, noise, coef, x_out):
 
 
 def rrg_update(prev, x0, low_latent, low_uncond, low_dir, up_row, up_col, out, g, sqrt_beta_t, sqrt_alpha_t, norm, weight,
-               prediction_type="epsilon"):
+               prediction_type="epsilon", ratio_low=None, guidance_rescale=0.0):
+    """``ratio_low`` (f32 [B] from guidance_moments on low_uncond / low_dir) applies the guidance rescale to the
+    reduced-resolution prediction low_uncond + g * low_dir (ed_rrg_update_gr); None is the plain launch."""
     pt = _pred_code(prediction_type)
     B, C, H, W = prev.shape
     h, w = low_latent.shape[-2:]
     assert tuple(low_latent.shape) == (B, C, h, w) == tuple(low_uncond.shape) == tuple(low_dir.shape)
     assert up_row.numel() == H and up_col.numel() == W
+    if ratio_low is None and float(guidance_rescale) != 0.0:
+        _reject("rrg_update: guidance_rescale needs ratio_low (guidance_moments)")
+    if ratio_low is not None:
+        gr_f, omgr_f = rescale_coefficients(guidance_rescale)  # ValueError before any argument of the launch is taken
+        _call("ed_rrg_update_gr",
+              _dev(prev, torch.float32), _dev(x0, torch.float32), _dev(low_latent, torch.float32),
+              _dev(low_uncond, torch.float32), _dev(low_dir, torch.float32),
+              _dev(up_row, torch.int32), _dev(up_col, torch.int32), _dev(out, torch.float32),
+              float(g), float(sqrt_beta_t), float(sqrt_alpha_t), float(norm), float(weight),
+              B, C, H, W, h, w, pt, _ratio_ptr(ratio_low, B, "ratio_low"), gr_f, omgr_f, _stream())
+        return out
     _call("ed_rrg_update_pt" if pt else "ed_rrg_update",
           _dev(prev, torch.float32), _dev(x0, torch.float32), _dev(low_latent, torch.float32),
           _dev(low_uncond, torch.float32), _dev(low_dir, torch.float32),

@@ -89,6 +89,20 @@ class _Plan:
     """Per-call geometry: host plans (geometry.py) + their int32 device tables + the pick sampler."""
 
 
+class _Rescale:
+    """Guidance rescale of ONE image in flight (``guidance_rescale`` > 0): the factor and its device buffers -- the
+    per-sample std ratios the moments kernels write and the epilogue / DDIM / RRG kernels read (never the host), and the
+    partials workspace.  Allocated once per image; every phase reuses them (launches are ordered on one stream).
+    ``ratio_low`` (B floats) and the reduced-resolution part of the workspace (a few KB) are allocated whether or not RRG ever
+    becomes active in the run: cheaper than deciding it per timestep."""
+
+    def __init__(self, gr, B, n_full, n_low, device):
+        self.gr = gr
+        self.ratio = torch.empty(B, device=device, dtype=torch.float32)
+        self.ratio_low = torch.empty(B, device=device, dtype=torch.float32)
+        self.ws = ops.guidance_moments_workspace(B, n_full, n_low, device)
+
+
 class _ModelCall:
     """One request of a denoising program to the model boundary: ``rows`` [n,C,d,d] in the model dtype at timestep
     ``t`` (0-d device tensor) with per-row text / pooled / ControlNet-condition rows.  Programs are generators that
@@ -464,12 +478,15 @@ class ElasticDiffusion(nn.Module):
                                 x_rows, text, pooled, cond_rows, t_dev)
 
     # ---- one estimation phase (ED:1016-1035 or ED:1043-1056) ---------------------------------------
-    def _phase_steps(self, P, x, ti, K, g, drop_p, emb, cond=None, direct=True, rrg_w=None, rrg_norm=0.0, frames=None):
+    def _phase_steps(self, P, x, ti, K, g, drop_p, emb, cond=None, direct=True, rrg_w=None, rrg_norm=0.0, frames=None,
+                     rescale=None):
         """Generator: pre-model glue -> ``yield _ModelCall`` (receives the model output rows) -> post-model glue;
         returns (prev, x0, info).  ``direct``: assemble straight into the hipGraph's static input (one image in flight,
         one rank); otherwise into a scratch batch the driver concatenates / the sharder slices.  ``rrg_w``: this is the
         last phase of a timestep with Reduced-Resolution Guidance active -- with FUSED_GLUE the epilogue then also
-        produces info["x_next"] = prev + RRG term (ED:1061-1078)."""
+        produces info["x_next"] = prev + RRG term (ED:1061-1078).  ``rescale`` (a ``_Rescale``): the guided model output is
+        std-rescaled before the DDIM update -- one moments reduction over the same rows, then the rescale-aware kernels;
+        with ``rrg_w`` the reduced-resolution pair gets its own ratio (info["ratio_low"])."""
         B, C = x.shape[:2]
         dev, mdt = self.device, self.model_dtype
         n_g, n_v = 2 * K * B, P.views.V * B
@@ -521,19 +538,26 @@ class ElasticDiffusion(nn.Module):
         low_dir = torch.empty(B, C, P.h, P.w, device=dev, dtype=torch.float32)
         prev, x0 = torch.empty_like(x), torch.empty_like(x)
         x_next, direction, local = None, None, None
+        pt = self.scheduler.config.prediction_type
+        ratio_low = rescale.ratio_low if rescale is not None and rrg_w is not None else None
         if FUSED_GLUE:
             keep = self.verbose  # the full-resolution direction / local score are only by-products for the image logs
             direction = torch.empty_like(x) if keep else None
             local = torch.empty_like(x) if keep else None
             x_next = torch.empty_like(x) if rrg_w is not None else None
-            ops.phase_epilogue(g_out, v_out, x, stamp,
-                               (P.inv_row, P.inv_col, P.up_row, P.up_col, P.down_row, P.down_col),
-                               (P.row_blk, P.row_src, P.col_blk, P.col_src), P.views.n_col_blocks,
+            pick_t = (P.inv_row, P.inv_col, P.up_row, P.up_col, P.down_row, P.down_col)
+            view_t = (P.row_blk, P.row_src, P.col_blk, P.col_src)
+            rs_kw = {}
+            if rescale is not None:
+                ops.phase_moments(g_out, v_out, x.shape, stamp, pick_t, view_t, P.views.n_col_blocks,
+                                  (P.gpad.top, P.gpad.left), K, P.h, P.w, np.float32(g), rescale.ratio, rescale.ws,
+                                  ratio_low=ratio_low)
+                rs_kw = dict(ratio=rescale.ratio, ratio_low=ratio_low, guidance_rescale=rescale.gr)
+            ops.phase_epilogue(g_out, v_out, x, stamp, pick_t, view_t, P.views.n_col_blocks,
                                (P.gpad.top, P.gpad.left), K, P.h, P.w, np.float32(g), self._step_coef[ti], prev, x0,
                                low_dir=low_dir, uncond_last=uncond_last, direction=direction, local=local, x_next=x_next,
                                low_latent=low[K - 1] if rrg_w is not None else None, rrg_norm=rrg_norm,
-                               rrg_weight=0.0 if rrg_w is None else np.float32(rrg_w),
-                               prediction_type=self.scheduler.config.prediction_type)
+                               rrg_weight=0.0 if rrg_w is None else np.float32(rrg_w), prediction_type=pt, **rs_kw)
         else:
             dirs = torch.empty(K, B, C, P.h, P.w, device=dev, dtype=torch.float32)
             ops.unpad_direction(g_out, dirs, uncond_last, P.gpad.top, P.gpad.left)
@@ -542,11 +566,16 @@ class ElasticDiffusion(nn.Module):
                                 low_dir)
             local = torch.empty_like(x)
             ops.scatter_centres(v_out, local, P.views.n_col_blocks, P.row_blk, P.row_src, P.col_blk, P.col_src)
-            ops.cfg_ddim_step(local, direction, x, prev, x0, np.float32(g), *self._step_coef[ti],
-                              prediction_type=self.scheduler.config.prediction_type)
+            rs_kw = {}
+            if rescale is not None:
+                ops.guidance_moments(local, direction, np.float32(g), rescale.ratio, rescale.ws)
+                if ratio_low is not None:  # the pair ops.rrg_update forms (in _program)
+                    ops.guidance_moments(uncond_last, low_dir, np.float32(g), ratio_low, rescale.ws)
+                rs_kw = dict(ratio=rescale.ratio, guidance_rescale=rescale.gr)
+            ops.cfg_ddim_step(local, direction, x, prev, x0, np.float32(g), *self._step_coef[ti], prediction_type=pt, **rs_kw)
         self.host_s["phase_total"] += time.perf_counter() - h0
         info = {"low_latent": low[K - 1], "uncond_score": uncond_last, "low_direction": low_dir,
-                "direction": direction, "local": local, "init_low": low[0], "x_next": x_next}
+                "direction": direction, "local": local, "init_low": low[0], "x_next": x_next, "ratio_low": ratio_low}
         return prev, x0, info
 
     def _drive(self, program):
@@ -611,9 +640,11 @@ class ElasticDiffusion(nn.Module):
 
     # ---- the loop (ED:953-1078) --------------------------------------------------------------------
     def _setup_run(self, height, width, num_inference_steps, guidance_scale, resampling_steps, new_p, rrg_stop_t,
-                   rrg_init_weight, rrg_scherduler_cls, cosine_scale, repaint_sampling, controlnet_conditioning_scale):
+                   rrg_init_weight, rrg_scherduler_cls, cosine_scale, repaint_sampling, controlnet_conditioning_scale,
+                   guidance_rescale=0.0):
         """Everything of one ``generate_image`` call that does not depend on the prompt, the seed or the condition
         image: geometry tables, schedules, the noised pad-background frames.  Shared by all images in flight."""
+        ops.rescale_coefficients(guidance_rescale)  # ValueError outside [0, 1], before anything is launched
         self._mark("start")
         self.host_s = {"picks": 0.0, "phase_total": 0.0, "noise": 0.0, "stager_wait": 0.0}
         self._stager.waited = 0.0
@@ -651,6 +682,7 @@ class ElasticDiffusion(nn.Module):
             self._runner.entries.clear()  # the scale is a constant inside captured graphs
         self._cn_scale = controlnet_conditioning_scale
         S.guidance, S.drop_p = guidance_scale, 1 - new_p
+        S.guidance_rescale = float(guidance_rescale)  # 0 = plain CFG: the loop launches what it always launched
         S.norm = np.float32(2.0 / (C * P.Hl * P.Wl))
         return S
 
@@ -678,12 +710,15 @@ class ElasticDiffusion(nn.Module):
             cond = self._condition_rows(P, condition_image, B, S.Ks)
         logs = {"x0": [], "rrg_x0": [], "init_low": None, "embeds": (un, co, pun, pco)} if self.verbose else None
         self._logs = logs
+        rescale = None
+        if S.guidance_rescale:
+            rescale = _Rescale(S.guidance_rescale, B, S.C * P.Hl * P.Wl, S.C * P.h * P.w, self.device)
         for i, t in enumerate(progress(self._timesteps)):
             w_i = S.rrg(i)
             rrg_w = w_i if w_i > 10 else None  # ED:1061-1062
             two_phase = S.repaint and i < S.T - 1
             prev, x0, info = yield from self._phase_steps(P, x, i, S.R + 1, S.guidance, S.drop_p, emb, cond, direct,
-                                                          None if two_phase else rrg_w, S.norm, frames)
+                                                          None if two_phase else rrg_w, S.norm, frames, rescale)
             if logs is not None and logs["init_low"] is None:
                 # ED:1023-1024: taken right after the FIRST direction estimate, i.e. before the RePaint phase replaces
                 # ``info`` with the one of the undone sample (ED:1043)
@@ -693,13 +728,16 @@ class ElasticDiffusion(nn.Module):
                 x = self._undo(prev, i + 1)
                 cfg = S.guidance / 3
                 prev, x0, info = yield from self._phase_steps(P, x, i, 1, cfg, S.drop_p, emb, cond, direct, rrg_w, S.norm,
-                                                              frames)
+                                                              frames, rescale)
             if logs is not None:  # verbose image logs (ED:1058-1059, 1073-1076)
                 if i % self.log_freq == 0:
                     logs["x0"].append(x0.clone())
                     if rrg_w is not None:  # the reduced-resolution x0 the guidance pulls towards (ED:909-921)
                         sb, sa = self._step_coef[i][0], self._step_coef[i][1]
                         out = info["uncond_score"] + np.float32(cfg) * info["low_direction"]
+                        if info["ratio_low"] is not None:  # the rescaled prediction the RRG term was formed from
+                            gr, omgr = ops.rescale_coefficients(S.guidance_rescale)
+                            out = gr * (out * info["ratio_low"].view(-1, 1, 1, 1)) + omgr * out
                         if self.scheduler.config.prediction_type == "v_prediction":
                             logs["rrg_x0"].append(np.float32(sa) * info["low_latent"] - np.float32(sb) * out)
                         else:
@@ -711,7 +749,8 @@ class ElasticDiffusion(nn.Module):
                 nxt = torch.empty_like(prev)
                 ops.rrg_update(prev, x0, info["low_latent"], info["uncond_score"], info["low_direction"], P.up_row,
                                P.up_col, nxt, np.float32(cfg), sb, sa, S.norm, np.float32(w_i),
-                               prediction_type=self.scheduler.config.prediction_type)
+                               prediction_type=self.scheduler.config.prediction_type, ratio_low=info["ratio_low"],
+                               guidance_rescale=S.guidance_rescale if info["ratio_low"] is not None else 0.0)
                 x = nxt
             else:
                 x = prev
@@ -725,10 +764,13 @@ class ElasticDiffusion(nn.Module):
                          guidance_scale=10.0, resampling_steps=20, new_p=0.3, rrg_stop_t=0.2, rrg_init_weight=1000,
                          rrg_scherduler_cls=CosineScheduler, cosine_scale=3.0, repaint_sampling=True,
                          progress=_identity_progress, condition_image=None, controlnet_conditioning_scale=1.0,
-                         trace=None):
+                         trace=None, guidance_rescale=0.0):
+        """``guidance_rescale`` in [0, 1] (diffusers' keyword; 0 = off): the std rescale of the guided model output of
+        arXiv 2305.08891 section 3.4, what zero-terminal-SNR / v-prediction checkpoints are meant to be sampled with
+        (DESIGN.md section 17)."""
         S = self._setup_run(height, width, num_inference_steps, guidance_scale, resampling_steps, new_p, rrg_stop_t,
                             rrg_init_weight, rrg_scherduler_cls, cosine_scale, repaint_sampling,
-                            controlnet_conditioning_scale)
+                            controlnet_conditioning_scale, guidance_rescale)
         self._runner.new_image()
         x = self._drive(self._program(S, prompts, negative_prompts, condition_image, trace, progress, direct=True))
         self.last_latents = x
@@ -741,7 +783,8 @@ class ElasticDiffusion(nn.Module):
     def generate_latents_interleaved(self, jobs, in_flight=2, height=768, width=768, num_inference_steps=50,
                                      guidance_scale=10.0, resampling_steps=20, new_p=0.3, rrg_stop_t=0.2,
                                      rrg_init_weight=1000, rrg_scherduler_cls=CosineScheduler, cosine_scale=3.0,
-                                     repaint_sampling=True, controlnet_conditioning_scale=1.0, on_done=None):
+                                     repaint_sampling=True, controlnet_conditioning_scale=1.0, on_done=None,
+                                     guidance_rescale=0.0):
         """Several images of the SAME size / settings in flight at once (new; the reference has nothing like it).
 
         ``jobs`` = list of dicts {prompts, negative_prompts="", seed, condition_image=None}.  Each job is one
@@ -755,7 +798,7 @@ class ElasticDiffusion(nn.Module):
         (``on_done(index, latent)`` is called as each finishes, e.g. to decode it)."""
         S = self._setup_run(height, width, num_inference_steps, guidance_scale, resampling_steps, new_p, rrg_stop_t,
                             rrg_init_weight, rrg_scherduler_cls, cosine_scale, repaint_sampling,
-                            controlnet_conditioning_scale)
+                            controlnet_conditioning_scale, guidance_rescale)
         self._runner.new_image()
         results = [None] * len(jobs)
         queue = list(range(len(jobs)))
@@ -841,12 +884,15 @@ class ElasticDiffusion(nn.Module):
 
     @_on_own_device
     @torch.no_grad()
-    def generate(self, latent, text_embeds, add_text_embeds, guidance_scale=7.5):
+    def generate(self, latent, text_embeds, add_text_embeds, guidance_scale=7.5, guidance_rescale=0.0):
         """ED:761-796: plain CFG + DDIM generation of ``latent`` (B,C,h,w; the reference calls it on the initial
         reduced-resolution latent for its ``verbose`` image log) over the scheduler's current timesteps.
         ``text_embeds`` / ``add_text_embeds`` = cat([uncond, cond]) like the reference's.  A latent smaller than the
         model's native size is padded with the noised-background frames (ED:404-411).
+        ``guidance_rescale`` > 0: the reference's rescale_noise_cfg (ED:800-811) on uncond + g * (cond - uncond) with
+        noise_pred_text = cond, its std ratio computed on the device.
         -> (PIL image of the first sample, {"inter_x0": [pred_original_sample every log_freq steps]})"""
+        ops.rescale_coefficients(guidance_rescale)
         dev, mdt = self.device, self.model_dtype
         x = latent.to(dev, torch.float32).contiguous()
         B, C, h, w = x.shape
@@ -864,6 +910,10 @@ class ElasticDiffusion(nn.Module):
         self._time_ids.copy_(torch.tensor([[d0, d1, 0, 0, d0, d1]], dtype=torch.float32))
         self._runner.new_image()
         inter = []
+        rs_kw = {}
+        if guidance_rescale:
+            ws = ops.guidance_moments_workspace(B, C * h * w, 0, dev)
+            rs_kw = dict(ratio=torch.empty(B, device=dev, dtype=torch.float32), guidance_rescale=guidance_rescale)
         for i, t in enumerate(ts):
             if pad.padded:  # the reference re-seeds the global generators once per pad strip (ED:359)
                 host_rng.replay_strip_reseeds(len(pad.strips))
@@ -875,9 +925,12 @@ class ElasticDiffusion(nn.Module):
             out = out[:, :, pad.top:pad.top + h, pad.left:pad.left + w].float()
             uncond, cnd = out[:B].contiguous(), out[B:].contiguous()
             prev, x0 = torch.empty_like(x), torch.empty_like(x)
-            ops.cfg_ddim_step(uncond, (cnd - uncond).contiguous(), x, prev, x0, np.float32(guidance_scale),
+            direction = (cnd - uncond).contiguous()
+            if rs_kw:
+                ops.guidance_moments(uncond, direction, np.float32(guidance_scale), rs_kw["ratio"], ws, text=cnd)
+            ops.cfg_ddim_step(uncond, direction, x, prev, x0, np.float32(guidance_scale),
                               *self.scheduler.step_coefficients(t),
-                              prediction_type=self.scheduler.config.prediction_type)
+                              prediction_type=self.scheduler.config.prediction_type, **rs_kw)
             x = prev
             if i % self.log_freq == 0:
                 inter.append(x0.cpu())
@@ -889,7 +942,7 @@ class ElasticDiffusion(nn.Module):
         arr = imgs.mul(255).byte().permute(0, 2, 3, 1).cpu().numpy()  # what ToPILImage does for float CHW (ED:1125)
         return [Image.fromarray(a) for a in arr]
 
-    def _image_log(self, decode_fn, guidance_scale):
+    def _image_log(self, decode_fn, guidance_scale, guidance_rescale=0.0):
         """ED:1092-1118: the ``verbose`` image log of the last single-image run (grids via make_grid's defaults)."""
         logs, image_log = getattr(self, "_logs", None), {}
         if not logs:
@@ -902,7 +955,7 @@ class ElasticDiffusion(nn.Module):
         if logs["init_low"] is not None:
             un, co, pun, pco = logs["embeds"]
             image_log["global_img"], info = self.generate(logs["init_low"], torch.cat([un, co]), torch.cat([pun, pco]),
-                                                          guidance_scale=guidance_scale)
+                                                          guidance_scale=guidance_scale, guidance_rescale=guidance_rescale)
             if info["inter_x0"]:
                 image_log["global_img_inter_x0_imgs"] = grid_of([z.to(self.device) for z in info["inter_x0"]])
         if logs["x0"]:
@@ -949,16 +1002,17 @@ class ElasticDiffusion(nn.Module):
     def generate_image(self, prompts, negative_prompts="", height=768, width=768, num_inference_steps=50,
                        guidance_scale=10.0, resampling_steps=20, new_p=0.3, rrg_stop_t=0.2, rrg_init_weight=1000,
                        rrg_scherduler_cls=CosineScheduler, cosine_scale=3.0, repaint_sampling=True,
-                       progress=_default_progress, tiled_decoder=False, grid=False, *, condition_image=None,
-                       controlnet_conditioning_scale=1.0, output_type="pil"):
-        """ED:953-965 signature (ControlNet keywords of EDC:1120-1134 are keyword-only here).
+                       progress=_default_progress, tiled_decoder=False, grid=False, guidance_rescale=0.0, *,
+                       condition_image=None, controlnet_conditioning_scale=1.0, output_type="pil"):
+        """ED:953-965 signature (ControlNet keywords of EDC:1120-1134 are keyword-only here), then ``guidance_rescale``
+        (diffusers' keyword, see ``generate_latents``).
         Returns ``(images, image_log)``; images are PIL by default, a float tensor with ``output_type='pt'``."""
         z = self.generate_latents(prompts, negative_prompts, height, width, num_inference_steps, guidance_scale,
                                   resampling_steps, new_p, rrg_stop_t, rrg_init_weight, rrg_scherduler_cls,
                                   cosine_scale, repaint_sampling, progress, condition_image,
-                                  controlnet_conditioning_scale)
+                                  controlnet_conditioning_scale, guidance_rescale=guidance_rescale)
         dec = self.tiled_decode if tiled_decoder else self.decode_latents
-        image_log = self._image_log(dec, guidance_scale) if self.verbose else {}  # ED:1092-1118 (before the final decode)
+        image_log = self._image_log(dec, guidance_scale, guidance_rescale) if self.verbose else {}  # ED:1092-1118 (before the final decode)
         imgs = torch.cat([dec(z[i:i + 1]) for i in range(len(z))])  # decode_bs = 1 (ED:1090, 1121)
         self._mark("decode_done")
         if grid:
@@ -1099,7 +1153,8 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
                        num_inference_steps=50, guidance_scale=10.0, controlnet_conditioning_scale=1.0,
                        resampling_steps=20, new_p=0.3, rrg_stop_t=0.2, rrg_init_weight=1000,
                        rrg_scherduler_cls=CosineScheduler, cosine_scale=3.0, repaint_sampling=True,
-                       progress=_default_progress, tiled_decoder=False, grid=False, *, output_type="pil"):
+                       progress=_default_progress, tiled_decoder=False, grid=False, guidance_rescale=0.0, *,
+                       output_type="pil"):
         if condition_image is None:
             raise ValueError("condition_image is required (EDC:1183-1193)")
         h, w = self.get_downsample_size(height, width)
@@ -1107,6 +1162,6 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
         cond = self._to_condition_tensor(condition_image, h * s, w * s)
         return super().generate_image(prompts, negative_prompts, height, width, num_inference_steps, guidance_scale,
                                       resampling_steps, new_p, rrg_stop_t, rrg_init_weight, rrg_scherduler_cls,
-                                      cosine_scale, repaint_sampling, progress, tiled_decoder, grid,
+                                      cosine_scale, repaint_sampling, progress, tiled_decoder, grid, guidance_rescale,
                                       condition_image=cond, controlnet_conditioning_scale=controlnet_conditioning_scale,
                                       output_type=output_type)

@@ -351,6 +351,77 @@ int ed_phase_epilogue_pt(const void* g_out, const void* v_out, int dtype, const 
                          float sqrt_1m_alpha_prev, float rrg_norm, float rrg_weight, int prediction_type, void* stream);
 
 /*
+ * ---- guidance rescale (arXiv 2305.08891 section 3.4; the reference's rescale_noise_cfg, ED:800-811) ----
+ * Wherever a guided model output m_cfg = local + g * direction is handed to the DDIM update (ED:1031, 1053) or to the
+ * reduced-resolution x0 of RRG (ED:920), guidance_rescale > 0 replaces it by
+ *   m = gr * (m_cfg * ratio[b]) + omgr * m_cfg,   ratio[b] = std(m_text[b]) / std(m_cfg[b]),   m_text = local + direction
+ * with the unbiased std over all elements of sample b, gr = float32(guidance_rescale), omgr = float32(1 - guidance_rescale).
+ * The elementwise part rounds every product and sum on its own in that order (bit-identical to torch on the CPU given the
+ * same ratio); ratio is a float[B] DEVICE buffer written by one of the two moments entry points and read by the *_gr
+ * consumers -- nothing synchronises the host.
+ *
+ * The moments entry points reduce deterministically (fixed partial layout in the caller's workspace, partials merged in a
+ * fixed order by a second tiny launch, no atomics), in fp64 with shifted sums: each std is the fp32 rounding of its fp64
+ * value, the ratio one fp32 division.  ed_guidance_moments_workspace -> bytes needed (8-byte aligned buffer) for B samples
+ * of n_full elements plus, when n_low > 0, the reduced-resolution pair of n_low elements.
+ */
+int64_t ed_guidance_moments_workspace(int B, int64_t n_full, int64_t n_low);
+
+/*
+ * ed_guidance_moments -- ratio[b] for flat f32 buffers local, direction [B, n] and guidance g (the un-fused path and the
+ * reduced-resolution pair uncond_last / low_dir).  text f32 [B, n] (optional): m_text as a tensor instead of
+ * local + direction -- plain CFG (generate(), ED:761-796), where noise_pred_text is the conditional prediction itself.
+ * workspace: ed_guidance_moments_workspace(B, n, 0) bytes.
+ */
+int ed_guidance_moments(const float* local, const float* direction, const float* text, float g, int B, int64_t n,
+                        float* ratio, void* workspace, void* stream);
+
+/*
+ * ed_phase_moments -- the same ratios over the gathers of ed_phase_epilogue (same tables and model output rows; direction /
+ * local still never go through HBM): ratio f32 [B] over (C,H,W) of local + g * direction and, when ratio_low != NULL,
+ * ratio_low f32 [B] over (C,h,w) of uncond_last + g * low_dir (the pair of the fused RRG term).
+ * workspace: ed_guidance_moments_workspace(B, C*H*W, ratio_low ? C*h*w : 0) bytes.
+ */
+int ed_phase_moments(const void* g_out, const void* v_out, int dtype, const int8_t* stamp, const int32_t* inv_row,
+                     const int32_t* inv_col, const int32_t* up_row, const int32_t* up_col, const int32_t* down_row,
+                     const int32_t* down_col, const int32_t* row_blk, const int32_t* row_src, const int32_t* col_blk,
+                     const int32_t* col_src, float* ratio, float* ratio_low, void* workspace, int K, int B, int C, int H,
+                     int W, int h, int w, int gPH, int gPW, int g_off_y, int g_off_x, int vPH, int vPW, int n_col_blocks,
+                     float g, void* stream);
+
+/*
+ * ed_cfg_ddim_step_gr / ed_rrg_update_gr / ed_phase_epilogue_gr -- the *_pt entry points with the rescale applied to the
+ * guided model output (ratio f32 [B]; B samples of n / B elements for the flat step) and, in the RRG term, to the
+ * reduced-resolution one (ratio_low f32 [B]; required by ed_phase_epilogue_gr when both ratio and x_next are given).
+ * A NULL ratio launches exactly the kernels the *_pt entry point launches.
+ */
+int ed_cfg_ddim_step_gr(const float* local, const float* direction, const float* x, float* prev, float* x0,
+                        float g, float sqrt_beta_t, float sqrt_alpha_t, float sqrt_alpha_prev,
+                        float sqrt_one_minus_alpha_prev, int64_t n, int prediction_type, const float* ratio, float gr,
+                        float omgr, int B, void* stream);
+/*
+ * ed_cfg_ddim_step_width -- launches nothing: the elements per thread (4 = the 16-byte kernels, 1 = the scalar ones) that
+ * ed_cfg_ddim_step / _pt / _gr choose for these buffers, by the very predicate they launch by (ratio NULL = the plain entry
+ * points, B ignored).  0 = arguments ed_cfg_ddim_step_gr refuses.  For tests and callers that want to know which path runs.
+ */
+int ed_cfg_ddim_step_width(const float* local, const float* direction, const float* x, const float* prev, const float* x0,
+                           int64_t n, const float* ratio, int B);
+int ed_rrg_update_gr(const float* prev, const float* x0, const float* low_latent, const float* low_uncond,
+                     const float* low_dir, const int32_t* up_row, const int32_t* up_col, float* out,
+                     float g, float sqrt_beta_t, float sqrt_alpha_t, float norm, float weight,
+                     int B, int C, int H, int W, int h, int w, int prediction_type, const float* ratio_low, float gr,
+                     float omgr, void* stream);
+int ed_phase_epilogue_gr(const void* g_out, const void* v_out, int dtype, const float* x, const int8_t* stamp,
+                         const int32_t* inv_row, const int32_t* inv_col, const int32_t* up_row, const int32_t* up_col,
+                         const int32_t* down_row, const int32_t* down_col, const int32_t* row_blk, const int32_t* row_src,
+                         const int32_t* col_blk, const int32_t* col_src, const float* low_latent, float* prev, float* x0,
+                         float* x_next, float* low_dir, float* uncond_last, float* direction, float* local, int K, int B,
+                         int C, int H, int W, int h, int w, int gPH, int gPW, int g_off_y, int g_off_x, int vPH, int vPW,
+                         int n_col_blocks, float g, float sqrt_beta_t, float sqrt_alpha_t, float sqrt_alpha_prev,
+                         float sqrt_1m_alpha_prev, float rrg_norm, float rrg_weight, int prediction_type,
+                         const float* ratio, const float* ratio_low, float gr, float omgr, void* stream);
+
+/*
  * ed_flash_attention -- fused attention forward of the UNet's transformer blocks (what diffusers' AttnProcessor2_0
  * does with F.scaled_dot_product_attention inside `self.unet(...)`, ED:422-426): out = softmax(scale * Q K^T) V per
  * (batch, head), never materialising the Nq x Nk score matrix.  MFMA 32x32x16 (bf16 / f16), online softmax in fp32.
