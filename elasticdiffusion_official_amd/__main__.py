@@ -13,7 +13,9 @@ flag of the same name (resize to the reduced resolution, canny on the device / i
 extracted condition as ``condition.png``.  ``--prediction_type``, ``--timestep_spacing`` and
 ``--rescale_betas_zero_snr`` override what the snapshot's ``scheduler/scheduler_config.json`` says (or the SD defaults
 without ``--weights``); the reference takes these from the hub config only.  ``--guidance_rescale`` is diffusers' keyword of
-that name (0 = off), what such checkpoints are meant to be sampled with.
+that name (0 = off), what such checkpoints are meant to be sampled with.  ``--init_image FILE`` with ``--strength`` (and
+``--mask_image FILE``: white = repaint, black = keep) is image-to-image / inpainting with diffusers' semantics; the picture is
+resized to H x W with Pillow's Lanczos filter, a mask of the picture's size with NEAREST.
 """
 import argparse
 import os
@@ -70,6 +72,11 @@ def build_parser():
     ap.add_argument("--guidance_rescale", type=float, default=0.0,
                     help="std rescale of the guided prediction in [0, 1] (arXiv 2305.08891 section 3.4; diffusers' "
                     "guidance_rescale), for zero-terminal-SNR / v-prediction checkpoints; 0 = off")
+    ap.add_argument("--init_image", type=str, default=None, help="start from this picture instead of pure noise "
+                    "(image-to-image; resized to H x W)")
+    ap.add_argument("--strength", type=float, default=1.0, help="fraction of the schedule an --init_image run executes, in "
+                    "(0, 1] (diffusers' strength); 1 = all of it")
+    ap.add_argument("--mask_image", type=str, default=None, help="inpainting mask for --init_image: white = repaint, black = keep")
     return ap
 
 
@@ -77,6 +84,11 @@ def main(argv=None):
     opt = build_parser().parse_args(argv)
     if not 0.0 <= opt.guidance_rescale <= 1.0:
         raise SystemExit(f"--guidance_rescale must be in [0, 1], got {opt.guidance_rescale}")
+    from .pipeline import check_img2img_arguments
+    try:
+        check_img2img_arguments(opt.steps, opt.init_image, opt.strength, opt.mask_image)
+    except ValueError as e:
+        raise SystemExit(f"--init_image / --strength / --mask_image: {e}")
 
     from . import ElasticDiffusion, ElasticDiffusionControlNet
     if not torch.cuda.is_available():
@@ -105,6 +117,11 @@ def main(argv=None):
     else:
         sd = ElasticDiffusion(device, opt.sd_version, verbose=opt.verbose, log_freq=opt.log_freq,
                               view_batch_size=opt.view_batch_size, low_vram=opt.low_vram, **kw)
+    if opt.init_image:
+        from PIL import Image
+        extra["init_image"], extra["strength"] = Image.open(opt.init_image).convert("RGB"), opt.strength
+        if opt.mask_image:
+            extra["mask_image"] = Image.open(opt.mask_image).convert("L")
     sd.seed_everything(opt.seed)
     t0 = time.time()
     imgs, image_log = sd.generate_image(prompts=[opt.prompt] * opt.num_sampled, negative_prompts=opt.negative,

@@ -942,6 +942,120 @@ k_tile_accumulate(const void* __restrict__ dec, float* __restrict__ image, int B
   image[t] = __fdiv_rn(sum, cnt);
 }
 
+// ---- img2img / inpainting glue ------------------------------------------------
+// Four pure streaming kernels that run once per image (the first three) or once per phase (the blend), on 12 MB of pixels at
+// most and 64 KiB - 1 MiB latents: one thread per 4 elements with 16-byte accesses where the extents and pointers allow it, a
+// scalar kernel otherwise; both evaluate the same expression per element, so they give the same bits.
+
+// ed_u8_to_vae_input: v -> 2 * (v / 255) - 1, each operation rounded on its own (np.float32(v) / 255, then 2 * x - 1)
+__device__ __forceinline__ float vae_input_of(uint32_t v) {
+  return __fsub_rn(__fmul_rn(2.0f, __fdiv_rn((float)v, 255.0f)), 1.0f);
+}
+
+// 4 pixels per thread: 12 interleaved bytes as three aligned dwords in, one 4-element vector store per colour plane out
+template <typename Tag>
+__global__ void __launch_bounds__(ED_BLOCK)
+k_u8_to_vae_input_x4(const uint32_t* __restrict__ img, void* __restrict__ out, int64_t HW) {
+  int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
+  if (t >= (HW >> 2)) return;
+  uint32_t w0 = img[3 * t], w1 = img[3 * t + 1], w2 = img[3 * t + 2];  // R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3
+  int64_t p = t << 2;
+  st4<Tag>(out, p, vae_input_of(w0 & 255u), vae_input_of(w0 >> 24), vae_input_of((w1 >> 16) & 255u),
+           vae_input_of((w2 >> 8) & 255u));
+  st4<Tag>(out, HW + p, vae_input_of((w0 >> 8) & 255u), vae_input_of(w1 & 255u), vae_input_of(w1 >> 24),
+           vae_input_of((w2 >> 16) & 255u));
+  st4<Tag>(out, 2 * HW + p, vae_input_of((w0 >> 16) & 255u), vae_input_of((w1 >> 8) & 255u), vae_input_of(w2 & 255u),
+           vae_input_of(w2 >> 24));
+}
+
+template <typename Tag>
+__global__ void __launch_bounds__(ED_BLOCK)
+k_u8_to_vae_input(const uint8_t* __restrict__ img, void* __restrict__ out, int64_t HW) {
+  int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
+  if (t >= 3 * HW) return;
+  int64_t c = t / HW, p = t - c * HW;
+  st<Tag>(out, t, vae_input_of(img[3 * p + c]));
+}
+
+// ed_img2img_init: z0 = (mean + std * eps) * sf, x = a * z0 + b * noise
+__device__ __forceinline__ void img2img_one(float m, float s, float e, float nz, float sf, float a, float b, float& z, float& x) {
+  z = __fmul_rn(__fadd_rn(m, __fmul_rn(s, e)), sf);
+  x = __fadd_rn(__fmul_rn(a, z), __fmul_rn(b, nz));
+}
+
+template <typename Tag>
+__global__ void __launch_bounds__(ED_BLOCK)
+k_img2img_init_v4(const void* __restrict__ mean, const void* __restrict__ stdv, const float4* __restrict__ eps,
+                  const float4* __restrict__ noise, float sf, float a, float b, float4* __restrict__ z0,
+                  float4* __restrict__ x, int64_t n4) {
+  int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
+  if (t >= n4) return;
+  float4 m = ld4<Tag>(mean, t << 2), s = ld4<Tag>(stdv, t << 2), e = eps[t], nz = noise[t], z, o;
+  img2img_one(m.x, s.x, e.x, nz.x, sf, a, b, z.x, o.x);
+  img2img_one(m.y, s.y, e.y, nz.y, sf, a, b, z.y, o.y);
+  img2img_one(m.z, s.z, e.z, nz.z, sf, a, b, z.z, o.z);
+  img2img_one(m.w, s.w, e.w, nz.w, sf, a, b, z.w, o.w);
+  z0[t] = z;
+  x[t] = o;
+}
+
+template <typename Tag>
+__global__ void __launch_bounds__(ED_BLOCK)
+k_img2img_init_s(const void* __restrict__ mean, const void* __restrict__ stdv, const float* __restrict__ eps,
+                 const float* __restrict__ noise, float sf, float a, float b, float* __restrict__ z0,
+                 float* __restrict__ x, int64_t n) {
+  int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
+  if (t >= n) return;
+  float z, o;
+  img2img_one(ld<Tag>(mean, t), ld<Tag>(stdv, t), eps[t], noise[t], sf, a, b, z, o);
+  z0[t] = z;
+  x[t] = o;
+}
+
+// ed_mask_to_latent: m[y, x] = src[scale * y, scale * x] >= threshold.  A strided byte gather into at most 64 KiB: every sample
+// sits in a sector of its own, so there is nothing to widen; one thread per output byte.
+__global__ void __launch_bounds__(ED_BLOCK)
+k_mask_to_latent(const uint8_t* __restrict__ src, int W, int scale, int threshold, uint8_t* __restrict__ m, int Hl, int Wl) {
+  int t = blockIdx.x * ED_BLOCK + threadIdx.x;
+  if (t >= Hl * Wl) return;
+  int y = t / Wl, x = t - y * Wl;
+  m[t] = (int)src[(int64_t)y * scale * W + (int64_t)x * scale] >= threshold ? 1 : 0;
+}
+
+// ed_inpaint_blend: out = m ? x : known, known = CLEAN ? z0 : a * z0 + b * noise; a select, so the kept side never sees x and the
+// repainted side never sees z0 / noise (NaN / inf on the side not taken do not leak).  out may be x (every thread reads its own
+// elements before it writes them): x and out are not __restrict__.
+template <bool CLEAN>
+__device__ __forceinline__ float blend_one(uint32_t m, float xv, float z, float nz, float a, float b) {
+  if (m) return xv;
+  return CLEAN ? z : __fadd_rn(__fmul_rn(a, z), __fmul_rn(b, nz));
+}
+
+template <bool CLEAN>
+__global__ void __launch_bounds__(ED_BLOCK)
+k_inpaint_blend_v4(const float4* x, const uint32_t* __restrict__ mask, const float4* __restrict__ z0,
+                   const float4* __restrict__ noise, float a, float b, float4* out, int64_t n4, int64_t HW4) {
+  int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
+  if (t >= n4) return;
+  uint32_t m = mask[t % HW4];
+  float4 xv = x[t], z = z0[t], nz = CLEAN ? z : noise[t], o;
+  o.x = blend_one<CLEAN>(m & 255u, xv.x, z.x, nz.x, a, b);
+  o.y = blend_one<CLEAN>((m >> 8) & 255u, xv.y, z.y, nz.y, a, b);
+  o.z = blend_one<CLEAN>((m >> 16) & 255u, xv.z, z.z, nz.z, a, b);
+  o.w = blend_one<CLEAN>(m >> 24, xv.w, z.w, nz.w, a, b);
+  out[t] = o;
+}
+
+template <bool CLEAN>
+__global__ void __launch_bounds__(ED_BLOCK)
+k_inpaint_blend_s(const float* x, const uint8_t* __restrict__ mask, const float* __restrict__ z0,
+                  const float* __restrict__ noise, float a, float b, float* out, int64_t n, int64_t HW) {
+  int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
+  if (t >= n) return;
+  float z = z0[t];
+  out[t] = blend_one<CLEAN>(mask[t % HW], x[t], z, CLEAN ? z : noise[t], a, b);
+}
+
 }  // namespace
 
 // ====================================================================================================
@@ -1377,6 +1491,61 @@ int ed_phase_epilogue_gr(const void* g_out, const void* v_out, int dtype, const 
                                uncond_last, direction, local, K, B, C, H, W, h, w, gPH, gPW, g_off_y, g_off_x, vPH, vPW,
                                n_col_blocks, g, sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev, sqrt_1m_alpha_prev, rrg_norm,
                                rrg_weight, stream, ratio, ratio_low, gr, omgr);
+}
+
+// ---- img2img / inpainting -----------------------------------------------------------------------------
+int ed_u8_to_vae_input(const uint8_t* img, int H, int W, void* out, int dtype, void* stream) {
+  if (!img || !out || H < 0 || W < 0) return (int)hipErrorInvalidValue;
+  int64_t HW = (int64_t)H * W;
+  if (HW == 0) return 0;
+  if ((HW & 3) == 0 && (((uintptr_t)img) & 3u) == 0 && aligned16(out)) {
+    ED_LAUNCH_T(dtype, k_u8_to_vae_input_x4, HW >> 2, (const uint32_t*)img, out, HW);
+  } else {
+    ED_LAUNCH_T(dtype, k_u8_to_vae_input, 3 * HW, img, out, HW);
+  }
+  return done();
+}
+
+int ed_img2img_init(const void* mean, const void* std, int dtype, const float* eps, const float* noise, float sf, float a,
+                    float b, float* z0, float* x, int64_t n, void* stream) {
+  if (!mean || !std || !eps || !noise || !z0 || !x || n < 0) return (int)hipErrorInvalidValue;
+  if (n == 0) return 0;
+  if ((n & 3) == 0 && aligned16(mean) && aligned16(std) && aligned16(eps) && aligned16(noise) && aligned16(z0) && aligned16(x)) {
+    ED_LAUNCH_T(dtype, k_img2img_init_v4, n / 4, mean, std, (const float4*)eps, (const float4*)noise, sf, a, b, (float4*)z0,
+                (float4*)x, n / 4);
+  } else {
+    ED_LAUNCH_T(dtype, k_img2img_init_s, n, mean, std, eps, noise, sf, a, b, z0, x, n);
+  }
+  return done();
+}
+
+int ed_mask_to_latent(const uint8_t* src, int H, int W, int scale, int threshold, uint8_t* mask, int Hl, int Wl, void* stream) {
+  if (!src || !mask || scale < 1 || Hl < 0 || Wl < 0 || (int64_t)Hl * scale != H || (int64_t)Wl * scale != W ||
+      (int64_t)Hl * Wl > INT32_MAX)
+    return (int)hipErrorInvalidValue;
+  if (Hl == 0 || Wl == 0) return 0;
+  ED_LAUNCH(k_mask_to_latent, (int64_t)Hl * Wl, src, W, scale, threshold, mask, Hl, Wl);
+  return done();
+}
+
+int ed_inpaint_blend(const float* x, const uint8_t* mask, const float* z0, const float* noise, float a, float b, int clean,
+                     float* out, int planes, int64_t HW, void* stream) {
+  if (!x || !mask || !z0 || !out || (!clean && !noise) || planes < 0 || HW < 0) return (int)hipErrorInvalidValue;
+  int64_t n = (int64_t)planes * HW;
+  if (n == 0) return 0;
+  if ((HW & 3) == 0 && aligned16(x) && aligned16(z0) && (clean || aligned16(noise)) && aligned16(out) &&
+      (((uintptr_t)mask) & 3u) == 0) {
+    if (clean)
+      ED_LAUNCH(k_inpaint_blend_v4<true>, n / 4, (const float4*)x, (const uint32_t*)mask, (const float4*)z0,
+                (const float4*)noise, a, b, (float4*)out, n / 4, HW / 4);
+    else
+      ED_LAUNCH(k_inpaint_blend_v4<false>, n / 4, (const float4*)x, (const uint32_t*)mask, (const float4*)z0,
+                (const float4*)noise, a, b, (float4*)out, n / 4, HW / 4);
+  } else {
+    if (clean) ED_LAUNCH(k_inpaint_blend_s<true>, n, x, mask, z0, noise, a, b, out, n, HW);
+    else ED_LAUNCH(k_inpaint_blend_s<false>, n, x, mask, z0, noise, a, b, out, n, HW);
+  }
+  return done();
 }
 
 }  // extern "C"

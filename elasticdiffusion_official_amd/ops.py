@@ -1345,3 +1345,102 @@ def resize_u8(img, size, filter="bicubic", out="u8"):
     _call("ed_resize_cols_u8", src, rows, Wo * C, pitch, _dev(coeff, torch.int32, "coeff"), _dev(bounds, torch.int32, "bounds"),
           ksz, Ho, C, p_u8, p_cond, _stream())
     return res
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Image-to-image and masked inpainting: once per image before the loop, the blend once per phase
+# ---------------------------------------------------------------------------------------------------------------------
+VAE_INPUT_MAX_DIM = 8192
+
+
+def u8_to_vae_input(img, dtype=torch.float32):
+    """img uint8 [H,W,3] (RGB, contiguous) -> [1,3,H,W] of ``dtype`` = 2 * (v / 255) - 1: what ``VaeImageProcessor.preprocess``
+    hands the VAE encoder, bit-identical to ``np.float32(v) / 255`` then ``2 * x - 1`` on the CPU.  See ed_u8_to_vae_input."""
+    p_img = _dev(img, torch.uint8, "img")
+    if img.dim() != 3 or img.shape[2] != 3:
+        _reject(f"img must be uint8 [H,W,3], got {tuple(img.shape)}")
+    H, W = int(img.shape[0]), int(img.shape[1])
+    if not (1 <= H <= VAE_INPUT_MAX_DIM and 1 <= W <= VAE_INPUT_MAX_DIM):
+        _reject(f"img: H and W must be in 1..{VAE_INPUT_MAX_DIM}, got {H} x {W}")
+    if dtype not in _DTYPE:
+        _reject(f"u8_to_vae_input: unsupported dtype {dtype}")
+    out = torch.empty((1, 3, H, W), dtype=dtype, device=img.device)
+    _call("ed_u8_to_vae_input", p_img, H, W, _dev(out, dtype, "out"), _DTYPE[dtype], _stream())
+    TIMER.note_work("ed_u8_to_vae_input", nbytes=float(3 * H * W * (1 + out.element_size())))
+    return out
+
+
+def img2img_init(mean, std, eps, noise, sf, a, b, z0=None, x=None):
+    """z0 = (mean + std * eps) * sf and x = a * z0 + b * noise in one launch -> (z0, x), both f32 of mean's shape.
+    mean / std: the encoder's posterior moments, f32 / f16 / bf16 (one dtype for both); eps / noise f32.  See ed_img2img_init."""
+    if not isinstance(mean, torch.Tensor) or not isinstance(std, torch.Tensor):
+        _reject("img2img_init: mean / std must be tensors on the MI355X; no CPU fallback")
+    shape = tuple(mean.shape)
+    for name, t in (("std", std), ("eps", eps), ("noise", noise), ("z0", z0), ("x", x)):
+        if t is not None and tuple(getattr(t, "shape", ())) != shape:
+            _reject(f"img2img_init: {name} must have mean's shape {shape}, got {tuple(getattr(t, 'shape', ()))}")
+    if std.dtype != mean.dtype:
+        _reject(f"img2img_init: mean and std must share a dtype, got {mean.dtype} / {std.dtype}")
+    code = _code(mean, "mean")
+    p_mean, p_std = _dev(mean, None, "mean"), _dev(std, None, "std")
+    p_eps, p_noise = _dev(eps, torch.float32, "eps"), _dev(noise, torch.float32, "noise")
+    z0 = torch.empty(shape, dtype=torch.float32, device=mean.device) if z0 is None else z0
+    x = torch.empty(shape, dtype=torch.float32, device=mean.device) if x is None else x
+    n = mean.numel()
+    _call("ed_img2img_init", p_mean, p_std, code, p_eps, p_noise, float(sf), float(a), float(b),
+          _dev(z0, torch.float32, "z0"), _dev(x, torch.float32, "x"), n, _stream())
+    TIMER.note_work("ed_img2img_init", flops=5.0 * n, nbytes=float(n * (2 * mean.element_size() + 16)))
+    return z0, x
+
+
+def mask_to_latent(mask, scale=1, threshold=None):
+    """mask uint8 / bool [H,W] (or [H,W,1]) -> uint8 [H // scale, W // scale], 1 = repaint, 0 = keep:
+    ``out[y, x] = mask[scale * y, scale * x] >= threshold`` -- torch's nearest ``interpolate`` of the mask binarised at 0.5
+    (``threshold`` 128, the default for ``scale`` > 1).  ``scale == 1`` with the default threshold 1 normalises a mask that is
+    already at latent resolution (non-zero = repaint).  H and W must be multiples of ``scale``.  See ed_mask_to_latent."""
+    if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool):
+        _reject(f"mask must be a uint8 or bool tensor, got {getattr(mask, 'dtype', type(mask).__name__)}")
+    src = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    p_src = _dev(src, torch.uint8, "mask")
+    if src.dim() == 3 and src.shape[2] == 1:
+        src = src[:, :, 0]
+    if src.dim() != 2:
+        _reject(f"mask must be [H,W] or [H,W,1], got {tuple(mask.shape)}")
+    scale = int(scale)
+    H, W = int(src.shape[0]), int(src.shape[1])
+    if scale < 1 or H == 0 or W == 0 or H % scale or W % scale:
+        _reject(f"mask: {H} x {W} is not a non-empty multiple of scale {scale}")
+    threshold = (128 if scale > 1 else 1) if threshold is None else int(threshold)
+    if not 1 <= threshold <= 255:
+        _reject(f"mask: threshold must be in 1..255, got {threshold}")
+    Hl, Wl = H // scale, W // scale
+    out = torch.empty((Hl, Wl), dtype=torch.uint8, device=mask.device)
+    _call("ed_mask_to_latent", p_src, H, W, scale, threshold, _dev(out, torch.uint8, "out"), Hl, Wl, _stream())
+    TIMER.note_work("ed_mask_to_latent", nbytes=2.0 * Hl * Wl)  # algorithmic: one sampled byte in, one out
+    return out
+
+
+def inpaint_blend(x, mask, z0, noise, a, b, out=None, clean=False):
+    """out = where(mask, x, known) with known = a * z0 + b * noise, or z0 itself with ``clean`` (``noise`` may then be None).
+    x / z0 / noise f32 [B,C,H,W], mask uint8 [H,W] (1 = keep x) broadcast over B and C; ``out`` None = in place into ``x``.
+    See ed_inpaint_blend."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        _reject(f"inpaint_blend: x must be an f32 [B,C,H,W] tensor on the MI355X; no CPU fallback (got "
+                f"{tuple(getattr(x, 'shape', ()))})")
+    B, C, H, W = x.shape
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8:
+        _reject(f"inpaint_blend: mask must be uint8 (ops.mask_to_latent), got {getattr(mask, 'dtype', type(mask).__name__)}")
+    if tuple(mask.shape) != (H, W):
+        _reject(f"inpaint_blend: mask must be [{H}, {W}], got {tuple(mask.shape)}")
+    if noise is None and not clean:
+        _reject("inpaint_blend: noise is required unless clean")
+    out = x if out is None else out
+    for name, t in (("z0", z0), ("noise", noise), ("out", out)):
+        if t is not None and tuple(getattr(t, "shape", ())) != tuple(x.shape):
+            _reject(f"inpaint_blend: {name} must have x's shape {tuple(x.shape)}, got {tuple(getattr(t, 'shape', ()))}")
+    _call("ed_inpaint_blend", _dev(x, torch.float32, "x"), _dev(mask, torch.uint8, "mask"), _dev(z0, torch.float32, "z0"),
+          _opt(noise, torch.float32, "noise"), float(a), float(b), int(bool(clean)), _dev(out, torch.float32, "out"),
+          B * C, H * W, _stream())
+    n = x.numel()
+    TIMER.note_work("ed_inpaint_blend", flops=0.0 if clean else 3.0 * n, nbytes=float(n * (12 if clean else 16) + n))
+    return out

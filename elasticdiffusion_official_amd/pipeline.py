@@ -85,6 +85,19 @@ def _on_own_device(fn):
     return wrapper
 
 
+def check_img2img_arguments(num_inference_steps, init_image=None, strength=1.0, mask_image=None):
+    """The argument rules of ``init_image`` / ``strength`` / ``mask_image``, pure host code that runs
+    before anything is launched -> ``t_start``, the index of the first timestep the loop executes (0 = the whole schedule).
+    ValueError: ``strength`` outside (0, 1] or leaving no step, ``strength != 1`` or a mask without an init image."""
+    t_start = DDIMSchedule.img2img_window(num_inference_steps, strength)
+    if init_image is None:
+        if float(strength) != 1.0:
+            raise ValueError(f"strength={strength!r} needs init_image (without one every image starts from pure noise)")
+        if mask_image is not None:
+            raise ValueError("mask_image needs init_image (the picture whose kept region it marks)")
+    return t_start
+
+
 class _Plan:
     """Per-call geometry: host plans (geometry.py) + their int32 device tables + the pick sampler."""
 
@@ -250,6 +263,7 @@ class ElasticDiffusion(nn.Module):
         self.default_size = None
         self._stager = _Stager()
         self.last_latents = None
+        self.last_init_latents = None  # z0 of the last image started with ``init_image`` (its encoded, scaled latent)
 
     @staticmethod
     def _model_layout(module):
@@ -638,13 +652,113 @@ class ElasticDiffusion(nn.Module):
             out[K] = torch.cat([g_part, v_part]).contiguous() if P.one_batch else (g_part.contiguous(), v_part.contiguous())
         return out
 
+    # ---- image-to-image / inpainting inputs ------------------------------------
+    def _u8_image(self, image, channels, what):
+        """A PIL image or a uint8 array / tensor [H,W,channels] ([H,W] too for one channel) -> contiguous uint8 numpy array or
+        tensor of exactly that rank-3 shape, else None (not an 8-bit picture)."""
+        if hasattr(image, "convert"):
+            mode = "RGB" if channels == 3 else "L"
+            image = np.array(image if image.mode == mode else image.convert(mode))
+        if not isinstance(image, (np.ndarray, torch.Tensor)) or image.dtype not in (np.uint8, torch.uint8):
+            return None
+        if image.ndim == 2 and channels == 1:
+            image = image[:, :, None]
+        if image.ndim != 3 or image.shape[2] != channels:
+            raise ValueError(f"{what}: an 8-bit picture must be [H,W,{channels}], got {tuple(image.shape)}")
+        return image
+
+    def _init_pixels(self, image, height, width):
+        """``init_image`` -> (the VAE encoder's input (1|B,3,height,width) in [-1, 1] in the VAE's dtype, the (H, W) of an 8-bit
+        source that was resized or None).  An 8-bit picture of another size is resized with Pillow's Lanczos filter on the
+        device (``ops.resize_u8``: ``VaeImageProcessor``'s default, Pillow's bytes) and converted by ``ops.u8_to_vae_input``."""
+        vdt = next(self.vae.parameters()).dtype
+        u8 = self._u8_image(image, 3, "init_image")
+        if u8 is None:
+            if not isinstance(image, torch.Tensor) or not image.is_floating_point():
+                raise ValueError("init_image must be an RGB PIL image, a uint8 [H,W,3] array / tensor or a float tensor "
+                                 f"(1|B,3,height,width) in [0,1], got {type(image).__name__}")
+            t = image[None] if image.dim() == 3 else image
+            if t.dim() != 4 or tuple(t.shape[1:]) != (3, height, width):
+                raise ValueError(f"a float init_image must already be (1|B,3,{height},{width}), got {tuple(image.shape)}")
+            return (2.0 * t.to(self.device, torch.float32) - 1.0).to(vdt).contiguous(), None
+        if isinstance(u8, np.ndarray):
+            u8 = torch.from_numpy(np.ascontiguousarray(u8))
+        u8 = u8.to(self.device).contiguous()
+        src = tuple(u8.shape[:2])
+        if src != (height, width):
+            if not all(1 <= n <= ops.RESIZE_MAX_DIM for n in src + (height, width)):
+                raise ValueError(f"init_image: cannot resize {src} to {(height, width)} (sides up to {ops.RESIZE_MAX_DIM})")
+            u8 = ops.resize_u8(u8, (height, width), "lanczos")
+        return ops.u8_to_vae_input(u8, vdt), (src if src != (height, width) else None)
+
+    def _latent_mask(self, mask, height, width, resized_from=None):
+        """``mask_image`` -> uint8 (Hl, Wl) on the device, 1 = repaint, 0 = keep.  A bool / uint8 tensor that is already
+        (Hl, Wl) is taken as the latent mask (non-zero = repaint); an 8-bit picture (L PIL image, uint8 [H,W] / [H,W,1]) of
+        height x width is sampled at the top-left pixel of every latent cell and compared with 128 (torch's nearest
+        ``interpolate`` of the mask binarised at 0.5).  A picture that has the size ``resized_from`` of an init image that
+        was resized is first resized on the HOST with PIL's NEAREST filter -- a rare path, one pass over the mask's bytes."""
+        s = self.vae_scale_factor
+        Hl, Wl = height // s, width // s
+        if isinstance(mask, torch.Tensor) and mask.dtype in (torch.bool, torch.uint8) and tuple(mask.shape) == (Hl, Wl):
+            return ops.mask_to_latent(mask.to(self.device).contiguous(), 1)
+        u8 = self._u8_image(mask, 1, "mask_image")
+        if u8 is None:
+            raise ValueError("mask_image must be an L PIL image, a uint8 [H,W] / [H,W,1] array / tensor of the image's size, or a "
+                             f"bool / uint8 tensor ({Hl},{Wl}); got {type(mask).__name__} {getattr(mask, 'dtype', '')}")
+        size = tuple(u8.shape[:2])
+        if size != (height, width):
+            if resized_from is None or size != tuple(resized_from):
+                raise ValueError(f"mask_image is {size}; it must be {(height, width)}"
+                                 + ("" if resized_from is None else f" or the init image's {tuple(resized_from)}"))
+            from PIL import Image
+            host = u8.cpu().numpy() if isinstance(u8, torch.Tensor) else u8
+            u8 = np.array(Image.fromarray(np.ascontiguousarray(host[:, :, 0])).resize((width, height), resample=Image.NEAREST))
+        if isinstance(u8, np.ndarray):
+            u8 = torch.from_numpy(np.ascontiguousarray(u8))
+        return ops.mask_to_latent(u8.to(self.device).contiguous(), s)
+
+    def _img2img_start(self, S, B, init_image, mask_image):
+        """The initial latent of an image-to-image run: encode, sample the posterior, noise to the first executed timestep.
+        Host RNG order: posterior noise, then the initial noise, both (B,C,Hl,Wl) fp32.  -> (x, z0, noise, latent mask | None)"""
+        P = S.P
+        s = self.vae_scale_factor
+        pix, resized_from = self._init_pixels(init_image, P.Hl * s, P.Wl * s)
+        if pix.shape[0] not in (1, B):
+            raise ValueError(f"init_image holds {pix.shape[0]} images for {B} prompts (1 or {B})")
+        mask = None if mask_image is None else self._latent_mask(mask_image, P.Hl * s, P.Wl * s, resized_from)
+        dist = self.vae.encode(pix).latent_dist
+        shape = (B, S.C, P.Hl, P.Wl)
+        if tuple(dist.mean.shape[1:]) != shape[1:]:
+            raise ValueError(f"the VAE encodes the init image to {tuple(dist.mean.shape)}, the loop runs on {shape}")
+        mean, std = (t.expand(shape).contiguous() for t in (dist.mean, dist.std))
+        h0 = time.perf_counter()
+        eps_host = self._stager.host(shape, torch.float32)
+        eps_host.normal_()
+        x_host = self._stager.host(shape, torch.float32)
+        x_host.normal_()
+        self.host_s["noise"] += time.perf_counter() - h0
+        eps = self._stager.upload(eps_host, self.device)
+        noise = self._stager.upload(x_host, self.device)
+        a, b = self.scheduler.add_noise_coefficients(self._timesteps[S.t_start])
+        z0, x = ops.img2img_init(mean, std, eps, noise, self.vae.config.scaling_factor, a, b)
+        return x, z0, noise, mask
+
+    def _blend_known(self, S, x, mask, z0, noise, j):
+        """x <- where(mask, x, known(j)) in place: the kept region of the init image at the noise level of timestep index ``j``
+        (the SAME initial noise at every step), the clean z0 after the last one."""
+        if j >= S.T:
+            return ops.inpaint_blend(x, mask, z0, None, 1.0, 0.0, clean=True)
+        a, b = self.scheduler.add_noise_coefficients(self._timesteps[j])
+        return ops.inpaint_blend(x, mask, z0, noise, a, b)
+
     # ---- the loop (ED:953-1078) --------------------------------------------------------------------
     def _setup_run(self, height, width, num_inference_steps, guidance_scale, resampling_steps, new_p, rrg_stop_t,
                    rrg_init_weight, rrg_scherduler_cls, cosine_scale, repaint_sampling, controlnet_conditioning_scale,
-                   guidance_rescale=0.0):
+                   guidance_rescale=0.0, strength=1.0):
         """Everything of one ``generate_image`` call that does not depend on the prompt, the seed or the condition
         image: geometry tables, schedules, the noised pad-background frames.  Shared by all images in flight."""
         ops.rescale_coefficients(guidance_rescale)  # ValueError outside [0, 1], before anything is launched
+        t_start = DDIMSchedule.img2img_window(num_inference_steps, strength)  # ValueError likewise
         self._mark("start")
         self.host_s = {"picks": 0.0, "phase_total": 0.0, "noise": 0.0, "stager_wait": 0.0}
         self._stager.waited = 0.0
@@ -660,6 +774,7 @@ class ElasticDiffusion(nn.Module):
         dev = self.device
         ts = self.scheduler.set_timesteps(num_inference_steps)
         S.T = len(ts)
+        S.t_start = t_start  # first executed timestep index (image-to-image ``strength``); 0 = the whole schedule
         self._timesteps = list(ts)
         self._t_dev = ts.to(dev)
         self._step_coef = [self.scheduler.step_coefficients(t) for t in ts]
@@ -687,9 +802,11 @@ class ElasticDiffusion(nn.Module):
         return S
 
     def _program(self, S, prompts, negative_prompts, condition_image=None, trace=None, progress=_identity_progress,
-                 direct=True, frames=None):
+                 direct=True, frames=None, init_image=None, mask_image=None):
         """Generator: the denoising loop of ONE image (ED:981-1078), yielding ``_ModelCall``s; returns the final latent.
-        All host RNG draws happen inside, in the reference's order."""
+        All host RNG draws happen inside, in the reference's order.  ``init_image`` / ``mask_image``: image-to-image and
+        inpainting -- the loop starts at timestep index ``S.t_start`` from the noised encoding of the
+        image, and with a mask the kept region is put back at the next noise level after every step."""
         P = S.P
         if isinstance(prompts, str):
             prompts = [prompts]
@@ -699,9 +816,14 @@ class ElasticDiffusion(nn.Module):
         co, pco = self.get_text_embeds(prompts)
         B = len(prompts)
         # initial latent from the host generator (ED:998-1000)
-        x_host = self._stager.host((B, S.C, P.Hl, P.Wl), torch.float32)
-        x_host.normal_()
-        x = self._stager.upload(x_host, self.device)
+        z0 = noise0 = mask = None
+        if init_image is None:
+            x_host = self._stager.host((B, S.C, P.Hl, P.Wl), torch.float32)
+            x_host.normal_()
+            x = self._stager.upload(x_host, self.device)
+        else:
+            x, z0, noise0, mask = self._img2img_start(S, B, init_image, mask_image)
+        self.last_init_latents = z0
         emb = {K: self._embed_rows(K, P.views.V, un, co, pun, pco) for K in S.Ks}
         cond = None
         if condition_image is not None:
@@ -713,7 +835,7 @@ class ElasticDiffusion(nn.Module):
         rescale = None
         if S.guidance_rescale:
             rescale = _Rescale(S.guidance_rescale, B, S.C * P.Hl * P.Wl, S.C * P.h * P.w, self.device)
-        for i, t in enumerate(progress(self._timesteps)):
+        for i, t in enumerate(progress(self._timesteps[S.t_start:]), start=S.t_start):  # absolute index; t_start = 0 without strength
             w_i = S.rrg(i)
             rrg_w = w_i if w_i > 10 else None  # ED:1061-1062
             two_phase = S.repaint and i < S.T - 1
@@ -725,6 +847,8 @@ class ElasticDiffusion(nn.Module):
                 logs["init_low"] = info["init_low"].clone()
             cfg = S.guidance
             if two_phase:  # ED:1038-1056
+                if mask is not None:  # the re-noised latent carries the known region into the second phase
+                    self._blend_known(S, prev, mask, z0, noise0, i + 1)
                 x = self._undo(prev, i + 1)
                 cfg = S.guidance / 3
                 prev, x0, info = yield from self._phase_steps(P, x, i, 1, cfg, S.drop_p, emb, cond, direct, rrg_w, S.norm,
@@ -754,6 +878,8 @@ class ElasticDiffusion(nn.Module):
                 x = nxt
             else:
                 x = prev
+            if mask is not None:
+                self._blend_known(S, x, mask, z0, noise0, i + 1)
             if trace is not None:
                 trace.append(x.clone())
         return x
@@ -764,15 +890,26 @@ class ElasticDiffusion(nn.Module):
                          guidance_scale=10.0, resampling_steps=20, new_p=0.3, rrg_stop_t=0.2, rrg_init_weight=1000,
                          rrg_scherduler_cls=CosineScheduler, cosine_scale=3.0, repaint_sampling=True,
                          progress=_identity_progress, condition_image=None, controlnet_conditioning_scale=1.0,
-                         trace=None, guidance_rescale=0.0):
+                         trace=None, guidance_rescale=0.0, init_image=None, strength=1.0, mask_image=None):
         """``guidance_rescale`` in [0, 1] (diffusers' keyword; 0 = off): the std rescale of the guided model output of
         arXiv 2305.08891 section 3.4, what zero-terminal-SNR / v-prediction checkpoints are meant to be sampled with
-        (DESIGN.md section 17)."""
+        (DESIGN.md section 17).
+
+        ``init_image`` / ``strength`` / ``mask_image`` (diffusers' image-to-image and 4-channel
+        inpainting semantics): start from the VAE encoding of ``init_image`` -- an RGB PIL image or uint8 [H,W,3] array /
+        tensor (Lanczos-resized to height x width on the device when it has another size), or a float tensor
+        (1|B,3,height,width) in [0,1] -- noised to the first of the last ``int(steps * strength)`` timesteps, which are the ones
+        that run.  ``mask_image`` (L PIL image / uint8 [H,W] of the image's size, or a bool / uint8 tensor at latent
+        resolution; white = repaint, black = keep; a mask of the size of an init image that gets resized is resized on the host
+        with PIL's NEAREST, a rare path): after every step the kept region is replaced by the init latent at the next
+        noise level, so it ends as ``last_init_latents`` bit for bit.  Absent, the loop is what it always was."""
+        check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
         S = self._setup_run(height, width, num_inference_steps, guidance_scale, resampling_steps, new_p, rrg_stop_t,
                             rrg_init_weight, rrg_scherduler_cls, cosine_scale, repaint_sampling,
-                            controlnet_conditioning_scale, guidance_rescale)
+                            controlnet_conditioning_scale, guidance_rescale, strength)
         self._runner.new_image()
-        x = self._drive(self._program(S, prompts, negative_prompts, condition_image, trace, progress, direct=True))
+        x = self._drive(self._program(S, prompts, negative_prompts, condition_image, trace, progress, direct=True,
+                                      init_image=init_image, mask_image=mask_image))
         self.last_latents = x
         self.host_s["blocked_ahead_of_gpu"] = self._stager.waited
         self._mark("loop_done")
@@ -784,10 +921,12 @@ class ElasticDiffusion(nn.Module):
                                      guidance_scale=10.0, resampling_steps=20, new_p=0.3, rrg_stop_t=0.2,
                                      rrg_init_weight=1000, rrg_scherduler_cls=CosineScheduler, cosine_scale=3.0,
                                      repaint_sampling=True, controlnet_conditioning_scale=1.0, on_done=None,
-                                     guidance_rescale=0.0):
+                                     guidance_rescale=0.0, strength=1.0):
         """Several images of the SAME size / settings in flight at once (new; the reference has nothing like it).
 
-        ``jobs`` = list of dicts {prompts, negative_prompts="", seed, condition_image=None}.  Each job is one
+        ``jobs`` = list of dicts {prompts, negative_prompts="", seed, condition_image=None, init_image=None,
+        mask_image=None}; ``strength`` is a setting of the call like the other schedule parameters, and jobs with and without
+        an init image may mix (at ``strength`` 1: below it every job needs one).  Each job is one
         ``_program`` with its own host RNG stream (``_HostRng``: exactly the stream ``seed_everything(seed)`` +
         ``generate_latents`` would consume, so every image's latents are those of running it alone, up to the model's
         own batch-shape dependent rounding).  Per tick, the pending model calls of all live programs -- e.g. the 20-row
@@ -796,9 +935,11 @@ class ElasticDiffusion(nn.Module):
         per rank, where the UNet runs at a fraction of its batch-20 rate; m images in flight multiply the rows per
         forward by ~m while the exchange stays one all-gather per tick.  Returns the final latents in job order
         (``on_done(index, latent)`` is called as each finishes, e.g. to decode it)."""
+        for job in jobs:
+            check_img2img_arguments(num_inference_steps, job.get("init_image"), strength, job.get("mask_image"))
         S = self._setup_run(height, width, num_inference_steps, guidance_scale, resampling_steps, new_p, rrg_stop_t,
                             rrg_init_weight, rrg_scherduler_cls, cosine_scale, repaint_sampling,
-                            controlnet_conditioning_scale, guidance_rescale)
+                            controlnet_conditioning_scale, guidance_rescale, strength)
         self._runner.new_image()
         results = [None] * len(jobs)
         queue = list(range(len(jobs)))
@@ -822,7 +963,8 @@ class ElasticDiffusion(nn.Module):
                 frames = (self._strip_frames(S.P.gpad, self._timesteps, S.C), self._strip_frames(S.P.vpad, self._timesteps, S.C))
             started[0] += 1
             prog = self._program(S, job["prompts"], job.get("negative_prompts", ""), job.get("condition_image"),
-                                 direct=False, frames=frames)
+                                 direct=False, frames=frames, init_image=job.get("init_image"),
+                                 mask_image=job.get("mask_image"))
             with rng:
                 call = next(prog)
             live.append([j, prog, rng, call])
@@ -1003,14 +1145,16 @@ class ElasticDiffusion(nn.Module):
                        guidance_scale=10.0, resampling_steps=20, new_p=0.3, rrg_stop_t=0.2, rrg_init_weight=1000,
                        rrg_scherduler_cls=CosineScheduler, cosine_scale=3.0, repaint_sampling=True,
                        progress=_default_progress, tiled_decoder=False, grid=False, guidance_rescale=0.0, *,
-                       condition_image=None, controlnet_conditioning_scale=1.0, output_type="pil"):
+                       condition_image=None, controlnet_conditioning_scale=1.0, output_type="pil", init_image=None,
+                       strength=1.0, mask_image=None):
         """ED:953-965 signature (ControlNet keywords of EDC:1120-1134 are keyword-only here), then ``guidance_rescale``
-        (diffusers' keyword, see ``generate_latents``).
+        (diffusers' keyword) and, keyword-only, ``init_image`` / ``strength`` / ``mask_image`` (see ``generate_latents``).
         Returns ``(images, image_log)``; images are PIL by default, a float tensor with ``output_type='pt'``."""
         z = self.generate_latents(prompts, negative_prompts, height, width, num_inference_steps, guidance_scale,
                                   resampling_steps, new_p, rrg_stop_t, rrg_init_weight, rrg_scherduler_cls,
                                   cosine_scale, repaint_sampling, progress, condition_image,
-                                  controlnet_conditioning_scale, guidance_rescale=guidance_rescale)
+                                  controlnet_conditioning_scale, guidance_rescale=guidance_rescale, init_image=init_image,
+                                  strength=strength, mask_image=mask_image)
         dec = self.tiled_decode if tiled_decoder else self.decode_latents
         image_log = self._image_log(dec, guidance_scale, guidance_rescale) if self.verbose else {}  # ED:1092-1118 (before the final decode)
         imgs = torch.cat([dec(z[i:i + 1]) for i in range(len(z))])  # decode_bs = 1 (ED:1090, 1121)
@@ -1154,7 +1298,8 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
                        resampling_steps=20, new_p=0.3, rrg_stop_t=0.2, rrg_init_weight=1000,
                        rrg_scherduler_cls=CosineScheduler, cosine_scale=3.0, repaint_sampling=True,
                        progress=_default_progress, tiled_decoder=False, grid=False, guidance_rescale=0.0, *,
-                       output_type="pil"):
+                       output_type="pil", init_image=None, strength=1.0, mask_image=None):
+        check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
         if condition_image is None:
             raise ValueError("condition_image is required (EDC:1183-1193)")
         h, w = self.get_downsample_size(height, width)
@@ -1164,4 +1309,5 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
                                       resampling_steps, new_p, rrg_stop_t, rrg_init_weight, rrg_scherduler_cls,
                                       cosine_scale, repaint_sampling, progress, tiled_decoder, grid, guidance_rescale,
                                       condition_image=cond, controlnet_conditioning_scale=controlnet_conditioning_scale,
-                                      output_type=output_type)
+                                      output_type=output_type, init_image=init_image, strength=strength,
+                                      mask_image=mask_image)

@@ -97,6 +97,23 @@ class DDIMSchedule:
         self.timesteps = torch.from_numpy(ts)  # int64: str(t) == "tensor(981)"
         return self.timesteps
 
+    @staticmethod
+    def img2img_window(num_inference_steps, strength):
+        """diffusers' ``get_timesteps`` of the image-to-image pipelines: the index ``t_start`` of the first timestep an
+        image-to-image run of this ``strength`` executes -- n = min(int(T * strength), T) steps, t_start = max(T - n, 0).
+        ``strength`` outside (0, 1], or one that leaves no step (n < 1), raises ValueError."""
+        T = int(num_inference_steps)
+        try:
+            s = float(strength)
+        except (TypeError, ValueError):
+            raise ValueError(f"strength must be a number in (0, 1], got {strength!r}") from None
+        if not 0.0 < s <= 1.0:  # also refuses NaN
+            raise ValueError(f"strength must be in (0, 1], got {strength!r}")
+        n = min(int(T * s), T)
+        if n < 1:
+            raise ValueError(f"strength {strength!r} leaves no step of {T} to run (int({T} * strength) < 1)")
+        return max(T - n, 0)
+
     # ---- scalar tables ---------------------------------------------------------------------------
     def step_coefficients(self, t):
         """(sqrt(1-abar_t), sqrt(abar_t), sqrt(abar_prev), sqrt(1-abar_prev)) as python floats holding fp32 values."""

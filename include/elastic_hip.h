@@ -611,6 +611,32 @@ int ed_resize_rows_u8(const uint8_t* src, int H, int W, int C, int src_pitch, co
 int ed_resize_cols_u8(const uint8_t* src, int H, int WC_bytes, int src_pitch, const int32_t* coeff, const int32_t* bounds, int ksize,
                       int H_out, int C, uint8_t* dst_u8, float* dst_cond, void* stream);
 
+/*
+ * ---- image-to-image and masked inpainting (additions, no signature change, so still ABI v13).  The
+ * reference has neither; the semantics are those of diffusers' StableDiffusionImg2ImgPipeline and of the 4-channel-UNet branch
+ * of StableDiffusionInpaintPipeline.  Streaming kernels: 4 elements per thread with 16-byte accesses when the extents are
+ * multiples of 4 and the pointers aligned, one element per thread otherwise, the same bits either way.  fp32 arithmetic rounded
+ * per operation, in the torch-CPU order given.
+ *
+ * ed_u8_to_vae_input -- VaeImageProcessor.preprocess after the resize: img uint8 [H, W, 3] (interleaved RGB) ->
+ *   out [1, 3, H, W] (planar) of `dtype` = 2 * (float(v) / 255) - 1.
+ * ed_img2img_init -- latent_dist.sample() * scaling_factor, then scheduler.add_noise at the first executed timestep:
+ *   z0 = (mean + std * eps) * sf;  x = a * z0 + b * noise.   mean / std of `dtype` (ED_F32 / ED_F16 / ED_BF16, converted to fp32
+ *   exactly), eps / noise / z0 / x f32, n elements each.  std, not logvar: exp on the device is not torch-CPU's exp.
+ * ed_mask_to_latent -- torch's nearest interpolate of the binarised mask: mask[y, x] = src[scale * y, scale * x] >= threshold
+ *   (1 = repaint, 0 = keep), src uint8 [H, W] with H = Hl * scale and W = Wl * scale (anything else is hipErrorInvalidValue),
+ *   mask uint8 [Hl, Wl].  threshold = 128 for an 8-bit picture (v / 255 >= 0.5), 1 for a mask that is already 0 / non-zero.
+ * ed_inpaint_blend -- out = mask ? x : known over `planes` = B * C planes of HW elements (the mask broadcast over them), with
+ *   known = a * z0 + b * noise, or z0 itself when `clean` != 0 (after the last timestep; noise may then be NULL).  A select: the
+ *   side not taken is never combined arithmetically.  out may be x (in place).
+ */
+int ed_u8_to_vae_input(const uint8_t* img, int H, int W, void* out, int dtype, void* stream);
+int ed_img2img_init(const void* mean, const void* std, int dtype, const float* eps, const float* noise, float sf, float a,
+                    float b, float* z0, float* x, int64_t n, void* stream);
+int ed_mask_to_latent(const uint8_t* src, int H, int W, int scale, int threshold, uint8_t* mask, int Hl, int Wl, void* stream);
+int ed_inpaint_blend(const float* x, const uint8_t* mask, const float* z0, const float* noise, float a, float b, int clean,
+                     float* out, int planes, int64_t HW, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
