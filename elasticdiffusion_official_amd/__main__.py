@@ -15,13 +15,17 @@ extracted condition as ``condition.png``.  ``--prediction_type``, ``--timestep_s
 without ``--weights``); the reference takes these from the hub config only.  ``--guidance_rescale`` is diffusers' keyword of
 that name (0 = off), what such checkpoints are meant to be sampled with.  ``--init_image FILE`` with ``--strength`` (and
 ``--mask_image FILE``: white = repaint, black = keep) is image-to-image / inpainting with diffusers' semantics; the picture is
-resized to H x W with Pillow's Lanczos filter, a mask of the picture's size with NEAREST.
+resized to H x W with Pillow's Lanczos filter, a mask of the picture's size with NEAREST.  ``--mask_blur R`` feathers the mask with
+Pillow's ``GaussianBlur(R)`` on the device, ``--mask_mode graded`` reads the grey levels as release times, ``--composite`` pastes
+the result over the init picture through the mask, and ``--outpaint L,T,R,B`` grows ``--init_image`` by that many pixels per side
+(edge replicated) and repaints the new border; it takes the place of ``--mask_image``.
 """
 import argparse
 import os
 import time
 from datetime import datetime
 
+import numpy as np
 import torch
 
 
@@ -77,7 +81,24 @@ def build_parser():
     ap.add_argument("--strength", type=float, default=1.0, help="fraction of the schedule an --init_image run executes, in "
                     "(0, 1] (diffusers' strength); 1 = all of it")
     ap.add_argument("--mask_image", type=str, default=None, help="inpainting mask for --init_image: white = repaint, black = keep")
+    ap.add_argument("--mask_blur", type=float, default=0.0, help="feather the mask: Gaussian radius in pixels at H x W "
+                    "(PIL.ImageFilter.GaussianBlur); 0 = off")
+    ap.add_argument("--mask_mode", type=str, default="binary", choices=["binary", "graded"], help="binary: the (blurred) mask "
+                    "thresholded at 128; graded: its grey level is the fraction of the schedule a pixel is free for")
+    ap.add_argument("--composite", action="store_true", help="paste the result over the init picture through the (blurred) mask")
+    ap.add_argument("--outpaint", type=str, default=None, metavar="L,T,R,B", help="grow --init_image by this many pixels on the "
+                    "left, top, right and bottom (edge replicated) and repaint the new border; exclusive with --mask_image")
     return ap
+
+
+def _outpaint_borders(text):
+    try:
+        pads = tuple(int(v) for v in text.split(","))
+    except ValueError:
+        pads = ()
+    if len(pads) != 4 or min(pads) < 0 or max(pads) == 0:
+        raise SystemExit(f"--outpaint takes four integers >= 0, not all zero: L,T,R,B (got {text!r})")
+    return pads
 
 
 def main(argv=None):
@@ -85,10 +106,21 @@ def main(argv=None):
     if not 0.0 <= opt.guidance_rescale <= 1.0:
         raise SystemExit(f"--guidance_rescale must be in [0, 1], got {opt.guidance_rescale}")
     from .pipeline import check_img2img_arguments
+    pads = None
+    if opt.outpaint is not None:
+        if opt.mask_image or not opt.init_image:
+            raise SystemExit("--outpaint needs --init_image and takes the place of --mask_image")
+        pads = _outpaint_borders(opt.outpaint)
+    has_mask = opt.mask_image or pads
+    from .pipeline import check_soft_inpaint_arguments
     try:
-        check_img2img_arguments(opt.steps, opt.init_image, opt.strength, opt.mask_image)
+        check_img2img_arguments(opt.steps, opt.init_image, opt.strength, has_mask or None)
+        # the files are opened later: 8-bit pictures stand in for them, so that every rule is checked before a model is built
+        check_soft_inpaint_arguments(np.zeros((1, 1, 3), np.uint8) if opt.init_image else None,
+                                     np.zeros((1, 1), np.uint8) if has_mask else None, opt.mask_blur, opt.mask_mode,
+                                     opt.composite, grid=opt.make_grid)
     except ValueError as e:
-        raise SystemExit(f"--init_image / --strength / --mask_image: {e}")
+        raise SystemExit(f"--init_image / --strength / --mask_image / --mask_blur / --mask_mode / --composite: {e}")
 
     from . import ElasticDiffusion, ElasticDiffusionControlNet
     if not torch.cuda.is_available():
@@ -122,6 +154,9 @@ def main(argv=None):
         extra["init_image"], extra["strength"] = Image.open(opt.init_image).convert("RGB"), opt.strength
         if opt.mask_image:
             extra["mask_image"] = Image.open(opt.mask_image).convert("L")
+        if pads:
+            extra["init_image"], extra["mask_image"] = sd.outpaint_canvas(extra["init_image"], *pads)
+        extra.update(mask_blur=opt.mask_blur, mask_mode=opt.mask_mode, composite=opt.composite)
     sd.seed_everything(opt.seed)
     t0 = time.time()
     imgs, image_log = sd.generate_image(prompts=[opt.prompt] * opt.num_sampled, negative_prompts=opt.negative,

@@ -1444,3 +1444,153 @@ def inpaint_blend(x, mask, z0, noise, a, b, out=None, clean=False):
     n = x.numel()
     TIMER.note_work("ed_inpaint_blend", flops=0.0 if clean else 3.0 * n, nbytes=float(n * (12 if clean else 16) + n))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Soft-edged inpainting: the mask blur, the level map and the canvas once per image before the loop,
+# the graded blend once per phase, the composite once per image after the decode
+# ---------------------------------------------------------------------------------------------------------------------
+MASK_BLUR_MAX = 256.0
+
+
+def gaussian_box_parameters(radius):
+    """``PIL.ImageFilter.GaussianBlur(radius)`` -> (r, ww, fw): the box radius and the two 24-bit fixed-point weights of each of
+    its three box passes per direction, computed as Pillow computes them (the effective radius rounded to float32, the weight
+    of an inside pixel ``uint32(float32(2^24) / (2 * fr + 1))`` evaluated in float32).  Pure host arithmetic."""
+    import math
+    import numpy as np
+    try:
+        radius = float(radius)
+    except (TypeError, ValueError):
+        raise ValueError(f"the blur radius must be a number in [0, {MASK_BLUR_MAX:g}], got {radius!r}") from None
+    if not 0.0 <= radius <= MASK_BLUR_MAX:  # also refuses NaN
+        raise ValueError(f"the blur radius must be finite and in [0, {MASK_BLUR_MAX:g}], got {radius!r}")
+    sigma2 = radius * radius / 3
+    l = math.floor((math.sqrt(12.0 * sigma2 + 1.0) - 1.0) / 2.0)
+    a = (2 * l + 1) * (l * (l + 1) - 3 * sigma2) / (6 * (sigma2 - (l + 1) * (l + 1)))
+    fr = np.float32(l + a)
+    r = int(fr)
+    ww = int(np.uint32(np.float32(1 << 24) / (np.float32(2) * fr + np.float32(1))))
+    return r, ww, ((1 << 24) - (2 * r + 1) * ww) // 2
+
+
+def _u8_plane(t, name):
+    """uint8 [H,W] / [H,W,1] on the device -> (pointer, H, W), sides within RESIZE_MAX_DIM"""
+    p = _dev(t, torch.uint8, name)
+    if not (t.dim() == 2 or (t.dim() == 3 and t.shape[2] == 1)):
+        _reject(f"{name} must be uint8 [H,W] or [H,W,1], got {tuple(t.shape)}")
+    H, W = int(t.shape[0]), int(t.shape[1])
+    if not (1 <= H <= RESIZE_MAX_DIM and 1 <= W <= RESIZE_MAX_DIM):
+        _reject(f"{name}: H and W must be in 1..{RESIZE_MAX_DIM}, got {H} x {W}")
+    return p, H, W
+
+
+def gaussian_blur_u8(img, radius):
+    """``Image.filter(ImageFilter.GaussianBlur(radius))`` of an 8-bit single-channel image, Pillow's bytes: img uint8 [H,W] or
+    [H,W,1] on the device -> a new tensor of the same shape.  Two launches (three box passes along the rows, three along the
+    columns, each staged in LDS).  See ed_box_blur3_rows_u8."""
+    p_img, H, W = _u8_plane(img, "img")
+    try:
+        r, ww, fw = gaussian_box_parameters(radius)
+    except ValueError as e:
+        _reject(f"gaussian_blur_u8: {e}")
+    tmp, out = torch.empty_like(img), torch.empty_like(img)
+    p_tmp, p_out = _dev(tmp, torch.uint8, "tmp"), _dev(out, torch.uint8, "out")
+    stream = _stream()
+    dev = _LAUNCH["device"]
+    _call("ed_box_blur3_rows_u8", p_img, H, W, r, ww, fw, p_tmp, stream)
+    TIMER.note_work("ed_box_blur3_rows_u8", nbytes=2.0 * H * W)
+    _LAUNCH["device"] = dev
+    _call("ed_box_blur3_cols_u8", p_tmp, H, W, r, ww, fw, p_out, stream)
+    TIMER.note_work("ed_box_blur3_cols_u8", nbytes=2.0 * H * W)
+    return out
+
+
+def mask_levels_to_latent(mask, scale=1):
+    """mask uint8 / bool [H,W] (or [H,W,1]) -> the level map uint8 [H // scale, W // scale]: ``out[y, x] = mask[scale * y,
+    scale * x]``, the byte itself (``scale`` 1: a copy of a map that is already at latent resolution).  A bool mask is taken as
+    0 / 255.  See ed_mask_levels_to_latent."""
+    if isinstance(mask, torch.Tensor) and mask.dtype == torch.bool:
+        mask = mask.to(torch.uint8) * 255
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8:
+        _reject(f"mask must be a uint8 or bool tensor, got {getattr(mask, 'dtype', type(mask).__name__)}")
+    p_src, H, W = _u8_plane(mask, "mask")
+    scale = int(scale)
+    if scale < 1 or H % scale or W % scale:
+        _reject(f"mask: {H} x {W} is not a non-empty multiple of scale {scale}")
+    Hl, Wl = H // scale, W // scale
+    out = torch.empty((Hl, Wl), dtype=torch.uint8, device=mask.device)
+    _call("ed_mask_levels_to_latent", p_src, H, W, scale, _dev(out, torch.uint8, "out"), Hl, Wl, _stream())
+    TIMER.note_work("ed_mask_levels_to_latent", nbytes=2.0 * Hl * Wl)  # algorithmic: one sampled byte in, one out
+    return out
+
+
+def inpaint_blend_level(x, level, thr, z0, noise, a, b, out=None, clean=False):
+    """``inpaint_blend`` with a level map: out = where(level > thr, x, known), known = a * z0 + b * noise, or z0 itself with
+    ``clean``.  level uint8 [H,W] (``mask_levels_to_latent``), thr an integer in 0..255; ``out`` None = in place into ``x``.
+    See ed_inpaint_blend_level."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        _reject(f"inpaint_blend_level: x must be an f32 [B,C,H,W] tensor on the MI355X; no CPU fallback (got "
+                f"{tuple(getattr(x, 'shape', ()))})")
+    B, C, H, W = x.shape
+    if not isinstance(level, torch.Tensor) or level.dtype != torch.uint8:
+        _reject(f"inpaint_blend_level: level must be uint8 (ops.mask_levels_to_latent), got "
+                f"{getattr(level, 'dtype', type(level).__name__)}")
+    if tuple(level.shape) != (H, W):
+        _reject(f"inpaint_blend_level: level must be [{H}, {W}], got {tuple(level.shape)}")
+    if isinstance(thr, bool) or not isinstance(thr, int) or not 0 <= thr <= 255:
+        _reject(f"inpaint_blend_level: thr must be an integer in 0..255, got {thr!r}")
+    if noise is None and not clean:
+        _reject("inpaint_blend_level: noise is required unless clean")
+    out = x if out is None else out
+    for name, t in (("z0", z0), ("noise", noise), ("out", out)):
+        if t is not None and tuple(getattr(t, "shape", ())) != tuple(x.shape):
+            _reject(f"inpaint_blend_level: {name} must have x's shape {tuple(x.shape)}, got {tuple(getattr(t, 'shape', ()))}")
+    _call("ed_inpaint_blend_level", _dev(x, torch.float32, "x"), _dev(level, torch.uint8, "level"), thr,
+          _dev(z0, torch.float32, "z0"), _opt(noise, torch.float32, "noise"), float(a), float(b), int(bool(clean)),
+          _dev(out, torch.float32, "out"), B * C, H * W, _stream())
+    n = x.numel()
+    TIMER.note_work("ed_inpaint_blend_level", flops=0.0 if clean else 3.0 * n, nbytes=float(n * (12 if clean else 16) + n))
+    return out
+
+
+def composite_u8(decoded, init, mask):
+    """``PIL.Image.composite`` of the decoded picture over the init picture through the pixel mask, fused with ``_to_pil``'s
+    float -> 8-bit conversion: decoded f32 [1,3,H,W] in [0,1], init uint8 [H,W,3], mask uint8 [H,W] (255 = the decoded
+    picture, 0 = the init picture) -> uint8 [H,W,3].  See ed_composite_u8."""
+    p_dec = _dev(decoded, torch.float32, "decoded")
+    if decoded.dim() != 4 or decoded.shape[0] != 1 or decoded.shape[1] != 3:
+        _reject(f"decoded must be f32 [1,3,H,W], got {tuple(decoded.shape)}")
+    H, W = int(decoded.shape[2]), int(decoded.shape[3])
+    if not (1 <= H <= RESIZE_MAX_DIM and 1 <= W <= RESIZE_MAX_DIM):
+        _reject(f"decoded: H and W must be in 1..{RESIZE_MAX_DIM}, got {H} x {W}")
+    p_init, p_mask = _dev(init, torch.uint8, "init"), _dev(mask, torch.uint8, "mask")
+    if tuple(init.shape) != (H, W, 3):
+        _reject(f"init must be uint8 [{H},{W},3], got {tuple(init.shape)}")
+    if tuple(mask.shape) not in ((H, W), (H, W, 1)):
+        _reject(f"mask must be uint8 [{H},{W}], got {tuple(mask.shape)}")
+    out = torch.empty((H, W, 3), dtype=torch.uint8, device=decoded.device)
+    _call("ed_composite_u8", p_dec, p_init, p_mask, _dev(out, torch.uint8, "out"), H, W, _stream())
+    TIMER.note_work("ed_composite_u8", nbytes=float(H * W * (12 + 3 + 1 + 3)))
+    return out
+
+
+def canvas_pad_u8(img, left, top, right, bottom):
+    """The outpainting canvas: img uint8 [H,W,3] -> (canvas uint8 [H',W',3] = ``np.pad(img, mode="edge")`` by the four borders,
+    mask uint8 [H',W']: 255 on the new border, 0 over the original).  One launch.  See ed_canvas_pad_u8."""
+    p_img = _dev(img, torch.uint8, "img")
+    if img.dim() != 3 or img.shape[2] != 3:
+        _reject(f"img must be uint8 [H,W,3], got {tuple(img.shape)}")
+    H, W = int(img.shape[0]), int(img.shape[1])
+    pads = (left, top, right, bottom)
+    if any(isinstance(p, bool) or not isinstance(p, int) or p < 0 for p in pads):
+        _reject(f"canvas_pad_u8: the borders must be integers >= 0, got {pads!r}")
+    Ho, Wo = H + top + bottom, W + left + right
+    if not (1 <= H and 1 <= W and Ho <= RESIZE_MAX_DIM and Wo <= RESIZE_MAX_DIM):
+        _reject(f"canvas_pad_u8: {H} x {W} padded to {Ho} x {Wo}: sides must be in 1..{RESIZE_MAX_DIM}")
+    canvas = torch.empty((Ho, Wo, 3), dtype=torch.uint8, device=img.device)
+    mask = torch.empty((Ho, Wo), dtype=torch.uint8, device=img.device)
+    _call("ed_canvas_pad_u8", p_img, H, W, left, top, right, bottom, _dev(canvas, torch.uint8, "canvas"),
+          _dev(mask, torch.uint8, "mask"), _stream())
+    TIMER.note_work("ed_canvas_pad_u8", nbytes=float(Ho * Wo * 7))
+    return canvas, mask

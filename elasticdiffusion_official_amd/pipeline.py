@@ -98,6 +98,55 @@ def check_img2img_arguments(num_inference_steps, init_image=None, strength=1.0, 
     return t_start
 
 
+MASK_MODES = ("binary", "graded")
+
+
+def _is_8bit_picture(image, channels):
+    """is ``image`` what ``_u8_image`` takes as an 8-bit picture: a PIL image or a uint8 array / tensor [H,W,channels]?"""
+    if hasattr(image, "convert"):
+        return True
+    if not isinstance(image, (np.ndarray, torch.Tensor)) or image.dtype not in (np.uint8, torch.uint8):
+        return False
+    return (image.ndim == 3 and image.shape[2] == channels) or (image.ndim == 2 and channels == 1)
+
+
+def check_soft_inpaint_arguments(init_image=None, mask_image=None, mask_blur=0.0, mask_mode="binary", composite=False,
+                                 output_type="pil", grid=False, latent_size=None):
+    """The argument rules of ``mask_blur`` / ``mask_mode`` / ``composite``, pure host code that runs
+    before anything is launched -> ``mask_blur`` as a float.  ValueError: a radius that is not finite, negative or above
+    ``ops.MASK_BLUR_MAX``; an unknown mode; any of the three without ``mask_image``; ``mask_blur`` or ``composite`` with a mask
+    that is a tensor at latent resolution (``latent_size`` = (Hl, Wl)) and not an 8-bit picture; ``composite`` without an
+    8-bit ``init_image``, with another ``output_type`` than "pil" or with ``grid``."""
+    try:
+        blur = float(mask_blur)
+    except (TypeError, ValueError):
+        raise ValueError(f"mask_blur must be a number in [0, {ops.MASK_BLUR_MAX:g}], got {mask_blur!r}") from None
+    if not 0.0 <= blur <= ops.MASK_BLUR_MAX:  # also refuses NaN
+        raise ValueError(f"mask_blur must be finite and in [0, {ops.MASK_BLUR_MAX:g}], got {mask_blur!r}")
+    if mask_mode not in MASK_MODES:
+        raise ValueError(f"mask_mode must be one of {MASK_MODES}, got {mask_mode!r}")
+    if mask_image is None:
+        for name, on in (("mask_blur", blur > 0), ("mask_mode", mask_mode != "binary"), ("composite", composite)):
+            if on:
+                raise ValueError(f"{name} needs mask_image")
+        return blur
+    at_latent_size = (isinstance(mask_image, torch.Tensor) and mask_image.dtype in (torch.bool, torch.uint8)
+                      and latent_size is not None and tuple(mask_image.shape) == tuple(latent_size))
+    picture = _is_8bit_picture(mask_image, 1) and not at_latent_size
+    if blur > 0 and not picture:
+        raise ValueError("mask_blur needs an 8-bit picture mask (L PIL image, uint8 [H,W]), not a tensor at latent resolution")
+    if composite:
+        if not picture:
+            raise ValueError("composite needs an 8-bit picture mask (L PIL image, uint8 [H,W]): it is the alpha of the paste")
+        if not _is_8bit_picture(init_image, 3):
+            raise ValueError("composite needs an 8-bit init_image (RGB PIL image, uint8 [H,W,3]), the picture that is pasted over")
+        if output_type != "pil":
+            raise ValueError(f"composite needs output_type='pil', got {output_type!r}")
+        if grid:
+            raise ValueError("composite needs grid=False: one composited image per prompt")
+    return blur
+
+
 class _Plan:
     """Per-call geometry: host plans (geometry.py) + their int32 device tables + the pick sampler."""
 
@@ -264,6 +313,8 @@ class ElasticDiffusion(nn.Module):
         self._stager = _Stager()
         self.last_latents = None
         self.last_init_latents = None  # z0 of the last image started with ``init_image`` (its encoded, scaled latent)
+        self.last_init_pixels = None   # uint8 [height,width,3]: the (resized) 8-bit init picture of the last such image, on the device
+        self.last_pixel_mask = None    # uint8 [height,width]: its (resized, blurred) 8-bit picture mask, on the device
 
     @staticmethod
     def _model_layout(module):
@@ -680,6 +731,7 @@ class ElasticDiffusion(nn.Module):
             t = image[None] if image.dim() == 3 else image
             if t.dim() != 4 or tuple(t.shape[1:]) != (3, height, width):
                 raise ValueError(f"a float init_image must already be (1|B,3,{height},{width}), got {tuple(image.shape)}")
+            self.last_init_pixels = None
             return (2.0 * t.to(self.device, torch.float32) - 1.0).to(vdt).contiguous(), None
         if isinstance(u8, np.ndarray):
             u8 = torch.from_numpy(np.ascontiguousarray(u8))
@@ -689,18 +741,26 @@ class ElasticDiffusion(nn.Module):
             if not all(1 <= n <= ops.RESIZE_MAX_DIM for n in src + (height, width)):
                 raise ValueError(f"init_image: cannot resize {src} to {(height, width)} (sides up to {ops.RESIZE_MAX_DIM})")
             u8 = ops.resize_u8(u8, (height, width), "lanczos")
+        self.last_init_pixels = u8
         return ops.u8_to_vae_input(u8, vdt), (src if src != (height, width) else None)
 
-    def _latent_mask(self, mask, height, width, resized_from=None):
-        """``mask_image`` -> uint8 (Hl, Wl) on the device, 1 = repaint, 0 = keep.  A bool / uint8 tensor that is already
+    def _latent_mask(self, mask, height, width, resized_from=None, mask_blur=0.0, graded=False):
+        """``mask_image`` -> uint8 (Hl, Wl) on the device, 1 = repaint, 0 = keep; with ``graded`` the level map instead, the
+        sampled byte itself (a uint8 tensor at latent resolution is the level map, a bool one 0 / 255).  The 8-bit picture mask
+        at height x width, blurred by ``ops.gaussian_blur_u8`` when ``mask_blur`` > 0 (Pillow's ``GaussianBlur`` bytes), is
+        what gets sampled, and stays on the device as ``last_pixel_mask``.  A bool / uint8 tensor that is already
         (Hl, Wl) is taken as the latent mask (non-zero = repaint); an 8-bit picture (L PIL image, uint8 [H,W] / [H,W,1]) of
         height x width is sampled at the top-left pixel of every latent cell and compared with 128 (torch's nearest
         ``interpolate`` of the mask binarised at 0.5).  A picture that has the size ``resized_from`` of an init image that
         was resized is first resized on the HOST with PIL's NEAREST filter -- a rare path, one pass over the mask's bytes."""
         s = self.vae_scale_factor
         Hl, Wl = height // s, width // s
+        self.last_pixel_mask = None
         if isinstance(mask, torch.Tensor) and mask.dtype in (torch.bool, torch.uint8) and tuple(mask.shape) == (Hl, Wl):
-            return ops.mask_to_latent(mask.to(self.device).contiguous(), 1)
+            if mask_blur > 0:
+                raise ValueError("mask_blur needs an 8-bit picture mask, not a tensor at latent resolution")
+            mask = mask.to(self.device).contiguous()
+            return ops.mask_levels_to_latent(mask, 1) if graded else ops.mask_to_latent(mask, 1)
         u8 = self._u8_image(mask, 1, "mask_image")
         if u8 is None:
             raise ValueError("mask_image must be an L PIL image, a uint8 [H,W] / [H,W,1] array / tensor of the image's size, or a "
@@ -715,9 +775,14 @@ class ElasticDiffusion(nn.Module):
             u8 = np.array(Image.fromarray(np.ascontiguousarray(host[:, :, 0])).resize((width, height), resample=Image.NEAREST))
         if isinstance(u8, np.ndarray):
             u8 = torch.from_numpy(np.ascontiguousarray(u8))
-        return ops.mask_to_latent(u8.to(self.device).contiguous(), s)
+        u8 = u8.to(self.device).contiguous()
+        u8 = u8.view(u8.shape[0], u8.shape[1])       # [H,W,1] from ``_u8_image``, [H,W] from the host resize
+        if mask_blur > 0:
+            u8 = ops.gaussian_blur_u8(u8, mask_blur)
+        self.last_pixel_mask = u8
+        return ops.mask_levels_to_latent(u8, s) if graded else ops.mask_to_latent(u8, s)
 
-    def _img2img_start(self, S, B, init_image, mask_image):
+    def _img2img_start(self, S, B, init_image, mask_image, mask_blur=0.0, graded=False):
         """The initial latent of an image-to-image run: encode, sample the posterior, noise to the first executed timestep.
         Host RNG order: posterior noise, then the initial noise, both (B,C,Hl,Wl) fp32.  -> (x, z0, noise, latent mask | None)"""
         P = S.P
@@ -725,7 +790,10 @@ class ElasticDiffusion(nn.Module):
         pix, resized_from = self._init_pixels(init_image, P.Hl * s, P.Wl * s)
         if pix.shape[0] not in (1, B):
             raise ValueError(f"init_image holds {pix.shape[0]} images for {B} prompts (1 or {B})")
-        mask = None if mask_image is None else self._latent_mask(mask_image, P.Hl * s, P.Wl * s, resized_from)
+        mask = None
+        self.last_pixel_mask = None
+        if mask_image is not None:
+            mask = self._latent_mask(mask_image, P.Hl * s, P.Wl * s, resized_from, mask_blur, graded)
         dist = self.vae.encode(pix).latent_dist
         shape = (B, S.C, P.Hl, P.Wl)
         if tuple(dist.mean.shape[1:]) != shape[1:]:
@@ -743,9 +811,17 @@ class ElasticDiffusion(nn.Module):
         z0, x = ops.img2img_init(mean, std, eps, noise, self.vae.config.scaling_factor, a, b)
         return x, z0, noise, mask
 
-    def _blend_known(self, S, x, mask, z0, noise, j):
+    def _blend_known(self, S, x, mask, z0, noise, j, graded=False):
         """x <- where(mask, x, known(j)) in place: the kept region of the init image at the noise level of timestep index ``j``
-        (the SAME initial noise at every step), the clean z0 after the last one."""
+        (the SAME initial noise at every step), the clean z0 after the last one.  ``graded``: ``mask`` is the level map and a
+        pixel is held iff its level <= thr(j) = (255 * (T - j)) // T (DESIGN.md section 19.3) -- level 0 at every j, level 255
+        never, one in between until the remaining fraction of the schedule drops to level / 255.  One launch either way."""
+        if graded:
+            thr = (255 * (S.T - j)) // S.T
+            if j >= S.T:
+                return ops.inpaint_blend_level(x, mask, thr, z0, None, 1.0, 0.0, clean=True)
+            a, b = self.scheduler.add_noise_coefficients(self._timesteps[j])
+            return ops.inpaint_blend_level(x, mask, thr, z0, noise, a, b)
         if j >= S.T:
             return ops.inpaint_blend(x, mask, z0, None, 1.0, 0.0, clean=True)
         a, b = self.scheduler.add_noise_coefficients(self._timesteps[j])
@@ -802,11 +878,12 @@ class ElasticDiffusion(nn.Module):
         return S
 
     def _program(self, S, prompts, negative_prompts, condition_image=None, trace=None, progress=_identity_progress,
-                 direct=True, frames=None, init_image=None, mask_image=None):
+                 direct=True, frames=None, init_image=None, mask_image=None, mask_blur=0.0, mask_mode="binary"):
         """Generator: the denoising loop of ONE image (ED:981-1078), yielding ``_ModelCall``s; returns the final latent.
         All host RNG draws happen inside, in the reference's order.  ``init_image`` / ``mask_image``: image-to-image and
         inpainting -- the loop starts at timestep index ``S.t_start`` from the noised encoding of the
-        image, and with a mask the kept region is put back at the next noise level after every step."""
+        image, and with a mask the kept region is put back at the next noise level after every step.  ``mask_blur`` /
+        ``mask_mode``: the mask feathered on the device and, in "graded" mode, read as a per-pixel release time (section 19)."""
         P = S.P
         if isinstance(prompts, str):
             prompts = [prompts]
@@ -817,12 +894,14 @@ class ElasticDiffusion(nn.Module):
         B = len(prompts)
         # initial latent from the host generator (ED:998-1000)
         z0 = noise0 = mask = None
+        graded = mask_mode == "graded"
         if init_image is None:
             x_host = self._stager.host((B, S.C, P.Hl, P.Wl), torch.float32)
             x_host.normal_()
             x = self._stager.upload(x_host, self.device)
+            self.last_init_pixels = self.last_pixel_mask = None
         else:
-            x, z0, noise0, mask = self._img2img_start(S, B, init_image, mask_image)
+            x, z0, noise0, mask = self._img2img_start(S, B, init_image, mask_image, mask_blur, graded)
         self.last_init_latents = z0
         emb = {K: self._embed_rows(K, P.views.V, un, co, pun, pco) for K in S.Ks}
         cond = None
@@ -848,7 +927,7 @@ class ElasticDiffusion(nn.Module):
             cfg = S.guidance
             if two_phase:  # ED:1038-1056
                 if mask is not None:  # the re-noised latent carries the known region into the second phase
-                    self._blend_known(S, prev, mask, z0, noise0, i + 1)
+                    self._blend_known(S, prev, mask, z0, noise0, i + 1, graded)
                 x = self._undo(prev, i + 1)
                 cfg = S.guidance / 3
                 prev, x0, info = yield from self._phase_steps(P, x, i, 1, cfg, S.drop_p, emb, cond, direct, rrg_w, S.norm,
@@ -879,7 +958,7 @@ class ElasticDiffusion(nn.Module):
             else:
                 x = prev
             if mask is not None:
-                self._blend_known(S, x, mask, z0, noise0, i + 1)
+                self._blend_known(S, x, mask, z0, noise0, i + 1, graded)
             if trace is not None:
                 trace.append(x.clone())
         return x
@@ -890,7 +969,8 @@ class ElasticDiffusion(nn.Module):
                          guidance_scale=10.0, resampling_steps=20, new_p=0.3, rrg_stop_t=0.2, rrg_init_weight=1000,
                          rrg_scherduler_cls=CosineScheduler, cosine_scale=3.0, repaint_sampling=True,
                          progress=_identity_progress, condition_image=None, controlnet_conditioning_scale=1.0,
-                         trace=None, guidance_rescale=0.0, init_image=None, strength=1.0, mask_image=None):
+                         trace=None, guidance_rescale=0.0, init_image=None, strength=1.0, mask_image=None, *, mask_blur=0.0,
+                         mask_mode="binary"):
         """``guidance_rescale`` in [0, 1] (diffusers' keyword; 0 = off): the std rescale of the guided model output of
         arXiv 2305.08891 section 3.4, what zero-terminal-SNR / v-prediction checkpoints are meant to be sampled with
         (DESIGN.md section 17).
@@ -902,14 +982,24 @@ class ElasticDiffusion(nn.Module):
         that run.  ``mask_image`` (L PIL image / uint8 [H,W] of the image's size, or a bool / uint8 tensor at latent
         resolution; white = repaint, black = keep; a mask of the size of an init image that gets resized is resized on the host
         with PIL's NEAREST, a rare path): after every step the kept region is replaced by the init latent at the next
-        noise level, so it ends as ``last_init_latents`` bit for bit.  Absent, the loop is what it always was."""
+        noise level, so it ends as ``last_init_latents`` bit for bit.  Absent, the loop is what it always was.
+
+        ``mask_blur`` / ``mask_mode`` (keyword-only): ``mask_blur`` > 0 feathers an 8-bit picture mask at
+        the run's size with ``PIL.ImageFilter.GaussianBlur(mask_blur)``'s bytes, on the device.  ``mask_mode="binary"`` then
+        thresholds the (blurred) bytes at 128 as before; ``"graded"`` reads the byte L sampled for a latent pixel as a release
+        time: the pixel is held to the init image while L <= (255 * (T - j)) // T at target timestep index j, so black is kept
+        bit for bit, white is never held, and a grey one is free from the original at the noise level where the remaining
+        fraction of the schedule drops to L / 255.  No new RNG draws, one blend launch per phase in either mode.  The pixel
+        mask and the 8-bit init picture stay on the device as ``last_pixel_mask`` / ``last_init_pixels``."""
         check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
+        mask_blur = check_soft_inpaint_arguments(init_image, mask_image, mask_blur, mask_mode,
+                                                 latent_size=(height // self.vae_scale_factor, width // self.vae_scale_factor))
         S = self._setup_run(height, width, num_inference_steps, guidance_scale, resampling_steps, new_p, rrg_stop_t,
                             rrg_init_weight, rrg_scherduler_cls, cosine_scale, repaint_sampling,
                             controlnet_conditioning_scale, guidance_rescale, strength)
         self._runner.new_image()
         x = self._drive(self._program(S, prompts, negative_prompts, condition_image, trace, progress, direct=True,
-                                      init_image=init_image, mask_image=mask_image))
+                                      init_image=init_image, mask_image=mask_image, mask_blur=mask_blur, mask_mode=mask_mode))
         self.last_latents = x
         self.host_s["blocked_ahead_of_gpu"] = self._stager.waited
         self._mark("loop_done")
@@ -925,7 +1015,7 @@ class ElasticDiffusion(nn.Module):
         """Several images of the SAME size / settings in flight at once (new; the reference has nothing like it).
 
         ``jobs`` = list of dicts {prompts, negative_prompts="", seed, condition_image=None, init_image=None,
-        mask_image=None}; ``strength`` is a setting of the call like the other schedule parameters, and jobs with and without
+        mask_image=None, mask_blur=0.0, mask_mode="binary"}; ``strength`` is a setting of the call like the other schedule parameters, and jobs with and without
         an init image may mix (at ``strength`` 1: below it every job needs one).  Each job is one
         ``_program`` with its own host RNG stream (``_HostRng``: exactly the stream ``seed_everything(seed)`` +
         ``generate_latents`` would consume, so every image's latents are those of running it alone, up to the model's
@@ -937,6 +1027,11 @@ class ElasticDiffusion(nn.Module):
         (``on_done(index, latent)`` is called as each finishes, e.g. to decode it)."""
         for job in jobs:
             check_img2img_arguments(num_inference_steps, job.get("init_image"), strength, job.get("mask_image"))
+            if job.get("composite"):
+                raise ValueError("composite is a keyword of generate_image: a job of generate_latents_interleaved returns latents")
+            check_soft_inpaint_arguments(job.get("init_image"), job.get("mask_image"), job.get("mask_blur", 0.0),
+                                         job.get("mask_mode", "binary"),
+                                         latent_size=(height // self.vae_scale_factor, width // self.vae_scale_factor))
         S = self._setup_run(height, width, num_inference_steps, guidance_scale, resampling_steps, new_p, rrg_stop_t,
                             rrg_init_weight, rrg_scherduler_cls, cosine_scale, repaint_sampling,
                             controlnet_conditioning_scale, guidance_rescale, strength)
@@ -964,7 +1059,8 @@ class ElasticDiffusion(nn.Module):
             started[0] += 1
             prog = self._program(S, job["prompts"], job.get("negative_prompts", ""), job.get("condition_image"),
                                  direct=False, frames=frames, init_image=job.get("init_image"),
-                                 mask_image=job.get("mask_image"))
+                                 mask_image=job.get("mask_image"), mask_blur=float(job.get("mask_blur", 0.0)),
+                                 mask_mode=job.get("mask_mode", "binary"))
             with rng:
                 call = next(prog)
             live.append([j, prog, rng, call])
@@ -1146,15 +1242,21 @@ class ElasticDiffusion(nn.Module):
                        rrg_scherduler_cls=CosineScheduler, cosine_scale=3.0, repaint_sampling=True,
                        progress=_default_progress, tiled_decoder=False, grid=False, guidance_rescale=0.0, *,
                        condition_image=None, controlnet_conditioning_scale=1.0, output_type="pil", init_image=None,
-                       strength=1.0, mask_image=None):
+                       strength=1.0, mask_image=None, mask_blur=0.0, mask_mode="binary", composite=False):
         """ED:953-965 signature (ControlNet keywords of EDC:1120-1134 are keyword-only here), then ``guidance_rescale``
-        (diffusers' keyword) and, keyword-only, ``init_image`` / ``strength`` / ``mask_image`` (see ``generate_latents``).
+        (diffusers' keyword) and, keyword-only, ``init_image`` / ``strength`` / ``mask_image`` / ``mask_blur`` / ``mask_mode``
+        (see ``generate_latents``) and ``composite``: paste every decoded picture over the 8-bit init picture through the
+        (blurred) pixel mask, ``PIL.Image.composite``'s bytes, in the launch that converts the floats to 8 bit
+        (``ops.composite_u8``) -- where the mask is 0 the result IS the init picture.
         Returns ``(images, image_log)``; images are PIL by default, a float tensor with ``output_type='pt'``."""
+        check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
+        check_soft_inpaint_arguments(init_image, mask_image, mask_blur, mask_mode, composite, output_type, grid,
+                                     latent_size=(height // self.vae_scale_factor, width // self.vae_scale_factor))
         z = self.generate_latents(prompts, negative_prompts, height, width, num_inference_steps, guidance_scale,
                                   resampling_steps, new_p, rrg_stop_t, rrg_init_weight, rrg_scherduler_cls,
                                   cosine_scale, repaint_sampling, progress, condition_image,
                                   controlnet_conditioning_scale, guidance_rescale=guidance_rescale, init_image=init_image,
-                                  strength=strength, mask_image=mask_image)
+                                  strength=strength, mask_image=mask_image, mask_blur=mask_blur, mask_mode=mask_mode)
         dec = self.tiled_decode if tiled_decoder else self.decode_latents
         image_log = self._image_log(dec, guidance_scale, guidance_rescale) if self.verbose else {}  # ED:1092-1118 (before the final decode)
         imgs = torch.cat([dec(z[i:i + 1]) for i in range(len(z))])  # decode_bs = 1 (ED:1090, 1121)
@@ -1163,7 +1265,38 @@ class ElasticDiffusion(nn.Module):
             imgs = _make_grid(imgs)[None]  # ED:1124: torchvision make_grid(imgs, nrow=8, padding=2, pad_value=0)
         if output_type == "pt":
             return imgs, image_log
+        if composite:
+            return self._composite_pil(imgs), image_log
         return self._to_pil(imgs), image_log
+
+    def _composite_pil(self, imgs):
+        """decoded (B,3,H,W) floats in [0,1] -> PIL images: each pasted over ``last_init_pixels`` through ``last_pixel_mask``"""
+        from PIL import Image
+        init, mask = self.last_init_pixels, self.last_pixel_mask
+        if init is None or mask is None or tuple(init.shape[:2]) != tuple(imgs.shape[2:]):
+            raise ValueError(f"composite: the decoded picture is {tuple(imgs.shape[2:])}, the init picture "
+                             f"{None if init is None else tuple(init.shape[:2])}")
+        imgs = imgs.float().contiguous()
+        return [Image.fromarray(ops.composite_u8(imgs[i:i + 1], init, mask).cpu().numpy()) for i in range(len(imgs))]
+
+    @_on_own_device
+    def outpaint_canvas(self, image, left, top, right, bottom):
+        """The canvas of an outpainting run: ``image`` (what ``init_image`` accepts in 8-bit form: an RGB PIL image or a uint8
+        [H,W,3] array / tensor) grown by the four borders with its edge replicated -> (canvas uint8 [H',W',3], mask uint8
+        [H',W'], 255 on the new border and 0 over the original), both on the device, ready to pass as ``init_image`` /
+        ``mask_image``.  One launch (``ops.canvas_pad_u8``)."""
+        u8 = self._u8_image(image, 3, "image")
+        if u8 is None:
+            raise ValueError(f"outpaint_canvas takes an RGB PIL image or a uint8 [H,W,3] array / tensor, got {type(image).__name__}")
+        pads = (left, top, right, bottom)
+        if any(isinstance(p, bool) or not isinstance(p, (int, np.integer)) or p < 0 for p in pads):
+            raise ValueError(f"outpaint_canvas: the borders must be integers >= 0, got {pads!r}")
+        if isinstance(u8, np.ndarray):
+            u8 = torch.from_numpy(np.ascontiguousarray(u8))
+        H, W = int(u8.shape[0]), int(u8.shape[1])
+        if H < 1 or W < 1 or H + top + bottom > ops.RESIZE_MAX_DIM or W + left + right > ops.RESIZE_MAX_DIM:
+            raise ValueError(f"outpaint_canvas: {H} x {W} grown by {pads} leaves the sides 1..{ops.RESIZE_MAX_DIM}")
+        return ops.canvas_pad_u8(u8.to(self.device).contiguous(), *(int(p) for p in pads))
 
 
 class ElasticDiffusionControlNet(ElasticDiffusion):
@@ -1298,8 +1431,11 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
                        resampling_steps=20, new_p=0.3, rrg_stop_t=0.2, rrg_init_weight=1000,
                        rrg_scherduler_cls=CosineScheduler, cosine_scale=3.0, repaint_sampling=True,
                        progress=_default_progress, tiled_decoder=False, grid=False, guidance_rescale=0.0, *,
-                       output_type="pil", init_image=None, strength=1.0, mask_image=None):
+                       output_type="pil", init_image=None, strength=1.0, mask_image=None, mask_blur=0.0, mask_mode="binary",
+                       composite=False):
         check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
+        check_soft_inpaint_arguments(init_image, mask_image, mask_blur, mask_mode, composite, output_type, grid,
+                                     latent_size=(height // self.vae_scale_factor, width // self.vae_scale_factor))
         if condition_image is None:
             raise ValueError("condition_image is required (EDC:1183-1193)")
         h, w = self.get_downsample_size(height, width)
@@ -1310,4 +1446,4 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
                                       cosine_scale, repaint_sampling, progress, tiled_decoder, grid, guidance_rescale,
                                       condition_image=cond, controlnet_conditioning_scale=controlnet_conditioning_scale,
                                       output_type=output_type, init_image=init_image, strength=strength,
-                                      mask_image=mask_image)
+                                      mask_image=mask_image, mask_blur=mask_blur, mask_mode=mask_mode, composite=composite)

@@ -637,6 +637,41 @@ int ed_mask_to_latent(const uint8_t* src, int H, int W, int scale, int threshold
 int ed_inpaint_blend(const float* x, const uint8_t* mask, const float* z0, const float* noise, float a, float b, int clean,
                      float* out, int planes, int64_t HW, void* stream);
 
+/*
+ * ---- soft-edged inpainting (additions, no signature change, so still ABI v13): the mask blurred with
+ * Pillow's bytes, graded masks, Image.composite fused with the float -> 8-bit conversion, the outpainting canvas.  Integer or
+ * select arithmetic, exact; uint8 images are dense (pitch = width * channels), sides 1..8192.
+ *
+ * ed_box_blur3_rows_u8 / ed_box_blur3_cols_u8 -- PIL.ImageFilter.GaussianBlur(radius) on an L image is the rows launch followed by
+ *   the columns launch (src != dst in both).  Each launch performs the THREE box passes of its direction, every pass on the
+ *   previous pass's bytes, with the line (rows) or a strip of ed_box_blur3_cols_strip(H, W) columns (columns) staged in LDS.  One
+ *   pass over a line of n bytes, c(i) = clamp(i, 0, n - 1):
+ *       out[x] = (ww * sum_{d = -r..r} in[c(x + d)] + fw * (in[c(x - r - 1)] + in[c(x + r + 1)]) + 2^23) >> 24      (uint32)
+ *   The caller computes (r, ww, fw) from the radius as Pillow does: sigma2 = radius^2 / 3, Lw = sqrt(12 sigma2 + 1),
+ *   l = floor((Lw - 1) / 2), a = (2l + 1)(l(l + 1) - 3 sigma2) / (6 (sigma2 - (l + 1)^2)), fr = float32(l + a), r = int(fr),
+ *   ww = uint32(float32(2^24) / (2 fr + 1)) in float32, fw = (2^24 - (2r + 1) ww) / 2.  Weights with (2r + 1) ww + 2 fw > 2^24 (the
+ *   result would not be a byte) are hipErrorInvalidValue.
+ * ed_box_blur3_cols_strip -- no launch: the strip width in columns (a power of two in 4..32) the columns launch uses for an
+ *   H x W image; 0 for sides outside 1..8192.
+ * ed_mask_levels_to_latent -- ed_mask_to_latent's gather without the comparison: level[y, x] = src[scale * y, scale * x].
+ * ed_inpaint_blend_level -- ed_inpaint_blend with (level[p] <= thr) in place of (mask[p] == 0): out = level > thr ? x : known.
+ *   thr in 0..255; the caller's rule for target timestep index j of T is thr = (255 * (T - j)) / T (integer division).
+ * ed_composite_u8 -- u = (uint8)(decoded * 255) (fp32 product, truncated; decoded f32 [1, 3, H, W] in [0, 1]), then
+ *   PIL.Image.composite(u, init, mask) per channel: t = u * m + init * (255 - m) + 128; out = (t + (t >> 8)) >> 8.
+ *   init / out uint8 [H, W, 3] (interleaved), mask uint8 [H, W].  4 pixels per thread when W % 4 == 0 and the pointers allow it.
+ * ed_canvas_pad_u8 -- np.pad(img, mode="edge"): canvas uint8 [H + top + bottom, W + left + right, 3] and mask uint8 of the same
+ *   extent, 255 on the new border and 0 over the original; the padded sides must stay within 8192.
+ */
+int ed_box_blur3_rows_u8(const uint8_t* src, int H, int W, int r, int ww, int fw, uint8_t* dst, void* stream);
+int ed_box_blur3_cols_u8(const uint8_t* src, int H, int W, int r, int ww, int fw, uint8_t* dst, void* stream);
+int ed_box_blur3_cols_strip(int H, int W);
+int ed_mask_levels_to_latent(const uint8_t* src, int H, int W, int scale, uint8_t* level, int Hl, int Wl, void* stream);
+int ed_inpaint_blend_level(const float* x, const uint8_t* level, int thr, const float* z0, const float* noise, float a, float b,
+                           int clean, float* out, int planes, int64_t HW, void* stream);
+int ed_composite_u8(const float* decoded, const uint8_t* init, const uint8_t* mask, uint8_t* out, int H, int W, void* stream);
+int ed_canvas_pad_u8(const uint8_t* img, int H, int W, int left, int top, int right, int bottom, uint8_t* canvas, uint8_t* mask,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
