@@ -631,7 +631,8 @@ class Transformer2DModel(nn.Module):
         if self.linear_proj:
             h = linear_(group_norm_act(self.norm, x, tokens=True), self.proj_in.weight, self.proj_in.bias)
         else:
-            h = self.proj_in(group_norm_act(self.norm, x)).permute(0, 2, 3, 1).reshape(B, H * W, C)
+            # the blocks' LayerNorm kernels need a contiguous token tensor (.contiguous() is a no-op on a channels-last activation)
+            h = self.proj_in(group_norm_act(self.norm, x)).permute(0, 2, 3, 1).reshape(B, H * W, C).contiguous()
         s32 = _stream32(x, self.proj_out.weight.dtype)
         if s32:
             h = h.float()      # the blocks' own residual stream in fp32 as well (their LayerNorms hand the model dtype to the branches)
