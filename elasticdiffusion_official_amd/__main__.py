@@ -18,7 +18,9 @@ that name (0 = off), what such checkpoints are meant to be sampled with.  ``--in
 resized to H x W with Pillow's Lanczos filter, a mask of the picture's size with NEAREST.  ``--mask_blur R`` feathers the mask with
 Pillow's ``GaussianBlur(R)`` on the device, ``--mask_mode graded`` reads the grey levels as release times, ``--composite`` pastes
 the result over the init picture through the mask, and ``--outpaint L,T,R,B`` grows ``--init_image`` by that many pixels per side
-(edge replicated) and repaints the new border; it takes the place of ``--mask_image``.
+(edge replicated) and repaints the new border; it takes the place of ``--mask_image``.  ``--max_prompt_chunks N`` encodes a prompt of
+more than 75 tokens in up to N 75-token chunks instead of truncating it and ``--prompt_weighting true`` reads ``(word:1.3)`` / ``[word]``
+as A1111's emphasis syntax; both act on the CLIP encoders of ``--weights`` (the synthetic embeddings are always 77 tokens).
 """
 import argparse
 import os
@@ -88,6 +90,10 @@ def build_parser():
     ap.add_argument("--composite", action="store_true", help="paste the result over the init picture through the (blurred) mask")
     ap.add_argument("--outpaint", type=str, default=None, metavar="L,T,R,B", help="grow --init_image by this many pixels on the "
                     "left, top, right and bottom (edge replicated) and repaint the new border; exclusive with --mask_image")
+    ap.add_argument("--max_prompt_chunks", type=int, default=1, help="encode prompts of up to this many 75-token chunks "
+                    "(concatenated on the token axis) instead of truncating at 75 tokens; 1 = the reference's truncation")
+    ap.add_argument("--prompt_weighting", type=_bool, default=False, help="true: (word), [word], (word:1.3) scale the "
+                    "embeddings of their tokens (A1111 syntax); false: brackets are literal text")
     return ap
 
 
@@ -105,6 +111,8 @@ def main(argv=None):
     opt = build_parser().parse_args(argv)
     if not 0.0 <= opt.guidance_rescale <= 1.0:
         raise SystemExit(f"--guidance_rescale must be in [0, 1], got {opt.guidance_rescale}")
+    if opt.max_prompt_chunks < 1:
+        raise SystemExit(f"--max_prompt_chunks must be >= 1, got {opt.max_prompt_chunks}")
     from .pipeline import check_img2img_arguments
     pads = None
     if opt.outpaint is not None:
@@ -130,7 +138,8 @@ def main(argv=None):
     if opt.weights:
         from .text import load_clip
         kw["weights"] = opt.weights
-        kw["text_encoder"] = load_clip(opt.weights, opt.sd_version.startswith("XL"), device)
+        kw["text_encoder"] = load_clip(opt.weights, opt.sd_version.startswith("XL"), device,
+                                       max_prompt_chunks=opt.max_prompt_chunks, prompt_weighting=opt.prompt_weighting)
     sched = dict(prediction_type=opt.prediction_type, timestep_spacing=opt.timestep_spacing,
                  rescale_betas_zero_snr=opt.rescale_betas_zero_snr)
     if any(v is not None for v in sched.values()):  # a given flag overrides the snapshot's value / the default

@@ -339,12 +339,15 @@ k_flash_attn_fwd(const Params p) {
 //     P stays <= 2^RESCALE_LOG2 in between: harmless for a floating-point P (same relative rounding), fp32 sums.
 //     A ragged last tile (Nk % 64 != 0) is handled after the loop by the un-pipelined masked code.
 //
-// (2) k_flash_attn_smallkv -- cross-attention against the 77 text tokens (Nk <= 96).  The generic kernel pads 77 keys
+// (2) k_flash_attn_smallkv -- cross-attention against the text tokens (Nk <= 160; 77 per prompt chunk).  The generic kernel pads 77 keys
 //     to two 64-key tiles (40 % of its MFMAs are masked work), runs the online-softmax machinery for a single tile and
 //     re-stages K / V for every 128 query rows.  This kernel is a streaming kernel (the op is HBM-bound: 105 MB of q + out
 //     per 8 GFLOP at batch 20): K and V of one (batch, head) -- three 32-key blocks, zero beyond Nk -- are staged ONCE
 //     per workgroup, which then walks QBLOCKS x 128 query rows: per wave 12 + 12 MFMAs per 32 rows, plain softmax
-//     (no running state, no rescale), keys >= Nk masked.
+//     (no running state, no rescale), keys >= Nk masked.  A prompt of two 77-token chunks (154 keys) takes the same kernel with five
+//     key blocks: the 80 scores of a query row still live in registers, so the softmax stays one pass, and 53 760 B of LDS still fit two
+//     workgroups on a CU.  (Eight blocks for three chunks were built and measured 1.8-2x slower than the pipelined kernel -- 86 KB of LDS
+//     leave one wave per SIMD -- and are not kept: DESIGN.md section 21.5.)
 // =====================================================================================================================
 constexpr float RESCALE_LOG2 = 6.0f;  // defer the O rescale until a row's maximum grows by more than 2^6 (exp2 domain)
 constexpr float RESCALE_SUM_MAX = 64.0f;  // = 2^RESCALE_LOG2: the lazy variant's bound on a lane's sum of numerators
@@ -1149,7 +1152,7 @@ int ed_flash_attention(const void* q, const void* k, const void* v, void* out, i
   p.q = (const uint16_t*)q, p.k = (const uint16_t*)k, p.v = (const uint16_t*)v, p.o = (uint16_t*)out;
   hipStream_t st = (hipStream_t)stream;
   if ((v_path >= 4 && v_path <= 10)) {  // 4 / 5 / 6 = software-pipelined (5: lazy maximum, 6: + exponent-domain q), 8 = small-KV
-    if (v_path == 8 && Nk > 96) return (int)hipErrorInvalidValue;
+    if (v_path == 8 && Nk > 160) return (int)hipErrorInvalidValue;  // 5 blocks of 32 keys: the largest instantiation
     // the 8-wave variants' staging spans 64 key rows per pass, and 6 / 7 were only ever validated on full tiles: fewer than one
     // 64-key tile is rejected here, not only in the Python wrapper (which asks for >= 128)
     if ((v_path == 6 || v_path == 7 || v_path == 9 || v_path == 10) && Nk < 64) return (int)hipErrorInvalidValue;
@@ -1184,9 +1187,12 @@ int ed_flash_attention(const void* q, const void* k, const void* v, void* out, i
     } else if (Nk <= 64) {
       if (dtype == ED_BF16) k_flash_attn_smallkv<BF, 2><<<grid, block, 0, st>>>(p);
       else k_flash_attn_smallkv<HF, 2><<<grid, block, 0, st>>>(p);
-    } else {
+    } else if (Nk <= 96) {
       if (dtype == ED_BF16) k_flash_attn_smallkv<BF, 3><<<grid, block, 0, st>>>(p);
       else k_flash_attn_smallkv<HF, 3><<<grid, block, 0, st>>>(p);
+    } else {  // two prompt chunks (154 keys)
+      if (dtype == ED_BF16) k_flash_attn_smallkv<BF, 5><<<grid, block, 0, st>>>(p);
+      else k_flash_attn_smallkv<HF, 5><<<grid, block, 0, st>>>(p);
     }
     return (int)hipGetLastError();
   }

@@ -54,16 +54,19 @@ class GraphedForward:
         self.epoch += 1
 
     @staticmethod
-    def _key(shape, dtype, cond, t_shape=(), fresh_side=False):
-        """One graph per (rows shape, dtype, condition rows, timestep shape, fresh side inputs): the timestep is a 0-d tensor
-        when all rows share it and a per-row vector when the rows of several images in flight were fused into one batch."""
-        return (tuple(shape), dtype, None if cond is None else (tuple(cond.shape), cond.dtype), tuple(t_shape), bool(fresh_side))
+    def _key(shape, dtype, cond, t_shape=(), fresh_side=False, text=None, pooled=None):
+        """One graph per (rows shape, dtype, condition rows, timestep shape, fresh side inputs, text shape, pooled shape): the
+        timestep is a 0-d tensor when all rows share it and a per-row vector when the rows of several images in flight were
+        fused into one batch.  The text / pooled shapes (None when absent) keep a prompt of two or three 77-token chunks from
+        being copied into the static text rows -- and the hoisted cross-attention k|v -- of a graph captured for another length."""
+        return (tuple(shape), dtype, None if cond is None else (tuple(cond.shape), cond.dtype), tuple(t_shape), bool(fresh_side),
+                None if text is None else tuple(text.shape), None if pooled is None else tuple(pooled.shape))
 
-    def input_rows(self, shape, dtype, device, cond=None):
-        """The static model-input tensor for this batch shape (allocated on first request; 0-d timestep)."""
+    def input_rows(self, shape, dtype, device, cond=None, text=None, pooled=None):
+        """The static model-input tensor for this batch shape and these side inputs (allocated on first request; 0-d timestep)."""
         if not self.enabled:
             return torch.empty(shape, dtype=dtype, device=device)
-        key = self._key(shape, dtype, cond)
+        key = self._key(shape, dtype, cond, text=text, pooled=pooled)
         ent = self.entries.get(key)
         if ent is None:
             ent = {"x": torch.empty(shape, dtype=dtype, device=device), "graph": None, "epoch": -1, "eager": False}
@@ -107,7 +110,7 @@ class GraphedForward:
         in flight), so they are copied into the graph's static buffers on every replay, not once per image."""
         if not self.enabled:
             return self.fwd(x, t, text, pooled, cond, None)
-        key = self._key(x.shape, x.dtype, cond, t.shape, fresh_side)
+        key = self._key(x.shape, x.dtype, cond, t.shape, fresh_side, text, pooled)
         ent = self.entries.get(key)
         if ent is None:
             ent = {"x": torch.empty_like(x), "graph": None, "epoch": -1, "eager": False}

@@ -510,7 +510,7 @@ class Attention(nn.Module):
     def project_kv(self, context, out=None):
         """k, v of a cross-attention as ONE [B, Nk, 2 inner] tensor (fused weight).  They depend on the text rows only -- not on
         the latent, not on the timestep -- so a caller may compute them once per image and hand them to ``forward`` (``kv``)
-        instead of re-projecting the same 77 tokens in every one of the ~100 forwards of an image (UNet.cross_attention_kv)."""
+        instead of re-projecting the same text tokens in every one of the ~100 forwards of an image (UNet.cross_attention_kv)."""
         w = self._fused_weight(("to_k", "to_v"))
         if out is None:   # the same library call for the first projection and every refresh: one hipBLASLt solution, same bits
             out = torch.empty(context.shape[:-1] + (w.shape[0],), dtype=context.dtype, device=context.device)
@@ -868,9 +868,9 @@ class UNet2DConditionModel(nn.Module):
         return emb
 
     def cross_attention_kv(self, encoder_hidden_states, into=None):
-        """{id(attention module): k|v [B, 77, 2 inner]} for every cross-attention of the model: functions of the text rows only,
+        """{id(attention module): k|v [B, Nk, 2 inner]} for every cross-attention of the model: functions of the text rows only,
         so the pipeline computes them once per image (per hipGraph batch shape) instead of once per forward -- 70 projections
-        of 77 tokens per SDXL forward, ~100 forwards per image.  ``into``: a dict from an earlier call whose tensors are
+        of the text tokens (77 per prompt chunk) per SDXL forward, ~100 forwards per image.  ``into``: a dict from an earlier call whose tensors are
         overwritten in place (a captured hipGraph reads them at fixed addresses)."""
         ctx = encoder_hidden_states.to(self.dtype)
         out = {} if into is None else into

@@ -1087,8 +1087,8 @@ def vae_attention(q, k, v):
 # faster only when there is enough work to fill the chip with half as many workgroups (measured, batch 20: N=4096
 # 848 vs 776 TFLOP/s; N=1024 and the 77-key cross attention: no gain or slower; profiles/r2_s7_probe_attn.jsonl)
 # Round 3: 4 = software-pipelined self-attention kernel, 5 = the same with the lazy row maximum (no per-tile max after the
-# first tile; exact redo when a lane's sum of numerators exceeds 2^6), 8 = small-KV kernel (Nk <= 96: the 77-token cross
-# attention).  Round 4: 6 = 5 on exponent-domain queries (the caller folds scale * log2 e into q -- models.Attention folds it
+# first tile; exact redo when a lane's sum of numerators exceeds 2^6), 8 = small-KV kernel (Nk <= 160: the 77-token cross
+# attention; two prompt chunks where _stream_two_chunks says so).  Round 4: 6 = 5 on exponent-domain queries (the caller folds scale * log2 e into q -- models.Attention folds it
 # into the query projection weights -- and the reference maximum rides in the MFMA accumulator's initial value, so a
 # numerator is one v_exp_f32: 157 instead of 189 (lazy) / 214 (exact) instructions per 64-key tile and wave).
 FLASH_V_PATH = None
@@ -1136,12 +1136,22 @@ def _flash_variant(B, heads, Nq, Nk, k=None, v=None, prescaled=False):
         want = int(_ENV_VARIANT)
         if want in (4, 5, 7, 9, 10):
             return want if (Nk >= 128 and fits) else (8 if Nk <= 96 else legacy)
-        return want if (want != 8 or Nk <= 96) else legacy
-    if Nk <= 96:
+        return want if (want != 8 or Nk <= SMALLKV_MAX_KEYS) else legacy
+    if Nk <= 96 or _stream_two_chunks(Nq, Nk):
         return 8
     if Nk >= 128 and fits:
         return FLASH_DEFAULT_PIPE
     return legacy
+
+
+SMALLKV_MAX_KEYS = 160   # v_path 8: five blocks of 32 keys at the most (ed_flash_attention rejects more)
+
+
+def _stream_two_chunks(Nq, Nk):
+    """Cross attention on a prompt of two 77-token chunks (154 keys) through the streaming kernel instead of the pipelined
+    one?  Read off profiles/xattn_long_prompt_timing.json, as a rule on (Nq, Nk) alone: at
+    Nq = 4096 the five-block kernel is ahead at 20 and at 40 rows, at Nq = 1024 it loses at 20 rows."""
+    return 128 <= Nk <= SMALLKV_MAX_KEYS and Nq >= 4096
 
 
 FLASH_DEFAULT_PIPE = 5   # pipelined variant for natural-domain q (4 exact / 5 lazy maximum: +0.4-0.8 % on the forward, profiles/r4_s1_attention_variant_in_unet.txt)

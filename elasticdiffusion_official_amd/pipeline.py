@@ -242,11 +242,14 @@ class _Stager:
 class ElasticDiffusion(nn.Module):
     """Constructor signature of ED:111-115 plus keyword-only injection points (no pretrained weights, ``diffusers`` or
     network exist in the build environment): ``unet``, ``vae``, ``scheduler``, ``text_encoder`` (callable
-    ``prompts -> (embeds, pooled)``), ``controlnet``, ``process_group``."""
+    ``prompts -> (embeds, pooled)``), ``controlnet``, ``process_group``.  ``max_prompt_chunks`` / ``prompt_weighting`` are handed
+    to ``text.load_clip`` when the CLIP encoders come from ``weights`` (prompts of up to that many 75-token chunks instead of
+    truncation, A1111's ``(word:1.3)`` syntax; both off by default)."""
 
     def __init__(self, device, sd_version="2.0", verbose=False, log_freq=5, view_batch_size=1, low_vram=False, *,
                  unet=None, vae=None, scheduler=None, text_encoder=None, controlnet=None, process_group=None,
-                 model_dtype=None, weights=None, cache_backgrounds=False, use_graphs=True, residual_fp32=None):
+                 model_dtype=None, weights=None, cache_backgrounds=False, use_graphs=True, residual_fp32=None,
+                 max_prompt_chunks=1, prompt_weighting=False):
         super().__init__()
         device = torch.device(device)
         if device.type == "cuda" and device.index is None and torch.cuda.is_available():
@@ -295,7 +298,7 @@ class ElasticDiffusion(nn.Module):
             # real UNet/VAE weights with synthetic prompt embeddings would be prompt-independent garbage: a snapshot
             # must carry its CLIP encoders (ED:145-151); a failure to load them is an error, not a silent fallback
             from .text import load_clip
-            text_encoder = load_clip(weights, xl, device)
+            text_encoder = load_clip(weights, xl, device, max_prompt_chunks=max_prompt_chunks, prompt_weighting=prompt_weighting)
         self.text_encoder = text_encoder
         self.model_size = 128 if xl else 64  # d_H, d_W of ED:398-400
         self.vae_scale_factor = 2 ** (len(self.vae.config.block_out_channels) - 1)  # ED:156
@@ -366,11 +369,17 @@ class ElasticDiffusion(nn.Module):
         return next(self.unet.parameters()).dtype
 
     @torch.no_grad()
-    def get_text_embeds(self, prompt):
+    def get_text_embeds(self, prompt, min_chunks=None):
         """ED:254-265.  With no CLIP weights available the default is a deterministic synthetic embedding per prompt
-        string (shape-compatible: (B,77,cross_attention_dim) and the pooled (B,projection_dim))."""
+        string (shape-compatible: (B,77,cross_attention_dim) and the pooled (B,projection_dim)); the synthetic embeddings are
+        always 77 tokens, whatever the prompt's length.  ``min_chunks``: at least this many 77-token chunks from an encoder
+        that encodes long prompts in chunks (one with a ``chunks`` method, text.ClipTextEncoder); any other injected callable
+        is called as ``text_encoder(prompt)``."""
         if self.text_encoder is not None:
-            e, p = self.text_encoder(prompt)
+            if min_chunks is not None and hasattr(self.text_encoder, "chunks"):
+                e, p = self.text_encoder(prompt, min_chunks=min_chunks)
+            else:
+                e, p = self.text_encoder(prompt)
             return e.to(self.device), p.to(self.device)
         cfg = self.unet.config
         D = getattr(cfg, "cross_attention_dim", 768)
@@ -574,7 +583,7 @@ class ElasticDiffusion(nn.Module):
         direct = direct and P.one_batch and self.sharder.world_size == 1
         if P.one_batch:
             shape = (n_g + n_v, C, P.gpad.PH, P.gpad.PW)
-            rows = (self._runner.input_rows(shape, mdt, dev, None if cond is None else cond[K]) if direct
+            rows = (self._runner.input_rows(shape, mdt, dev, None if cond is None else cond[K], *emb[K]) if direct
                     else torch.empty(shape, device=dev, dtype=mdt))
             g_rows, v_rows = rows[:n_g], rows[n_g:]
         else:
@@ -877,8 +886,17 @@ class ElasticDiffusion(nn.Module):
         S.norm = np.float32(2.0 / (C * P.Hl * P.Wl))
         return S
 
+    def _prompt_chunks(self, prompts, negative_prompts):
+        """Chunk count the encoder needs for these prompts and negative prompts together, or None for an encoder that does not
+        chunk (an injected callable without ``chunks``, the synthetic embeddings)."""
+        enc = self.text_encoder
+        if enc is None or not hasattr(enc, "chunks"):
+            return None
+        return max(enc.chunks(prompts), enc.chunks(negative_prompts))
+
     def _program(self, S, prompts, negative_prompts, condition_image=None, trace=None, progress=_identity_progress,
-                 direct=True, frames=None, init_image=None, mask_image=None, mask_blur=0.0, mask_mode="binary"):
+                 direct=True, frames=None, init_image=None, mask_image=None, mask_blur=0.0, mask_mode="binary",
+                 min_chunks=None):
         """Generator: the denoising loop of ONE image (ED:981-1078), yielding ``_ModelCall``s; returns the final latent.
         All host RNG draws happen inside, in the reference's order.  ``init_image`` / ``mask_image``: image-to-image and
         inpainting -- the loop starts at timestep index ``S.t_start`` from the noised encoding of the
@@ -889,8 +907,15 @@ class ElasticDiffusion(nn.Module):
             prompts = [prompts]
         if isinstance(negative_prompts, str):
             negative_prompts = [negative_prompts] * len(prompts)
-        un, pun = self.get_text_embeds(negative_prompts)
-        co, pco = self.get_text_embeds(prompts)
+        # prompt and negative prompt share one token count: the larger chunk count of the two (and of ``min_chunks``)
+        n = self._prompt_chunks(prompts, negative_prompts)
+        if n is not None:
+            n = max(n, int(min_chunks or 1))
+        un, pun = self.get_text_embeds(negative_prompts, n)
+        co, pco = self.get_text_embeds(prompts, n)
+        if un.shape[1] != co.shape[1]:
+            raise ValueError(f"text_encoder returned {co.shape[1]} tokens for the prompts and {un.shape[1]} for the negative "
+                             "prompts: the two are rows of one model batch and must have the same token count")
         B = len(prompts)
         # initial latent from the host generator (ED:998-1000)
         z0 = noise0 = mask = None
@@ -970,7 +995,7 @@ class ElasticDiffusion(nn.Module):
                          rrg_scherduler_cls=CosineScheduler, cosine_scale=3.0, repaint_sampling=True,
                          progress=_identity_progress, condition_image=None, controlnet_conditioning_scale=1.0,
                          trace=None, guidance_rescale=0.0, init_image=None, strength=1.0, mask_image=None, *, mask_blur=0.0,
-                         mask_mode="binary"):
+                         mask_mode="binary", min_chunks=None):
         """``guidance_rescale`` in [0, 1] (diffusers' keyword; 0 = off): the std rescale of the guided model output of
         arXiv 2305.08891 section 3.4, what zero-terminal-SNR / v-prediction checkpoints are meant to be sampled with
         (DESIGN.md section 17).
@@ -990,7 +1015,10 @@ class ElasticDiffusion(nn.Module):
         time: the pixel is held to the init image while L <= (255 * (T - j)) // T at target timestep index j, so black is kept
         bit for bit, white is never held, and a grey one is free from the original at the noise level where the remaining
         fraction of the schedule drops to L / 255.  No new RNG draws, one blend launch per phase in either mode.  The pixel
-        mask and the 8-bit init picture stay on the device as ``last_pixel_mask`` / ``last_init_pixels``."""
+        mask and the 8-bit init picture stay on the device as ``last_pixel_mask`` / ``last_init_pixels``.
+
+        ``min_chunks`` (keyword-only): encode prompt and negative prompt to at least this many 77-token
+        chunks (a chunking ``text_encoder`` only) -- what a job of ``generate_latents_interleaved`` is encoded with."""
         check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
         mask_blur = check_soft_inpaint_arguments(init_image, mask_image, mask_blur, mask_mode,
                                                  latent_size=(height // self.vae_scale_factor, width // self.vae_scale_factor))
@@ -999,7 +1027,8 @@ class ElasticDiffusion(nn.Module):
                             controlnet_conditioning_scale, guidance_rescale, strength)
         self._runner.new_image()
         x = self._drive(self._program(S, prompts, negative_prompts, condition_image, trace, progress, direct=True,
-                                      init_image=init_image, mask_image=mask_image, mask_blur=mask_blur, mask_mode=mask_mode))
+                                      init_image=init_image, mask_image=mask_image, mask_blur=mask_blur, mask_mode=mask_mode,
+                                      min_chunks=min_chunks))
         self.last_latents = x
         self.host_s["blocked_ahead_of_gpu"] = self._stager.waited
         self._mark("loop_done")
@@ -1024,7 +1053,16 @@ class ElasticDiffusion(nn.Module):
         is then row-sharded over the ranks like any other batch.  Why: with N ranks a lone image leaves 20/N and 6/N rows
         per rank, where the UNet runs at a fraction of its batch-20 rate; m images in flight multiply the rows per
         forward by ~m while the exchange stays one all-gather per tick.  Returns the final latents in job order
-        (``on_done(index, latent)`` is called as each finishes, e.g. to decode it)."""
+        (``on_done(index, latent)`` is called as each finishes, e.g. to decode it).
+
+        Prompt length: the rows of all jobs share one text tensor, so with a chunking ``text_encoder`` every job is encoded to
+        n chunks, n = the largest chunk count over the prompts and negative prompts of ALL jobs of the call: a job equals the
+        same job run alone through ``generate_latents(..., min_chunks=n)``."""
+        n_chunks = None
+        for job in jobs:
+            n = self._prompt_chunks(job["prompts"], job.get("negative_prompts", ""))
+            if n is not None:
+                n_chunks = max(n_chunks or 1, n)
         for job in jobs:
             check_img2img_arguments(num_inference_steps, job.get("init_image"), strength, job.get("mask_image"))
             if job.get("composite"):
@@ -1060,7 +1098,7 @@ class ElasticDiffusion(nn.Module):
             prog = self._program(S, job["prompts"], job.get("negative_prompts", ""), job.get("condition_image"),
                                  direct=False, frames=frames, init_image=job.get("init_image"),
                                  mask_image=job.get("mask_image"), mask_blur=float(job.get("mask_blur", 0.0)),
-                                 mask_mode=job.get("mask_mode", "binary"))
+                                 mask_mode=job.get("mask_mode", "binary"), min_chunks=n_chunks)
             with rng:
                 call = next(prog)
             live.append([j, prog, rng, call])
@@ -1074,7 +1112,7 @@ class ElasticDiffusion(nn.Module):
             groups = {}
             for ent in live:
                 c = ent[3]
-                groups.setdefault((tuple(c.rows.shape[1:]), c.cond is None), []).append(ent)
+                groups.setdefault((tuple(c.rows.shape[1:]), c.cond is None, tuple(c.text.shape[1:])), []).append(ent)
             for ents in groups.values():
                 calls = [e[3] for e in ents]
                 sizes = [c.rows.shape[0] for c in calls]

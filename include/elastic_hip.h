@@ -430,13 +430,14 @@ int ed_phase_epilogue_gr(const void* g_out, const void* v_out, int dtype, const 
  *   out dtype [B, Nq, H, 64]   strides o_sb, o_sn
  *   head_dim = 64 (SDXL, SD 2.x: every v_path below) or 40 / 80 / 160 (SD 1.x's 8 heads: one generic kernel with the head
  *   dimension zero-padded to a multiple of 32 inside the kernel, v_path ignored); dtype = ED_F16 | ED_BF16; q/k/v 16-byte aligned with strides % 8 == 0, out 8-byte aligned
- *   with strides % 4 == 0.  Nk need not be a multiple of the 64-key tile (cross-attention: 77 text tokens).
+ *   with strides % 4 == 0.  Nk need not be a multiple of the 64-key tile (cross-attention: 77 text tokens per prompt chunk).
  *   v_path: kernel variant.  0 = V transposed on the fly by ds_read_b64_tr_b16, 1 = V^T tile staged in LDS; +2 = 64
  *   query rows per wave (0..3 give bit-identical results).  4 = software-pipelined kernel (softmax of tile t issued in
  *   the shadow of the MFMAs of tiles t+1 / t-1, deferred O rescale; K / V addressed with 32-bit offsets: returns
  *   hipErrorInvalidValue when (Nk + 128) * max(k_sn, v_sn) * 2 >= 2^31).  5 = 4 without the per-tile row maximum after the
- *   first tile (numerators against the standing reference; exact redo of a tile whose sum exceeds 2^6).  8 = small-KV kernel for Nk <= 96 (cross
- *   attention on the 77 text tokens: K / V staged once per 512 query rows, single pass, no online rescale).
+ *   first tile (numerators against the standing reference; exact redo of a tile whose sum exceeds 2^6).  8 = small-KV kernel for Nk <= 160 (cross
+ *   attention on the text tokens, 77 per prompt chunk: K / V staged once per 512 query rows, single pass, no online rescale; 2 / 3 / 5
+ *   blocks of 32 keys for Nk <= 64 / 96 / 160, Nk > 160 returns hipErrorInvalidValue before any launch).
  *   4, 5 and 8 agree with 0..3 to the rounding of P (same fp32 accumulation, different summation grouping).
  *   6 = 5 for EXPONENT-DOMAIN queries: the caller has multiplied q by scale * log2(e) (the model folds it into the query
  *   projection weights), `scale` is ignored and out = sum_k 2^(q.k) v / sum_k 2^(q.k).  The row reference -m is the initial
