@@ -21,6 +21,9 @@ the result over the init picture through the mask, and ``--outpaint L,T,R,B`` gr
 (edge replicated) and repaints the new border; it takes the place of ``--mask_image``.  ``--max_prompt_chunks N`` encodes a prompt of
 more than 75 tokens in up to N 75-token chunks instead of truncating it and ``--prompt_weighting true`` reads ``(word:1.3)`` / ``[word]``
 as A1111's emphasis syntax; both act on the CLIP encoders of ``--weights`` (the synthetic embeddings are always 77 tokens).
+``--sd_version 1.5-inpaint`` / ``2.0-inpaint`` / ``XL1.0-inpaint`` builds the 9-channel inpainting UNet of the family (what the
+inpainting checkpoints carry; a ``--weights`` snapshot with a 9-channel ``conv_in`` selects it by itself): it needs ``--init_image``
+and a mask, and conditions on the mask and the blanked picture instead of pasting the kept region back.
 """
 import argparse
 import os
@@ -40,7 +43,9 @@ def build_parser():
     ap.add_argument("--prompt", type=str, default="A realistic portrait of a young black woman. she has a Christmas red "
                     "hat and a red scarf. Her eyes are light brown like they're almost caramel color. Her attire, simple yet dignified.")
     ap.add_argument("--negative", type=str, default="blurry, ugly, duplicate, no details, deformed")
-    ap.add_argument("--sd_version", type=str, default="XL1.0")
+    ap.add_argument("--sd_version", type=str, default="XL1.0", help="1.4, 1.5, 2.0, 2.1, XL1.0; 1.5-inpaint, 2.0-inpaint, "
+                    "XL1.0-inpaint: the 9-channel inpainting UNet of that family (needs --init_image and --mask_image / "
+                    "--outpaint); a --weights snapshot with a 9-channel conv_in selects it by itself")
     ap.add_argument("--H", type=int, default=2048)
     ap.add_argument("--W", type=int, default=2048)
     ap.add_argument("--low_vram", type=_bool, default=False)
@@ -97,6 +102,9 @@ def build_parser():
     return ap
 
 
+INPAINT_VERSIONS = ("1.5-inpaint", "2.0-inpaint", "XL1.0-inpaint")
+
+
 def _outpaint_borders(text):
     try:
         pads = tuple(int(v) for v in text.split(","))
@@ -121,6 +129,13 @@ def main(argv=None):
         pads = _outpaint_borders(opt.outpaint)
     has_mask = opt.mask_image or pads
     from .pipeline import check_soft_inpaint_arguments
+    if opt.sd_version.endswith("-inpaint"):
+        if opt.sd_version not in INPAINT_VERSIONS:
+            raise SystemExit(f"--sd_version: the inpainting variants are {', '.join(INPAINT_VERSIONS)}, got {opt.sd_version!r}")
+        if not opt.init_image or not has_mask:
+            raise SystemExit(f"--sd_version {opt.sd_version} needs --init_image and --mask_image (or --outpaint)")
+        if opt.mask_mode == "graded" or opt.condition_image:
+            raise SystemExit(f"--sd_version {opt.sd_version} takes neither --mask_mode graded nor --condition_image")
     try:
         check_img2img_arguments(opt.steps, opt.init_image, opt.strength, has_mask or None)
         # the files are opened later: 8-bit pictures stand in for them, so that every rule is checked before a model is built

@@ -55,6 +55,8 @@ SIGNATURES = {
     "ed_groupnorm_nhwc_cat": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp],
     "ed_assemble_rows": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
                          _i, _i, _i, _i, _i, _i, _i, _i, _vp],
+    "ed_assemble_rows_x": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
+                           _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp],
     "ed_phase_epilogue": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                           _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f,
                           _vp],
@@ -96,6 +98,7 @@ SIGNATURES = {
     "ed_resize_rows_u8": [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp],
     "ed_resize_cols_u8": [_vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
     "ed_u8_to_vae_input": [_vp, _i, _i, _vp, _i, _vp],
+    "ed_u8_to_vae_input_masked": [_vp, _vp, _i, _i, _i, _vp, _i, _vp],
     "ed_img2img_init": [_vp, _vp, _i, _vp, _vp, _f, _f, _f, _vp, _vp, _i64, _vp],
     "ed_mask_to_latent": [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp],
     "ed_inpaint_blend": [_vp, _vp, _vp, _vp, _f, _f, _i, _vp, _i, _i64, _vp],

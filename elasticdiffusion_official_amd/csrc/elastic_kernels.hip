@@ -94,30 +94,37 @@ inline int grid_for(int64_t n, int per_thread = 1) {
 inline int done() { return (int)hipGetLastError(); }
 
 // ---- ed_gather_views / ed_tile_gather_pad ----------------------------------------------------------
-template <typename Tag>
+// X (ed_assemble_rows_x): rows carry C + E channels; channel c >= C is the same gather applied to plane c - C of `extra`
+// ([B,E,H,W]), with the constant pad_value[c - C] wherever a latent channel reads the frame.  X = false is the code as it was.
+template <typename Tag, bool X = false>
 __device__ __forceinline__ void gather_windows_body(int64_t t, const float* __restrict__ latent, void* __restrict__ out, int B, int C, int H, int W,
                  const int32_t* __restrict__ wy0, const int32_t* __restrict__ wx0, int V, int Sh, int Sw,
-                 int PH, int PW, int off_y, int off_x, const float* __restrict__ frame, float divisor, int use_div) {
-  int64_t n = (int64_t)V * B * C * PH * PW;
+                 int PH, int PW, int off_y, int off_x, const float* __restrict__ frame, float divisor, int use_div,
+                 const float* __restrict__ extra = nullptr, int E = 0, const float* __restrict__ pad_value = nullptr) {
+  const int CT = X ? C + E : C;
+  int64_t n = (int64_t)V * B * CT * PH * PW;
   if (t >= n) return;
   int x = (int)(t % PW);
   int64_t r = t / PW;
   int y = (int)(r % PH);
   r /= PH;
-  int c = (int)(r % C);
-  r /= C;  // row = v*B + b
+  int c = (int)(r % CT);
+  r /= CT;  // row = v*B + b
   int b = (int)(r % B);
   int v = (int)(r / B);
+  const bool ex = X && c >= C;
   int yy = y - off_y, xx = x - off_x;
   float val;
   if (yy >= 0 && yy < Sh && xx >= 0 && xx < Sw) {
     int sy = wy0[v] + yy, sx = wx0[v] + xx;
     if (sy >= 0 && sy < H && sx >= 0 && sx < W) {
-      val = latent[(((int64_t)b * C + c) * H + sy) * W + sx];
+      val = ex ? extra[(((int64_t)b * E + (c - C)) * H + sy) * W + sx] : latent[(((int64_t)b * C + c) * H + sy) * W + sx];
       if (use_div) val = __fdiv_rn(val, divisor);
     } else {
       val = 0.0f;
     }
+  } else if (ex) {
+    val = pad_value[c - C];
   } else {
     val = frame ? frame[((int64_t)c * PH + y) * PW + x] : 0.0f;
   }
@@ -133,26 +140,29 @@ k_gather_windows(const float* __restrict__ latent, void* __restrict__ out, int B
 }
 
 // 4 consecutive x per thread; requires PW, Sw, off_x multiples of 4 (a group is entirely inside or outside the window)
-template <typename Tag>
+template <typename Tag, bool X = false>
 __device__ __forceinline__ void gather_windows_x4_body(int64_t t, const float* __restrict__ latent, void* __restrict__ out, int B, int C, int H, int W,
                     const int32_t* __restrict__ wy0, const int32_t* __restrict__ wx0, int V, int Sh, int Sw,
-                    int PH, int PW, int off_y, int off_x, const float* __restrict__ frame, float divisor, int use_div) {
+                    int PH, int PW, int off_y, int off_x, const float* __restrict__ frame, float divisor, int use_div,
+                    const float* __restrict__ extra = nullptr, int E = 0, const float* __restrict__ pad_value = nullptr) {
+  const int CT = X ? C + E : C;
   int PW4 = PW >> 2;
-  int64_t n = (int64_t)V * B * C * PH * PW4;
+  int64_t n = (int64_t)V * B * CT * PH * PW4;
   if (t >= n) return;
   int x = (int)(t % PW4) << 2;
   int64_t r = t / PW4;
   int y = (int)(r % PH);
   r /= PH;
-  int c = (int)(r % C);
-  r /= C;
+  int c = (int)(r % CT);
+  r /= CT;
   int b = (int)(r % B);
   int v = (int)(r / B);
+  const bool ex = X && c >= C;
   int yy = y - off_y, xx = x - off_x;
   float val[4];
   if (yy >= 0 && yy < Sh && xx >= 0 && xx < Sw) {
     int sy = wy0[v] + yy, sx0 = wx0[v] + xx;
-    const float* src = latent + (((int64_t)b * C + c) * H + sy) * W;
+    const float* src = ex ? extra + (((int64_t)b * E + (c - C)) * H + sy) * W : latent + (((int64_t)b * C + c) * H + sy) * W;
     bool row_ok = sy >= 0 && sy < H;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -160,6 +170,8 @@ __device__ __forceinline__ void gather_windows_x4_body(int64_t t, const float* _
       float f = (row_ok && sx >= 0 && sx < W) ? src[sx] : 0.0f;
       val[e] = (use_div && row_ok && sx >= 0 && sx < W) ? __fdiv_rn(f, divisor) : f;
     }
+  } else if (ex) {
+    val[0] = val[1] = val[2] = val[3] = pad_value[c - C];
   } else if (frame) {
     float4 f = *reinterpret_cast<const float4*>(frame + ((int64_t)c * PH + y) * PW + x);
     val[0] = f.x; val[1] = f.y; val[2] = f.z; val[3] = f.w;
@@ -213,29 +225,38 @@ k_scatter_centres(const void* __restrict__ pred, float* __restrict__ local, int 
 }
 
 // ---- ed_pick_assemble ------------------------------------------------------------------------------
-template <typename Tag>
+template <typename Tag, bool X = false>
 __device__ __forceinline__ void pick_assemble_body(int64_t t, const float* __restrict__ latent, const uint8_t* __restrict__ idx,
                 const int32_t* __restrict__ src_row, const int32_t* __restrict__ src_col,
                 const float* __restrict__ frame, void* __restrict__ out, float* __restrict__ low,
-                int K, int B, int C, int H, int W, int h, int w, int PH, int PW, int off_y, int off_x) {
-  int64_t n = (int64_t)K * B * C * PH * PW;
+                int K, int B, int C, int H, int W, int h, int w, int PH, int PW, int off_y, int off_x,
+                const float* __restrict__ extra = nullptr, int E = 0, const float* __restrict__ pad_value = nullptr) {
+  const int CT = X ? C + E : C;  // X: see gather_windows_body; `low` keeps the C latent channels
+  int64_t n = (int64_t)K * B * CT * PH * PW;
   if (t >= n) return;
   int x = (int)(t % PW);
   int64_t r = t / PW;
   int y = (int)(r % PH);
   r /= PH;
-  int c = (int)(r % C);
-  r /= C;
+  int c = (int)(r % CT);
+  r /= CT;
   int b = (int)(r % B);
   int k = (int)(r / B);
+  const bool ex = X && c >= C;
   int i = y - off_y, j = x - off_x;
   float val;
   if (i >= 0 && i < h && j >= 0 && j < w) {
     int q = idx[(int64_t)k * h * w + (int64_t)i * w + j];
     int sy = src_row[2 * i + (q >> 1)];
     int sx = src_col[2 * j + (q & 1)];
-    val = latent[(((int64_t)b * C + c) * H + sy) * W + sx];
-    if (low) low[((((int64_t)k * B + b) * C + c) * h + i) * w + j] = val;
+    if (ex) {
+      val = extra[(((int64_t)b * E + (c - C)) * H + sy) * W + sx];
+    } else {
+      val = latent[(((int64_t)b * C + c) * H + sy) * W + sx];
+      if (low) low[((((int64_t)k * B + b) * C + c) * h + i) * w + j] = val;
+    }
+  } else if (ex) {
+    val = pad_value[c - C];
   } else {
     val = frame ? frame[((int64_t)c * PH + y) * PW + x] : 0.0f;
   }
@@ -243,8 +264,8 @@ __device__ __forceinline__ void pick_assemble_body(int64_t t, const float* __res
   int64_t e = ((int64_t)c * PH + y) * PW + x;
   int64_t row_u = ((int64_t)k * 2 + 0) * B + b;
   int64_t row_c = ((int64_t)k * 2 + 1) * B + b;
-  st<Tag>(out, row_u * C * plane + e, val);
-  st<Tag>(out, row_c * C * plane + e, val);
+  st<Tag>(out, row_u * CT * plane + e, val);
+  st<Tag>(out, row_c * CT * plane + e, val);
 }
 
 template <typename Tag>
@@ -257,27 +278,30 @@ k_pick_assemble(const float* __restrict__ latent, const uint8_t* __restrict__ id
 }
 
 // 4 consecutive x per thread; requires PW, w, off_x multiples of 4
-template <typename Tag>
+template <typename Tag, bool X = false>
 __device__ __forceinline__ void pick_assemble_x4_body(int64_t t, const float* __restrict__ latent, const uint8_t* __restrict__ idx,
                    const int32_t* __restrict__ src_row, const int32_t* __restrict__ src_col,
                    const float* __restrict__ frame, void* __restrict__ out, float* __restrict__ low,
-                   int K, int B, int C, int H, int W, int h, int w, int PH, int PW, int off_y, int off_x) {
+                   int K, int B, int C, int H, int W, int h, int w, int PH, int PW, int off_y, int off_x,
+                   const float* __restrict__ extra = nullptr, int E = 0, const float* __restrict__ pad_value = nullptr) {
+  const int CT = X ? C + E : C;
   int PW4 = PW >> 2;
-  int64_t n = (int64_t)K * B * C * PH * PW4;
+  int64_t n = (int64_t)K * B * CT * PH * PW4;
   if (t >= n) return;
   int x = (int)(t % PW4) << 2;
   int64_t r = t / PW4;
   int y = (int)(r % PH);
   r /= PH;
-  int c = (int)(r % C);
-  r /= C;
+  int c = (int)(r % CT);
+  r /= CT;
   int b = (int)(r % B);
   int k = (int)(r / B);
+  const bool ex = X && c >= C;
   int i = y - off_y, j = x - off_x;
   float val[4];
   if (i >= 0 && i < h && j >= 0 && j < w) {
     uint32_t q4 = *reinterpret_cast<const uint32_t*>(idx + (int64_t)k * h * w + (int64_t)i * w + j);
-    const float* plane = latent + ((int64_t)b * C + c) * H * W;
+    const float* plane = ex ? extra + ((int64_t)b * E + (c - C)) * H * W : latent + ((int64_t)b * C + c) * H * W;
     int r0 = src_row[2 * i], r1 = src_row[2 * i + 1];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -286,9 +310,11 @@ __device__ __forceinline__ void pick_assemble_x4_body(int64_t t, const float* __
       int sx = src_col[2 * (j + e) + (q & 1)];
       val[e] = plane[(int64_t)sy * W + sx];
     }
-    if (low)
+    if (low && !ex)
       *reinterpret_cast<float4*>(low + ((((int64_t)k * B + b) * C + c) * h + i) * w + j) =
           make_float4(val[0], val[1], val[2], val[3]);
+  } else if (ex) {
+    val[0] = val[1] = val[2] = val[3] = pad_value[c - C];
   } else if (frame) {
     float4 f = *reinterpret_cast<const float4*>(frame + ((int64_t)c * PH + y) * PW + x);
     val[0] = f.x; val[1] = f.y; val[2] = f.z; val[3] = f.w;
@@ -299,8 +325,8 @@ __device__ __forceinline__ void pick_assemble_x4_body(int64_t t, const float* __
   int64_t e0 = ((int64_t)c * PH + y) * PW + x;
   int64_t row_u = ((int64_t)k * 2 + 0) * B + b;
   int64_t row_c = ((int64_t)k * 2 + 1) * B + b;
-  st4<Tag>(out, row_u * C * plane_sz + e0, val[0], val[1], val[2], val[3]);
-  st4<Tag>(out, row_c * C * plane_sz + e0, val[0], val[1], val[2], val[3]);
+  st4<Tag>(out, row_u * CT * plane_sz + e0, val[0], val[1], val[2], val[3]);
+  st4<Tag>(out, row_c * CT * plane_sz + e0, val[0], val[1], val[2], val[3]);
 }
 
 template <typename Tag>
@@ -532,6 +558,36 @@ k_assemble_rows(const AssembleArgs a) {
     else
       gather_windows_body<Tag>(t, a.latent, a.v_out, a.B, a.C, a.H, a.W, a.win_y0, a.win_x0, a.V, a.Sh, a.Sw, a.vPH, a.vPW,
                                a.v_off_y, a.v_off_x, a.vframe, 1.0f, 0);
+  }
+}
+
+// ---- ed_assemble_rows_x: ed_assemble_rows on rows of C + E channels (9-channel inpainting UNets) --------
+// The same two bodies with the channel loop over C + E: channels C.. gather `extra` through the index map of the row's latent.
+struct AssembleArgsX : AssembleArgs {
+  const float* extra;      // [B,E,H,W]
+  const float* pad_value;  // [E]
+  int E;
+};
+
+template <typename Tag, bool PX4, bool GX4>
+__global__ void __launch_bounds__(ED_BLOCK)
+k_assemble_rows_x(const AssembleArgsX a) {
+  if ((int)blockIdx.x < a.pick_blocks) {
+    int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
+    if (PX4)
+      pick_assemble_x4_body<Tag, true>(t, a.latent, a.idx, a.src_row, a.src_col, a.gframe, a.g_out, a.low, a.K, a.B, a.C, a.H,
+                                       a.W, a.h, a.w, a.gPH, a.gPW, a.g_off_y, a.g_off_x, a.extra, a.E, a.pad_value);
+    else
+      pick_assemble_body<Tag, true>(t, a.latent, a.idx, a.src_row, a.src_col, a.gframe, a.g_out, a.low, a.K, a.B, a.C, a.H, a.W,
+                                    a.h, a.w, a.gPH, a.gPW, a.g_off_y, a.g_off_x, a.extra, a.E, a.pad_value);
+  } else {
+    int64_t t = (int64_t)((int)blockIdx.x - a.pick_blocks) * ED_BLOCK + threadIdx.x;
+    if (GX4)
+      gather_windows_x4_body<Tag, true>(t, a.latent, a.v_out, a.B, a.C, a.H, a.W, a.win_y0, a.win_x0, a.V, a.Sh, a.Sw, a.vPH,
+                                        a.vPW, a.v_off_y, a.v_off_x, a.vframe, 1.0f, 0, a.extra, a.E, a.pad_value);
+    else
+      gather_windows_body<Tag, true>(t, a.latent, a.v_out, a.B, a.C, a.H, a.W, a.win_y0, a.win_x0, a.V, a.Sh, a.Sw, a.vPH, a.vPW,
+                                     a.v_off_y, a.v_off_x, a.vframe, 1.0f, 0, a.extra, a.E, a.pad_value);
   }
 }
 
@@ -977,6 +1033,40 @@ k_u8_to_vae_input(const uint8_t* __restrict__ img, void* __restrict__ out, int64
   st<Tag>(out, t, vae_input_of(img[3 * p + c]));
 }
 
+// ed_u8_to_vae_input_masked: the same value, or +0.0 where the pixel's mask byte is >= threshold (a select, so the zero has no sign
+// to inherit: DESIGN.md section 22.3).  4 pixels per thread: the 4 mask bytes as one aligned dword.
+__device__ __forceinline__ float vae_input_masked_of(uint32_t v, uint32_t m, uint32_t thr) {
+  return m >= thr ? 0.0f : vae_input_of(v);
+}
+
+template <typename Tag>
+__global__ void __launch_bounds__(ED_BLOCK)
+k_u8_to_vae_input_masked_x4(const uint32_t* __restrict__ img, const uint32_t* __restrict__ mask, uint32_t thr, void* __restrict__ out,
+                            int64_t HW) {
+  int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
+  if (t >= (HW >> 2)) return;
+  uint32_t w0 = img[3 * t], w1 = img[3 * t + 1], w2 = img[3 * t + 2];  // R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3
+  uint32_t m4 = mask[t];
+  uint32_t m0 = m4 & 255u, m1 = (m4 >> 8) & 255u, m2 = (m4 >> 16) & 255u, m3 = m4 >> 24;
+  int64_t p = t << 2;
+  st4<Tag>(out, p, vae_input_masked_of(w0 & 255u, m0, thr), vae_input_masked_of(w0 >> 24, m1, thr),
+           vae_input_masked_of((w1 >> 16) & 255u, m2, thr), vae_input_masked_of((w2 >> 8) & 255u, m3, thr));
+  st4<Tag>(out, HW + p, vae_input_masked_of((w0 >> 8) & 255u, m0, thr), vae_input_masked_of(w1 & 255u, m1, thr),
+           vae_input_masked_of(w1 >> 24, m2, thr), vae_input_masked_of((w2 >> 16) & 255u, m3, thr));
+  st4<Tag>(out, 2 * HW + p, vae_input_masked_of((w0 >> 16) & 255u, m0, thr), vae_input_masked_of((w1 >> 8) & 255u, m1, thr),
+           vae_input_masked_of(w2 & 255u, m2, thr), vae_input_masked_of(w2 >> 24, m3, thr));
+}
+
+template <typename Tag>
+__global__ void __launch_bounds__(ED_BLOCK)
+k_u8_to_vae_input_masked(const uint8_t* __restrict__ img, const uint8_t* __restrict__ mask, uint32_t thr, void* __restrict__ out,
+                         int64_t HW) {
+  int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
+  if (t >= 3 * HW) return;
+  int64_t c = t / HW, p = t - c * HW;
+  st<Tag>(out, t, vae_input_masked_of(img[3 * p + c], mask[p], thr));
+}
+
 // ed_img2img_init: z0 = (mean + std * eps) * sf, x = a * z0 + b * noise
 __device__ __forceinline__ void img2img_one(float m, float s, float e, float nz, float sf, float a, float b, float& z, float& x) {
   z = __fmul_rn(__fadd_rn(m, __fmul_rn(s, e)), sf);
@@ -1176,6 +1266,47 @@ int ed_assemble_rows(const float* latent, int B, int C, int H, int W, const uint
     default: return (int)hipErrorInvalidValue;
   }
 #undef ED_ASM
+  return done();
+}
+
+int ed_assemble_rows_x(const float* latent, int B, int C, int H, int W, const uint8_t* idx, const int32_t* src_row,
+                       const int32_t* src_col, const float* gframe, void* g_rows, float* low, int K, int h, int w, int gPH,
+                       int gPW, int g_off_y, int g_off_x, const int32_t* win_y0, const int32_t* win_x0,
+                       const float* vframe, void* v_rows, int V, int Sh, int Sw, int vPH, int vPW, int v_off_y, int v_off_x,
+                       int dtype, const float* extra, int E, const float* pad_value, void* stream) {
+  if (!extra || !pad_value || E < 1 || C < 1 || B < 0 || K < 0 || V < 0 || H < 1 || W < 1 || h < 0 || w < 0 || Sh < 0 || Sw < 0 ||
+      g_off_y < 0 || g_off_x < 0 || g_off_y + h > gPH || g_off_x + w > gPW || v_off_y < 0 || v_off_x < 0 || v_off_y + Sh > vPH ||
+      v_off_x + Sw > vPW)
+    return (int)hipErrorInvalidValue;
+  int64_t n_g = (int64_t)K * B * (C + E) * gPH * gPW, n_v = (int64_t)V * B * (C + E) * vPH * vPW;
+  if (n_g + n_v == 0) return 0;
+  // the extras are read one element at a time in both forms, so `extra` carries no alignment condition
+  bool px4 = (gPW & 3) == 0 && (w & 3) == 0 && (g_off_x & 3) == 0 && aligned16(g_rows) && aligned16(idx) &&
+             (!gframe || aligned16(gframe)) && (!low || aligned16(low));
+  bool gx4 = (vPW & 3) == 0 && (Sw & 3) == 0 && (v_off_x & 3) == 0 && aligned16(v_rows) && (!vframe || aligned16(vframe));
+  AssembleArgsX a;
+  a.latent = latent, a.B = B, a.C = C, a.H = H, a.W = W;
+  a.idx = idx, a.src_row = src_row, a.src_col = src_col, a.gframe = gframe, a.g_out = g_rows, a.low = low;
+  a.K = K, a.h = h, a.w = w, a.gPH = gPH, a.gPW = gPW, a.g_off_y = g_off_y, a.g_off_x = g_off_x;
+  a.win_y0 = win_y0, a.win_x0 = win_x0, a.vframe = vframe, a.v_out = v_rows;
+  a.V = V, a.Sh = Sh, a.Sw = Sw, a.vPH = vPH, a.vPW = vPW, a.v_off_y = v_off_y, a.v_off_x = v_off_x;
+  a.extra = extra, a.pad_value = pad_value, a.E = E;
+  a.pick_blocks = n_g ? grid_for(px4 ? n_g >> 2 : n_g) : 0;
+  int view_blocks = n_v ? grid_for(gx4 ? n_v >> 2 : n_v) : 0;
+  dim3 grid(a.pick_blocks + view_blocks), block(ED_BLOCK);
+  hipStream_t st_ = (hipStream_t)stream;
+#define ED_ASM_X(T)                                                              \
+  if (px4 && gx4) k_assemble_rows_x<T, true, true><<<grid, block, 0, st_>>>(a);  \
+  else if (px4) k_assemble_rows_x<T, true, false><<<grid, block, 0, st_>>>(a);   \
+  else if (gx4) k_assemble_rows_x<T, false, true><<<grid, block, 0, st_>>>(a);   \
+  else k_assemble_rows_x<T, false, false><<<grid, block, 0, st_>>>(a);
+  switch (dtype) {
+    case ED_F32: ED_ASM_X(F32) break;
+    case ED_F16: ED_ASM_X(F16) break;
+    case ED_BF16: ED_ASM_X(BF16) break;
+    default: return (int)hipErrorInvalidValue;
+  }
+#undef ED_ASM_X
   return done();
 }
 
@@ -1502,6 +1633,20 @@ int ed_u8_to_vae_input(const uint8_t* img, int H, int W, void* out, int dtype, v
     ED_LAUNCH_T(dtype, k_u8_to_vae_input_x4, HW >> 2, (const uint32_t*)img, out, HW);
   } else {
     ED_LAUNCH_T(dtype, k_u8_to_vae_input, 3 * HW, img, out, HW);
+  }
+  return done();
+}
+
+int ed_u8_to_vae_input_masked(const uint8_t* img, const uint8_t* mask, int threshold, int H, int W, void* out, int dtype,
+                              void* stream) {
+  if (!img || !mask || !out || H < 0 || W < 0 || threshold < 1 || threshold > 255) return (int)hipErrorInvalidValue;
+  int64_t HW = (int64_t)H * W;
+  if (HW == 0) return 0;
+  if ((HW & 3) == 0 && (((uintptr_t)img) & 3u) == 0 && (((uintptr_t)mask) & 3u) == 0 && aligned16(out)) {
+    ED_LAUNCH_T(dtype, k_u8_to_vae_input_masked_x4, HW >> 2, (const uint32_t*)img, (const uint32_t*)mask, (uint32_t)threshold, out,
+                HW);
+  } else {
+    ED_LAUNCH_T(dtype, k_u8_to_vae_input_masked, 3 * HW, img, mask, (uint32_t)threshold, out, HW);
   }
   return done();
 }

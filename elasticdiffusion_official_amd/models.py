@@ -766,6 +766,22 @@ SMALL_UNET_CONFIGS = {
 }
 SMALL_VAE_CHANNELS = (32, 64, 64, 64)
 
+# Inpainting checkpoints (stable-diffusion-inpainting, stable-diffusion-2-inpainting, stable-diffusion-xl-1.0-inpainting-0.1): the
+# same architectures with a 9-channel ``conv_in`` -- noisy latent (4) | latent mask (1) | masked-image latent (4), DESIGN.md section
+# 22.  Only conv_in's input width differs, so every dispatch rule above applies unchanged (conv_in is library work at either width).
+INPAINT_IN_CHANNELS = 9
+INPAINT_SUFFIX = "-inpaint"
+
+
+def unet_config(fam, small=False, in_channels=4):
+    """The UNet configuration of a family at full or reduced width, with 4 (text-to-image) or 9 (inpainting) input channels."""
+    if in_channels not in (4, INPAINT_IN_CHANNELS):
+        raise ValueError(f"in_channels must be 4 or {INPAINT_IN_CHANNELS} (an inpainting checkpoint), got {in_channels}")
+    table = SMALL_UNET_CONFIGS if small else UNET_CONFIGS
+    if fam not in table:
+        raise ValueError(f"no {'reduced-width ' if small else ''}architecture for family {fam!r}")
+    return dict(table[fam], in_channels=in_channels)
+
 
 class _DownBlock(nn.Module):
     def __init__(self, cin, cout, temb, layers, attn, heads, depth, cross, linear, downsample):
@@ -825,7 +841,7 @@ class UNet2DConditionModel(nn.Module):
         super().__init__()
         boc = tuple(block_out_channels)
         temb = boc[0] * 4
-        self.config = SimpleNamespace(sample_size=sample_size, in_channels=in_channels, block_out_channels=boc,
+        self.config = SimpleNamespace(sample_size=sample_size, in_channels=in_channels, out_channels=out_channels, block_out_channels=boc,
                                       cross_attention_dim=cross_attention_dim,
                                       addition_time_embed_dim=addition_time_embed_dim,
                                       pooled_projection_dim=pooled_projection_dim)
@@ -1119,7 +1135,14 @@ class AutoencoderKL(nn.Module):
 
 
 # ---------------------------------------------------------------------------------------------------
+def is_inpaint_version(sd_version):
+    """``"1.5-inpaint"`` / ``"2.0-inpaint"`` / ``"XL1.0-inpaint"``: the 9-channel variant of that ``sd_version``"""
+    return sd_version.endswith(INPAINT_SUFFIX)
+
+
 def family(sd_version):
+    if is_inpaint_version(sd_version):
+        sd_version = sd_version[:-len(INPAINT_SUFFIX)]
     if sd_version.startswith("XL"):
         return "sdxl"
     if sd_version in ("2.0", "2.1"):
@@ -1139,6 +1162,20 @@ def _seeded_init(module, seed):
         for m in module.modules():
             if hasattr(m, "reset_parameters"):
                 m.reset_parameters()
+
+
+def state_dict_in_channels(state_dict):
+    """Input channels of the UNet a state dict belongs to, read off the SHAPE of ``conv_in.weight`` [C_out, C_in, 3, 3] (not off any
+    ``config.json``); None when the tensor is absent."""
+    w = state_dict.get("conv_in.weight")
+    return None if w is None else int(w.shape[1])
+
+
+def snapshot_in_channels(path):
+    """``state_dict_in_channels`` of a ``diffusion_pytorch_model.safetensors`` without loading its tensors"""
+    from safetensors import safe_open
+    with safe_open(path, framework="pt") as f:
+        return int(f.get_slice("conv_in.weight").get_shape()[1]) if "conv_in.weight" in f.keys() else None
 
 
 def load_weights(module, path):
@@ -1163,15 +1200,23 @@ def build_models(sd_version, device="cuda", dtype=None, weights=None, vae_dtype=
     """(unet, vae[, controlnet]) for the reference's ``sd_version`` keys (ED:128-141).  UNet/ControlNet run in
     DEFAULT_MODEL_DTYPE (fp16) unless ``dtype`` says otherwise; the VAE stays fp32 like the reference (its decode runs
     outside autocast, ED:1080-1121, and the encoder is explicitly kept out of autocast, ED:328).  ``small=True`` builds the
-    reduced-width variants (parity checks)."""
+    reduced-width variants (parity checks).  ``"1.5-inpaint"`` / ``"2.0-inpaint"`` / ``"XL1.0-inpaint"``, or a ``weights`` snapshot
+    whose ``conv_in.weight`` has 9 input channels, build the 9-channel inpainting UNet of the family."""
     fam = family(sd_version)
-    cfg = (SMALL_UNET_CONFIGS if small else UNET_CONFIGS)[fam]
+    in_channels = INPAINT_IN_CHANNELS if is_inpaint_version(sd_version) else 4
+    unet_file = os.path.join(weights, "unet", "diffusion_pytorch_model.safetensors") if weights else None
+    if unet_file and os.path.isfile(unet_file):
+        # an inpainting snapshot selects the 9-channel variant by itself: the width of its conv_in decides, whatever the name says
+        in_channels = snapshot_in_channels(unet_file) or in_channels
+    cfg = unet_config(fam, small, in_channels)
+    # the ControlNet keeps the 4-channel configuration (a 9-channel UNet with a ControlNet is refused by the pipeline)
+    cn_cfg = unet_config(fam, small, 4)
     dtype = dtype or DEFAULT_MODEL_DTYPE
     with torch.device("meta"):
         unet = UNet2DConditionModel(**cfg)
         vae_kw = dict(block_out_channels=SMALL_VAE_CHANNELS) if small else {}
         vae = AutoencoderKL(scaling_factor=0.13025 if fam == "sdxl" else 0.18215, force_upcast=(fam == "sdxl"), **vae_kw)
-        cn = ControlNetModel(cfg) if controlnet else None
+        cn = ControlNetModel(cn_cfg) if controlnet else None
     out = []
     for k, (m, dt, sub) in enumerate([(unet, dtype, "unet"), (vae, vae_dtype, "vae"), (cn, dtype, "controlnet")]):
         if m is None:

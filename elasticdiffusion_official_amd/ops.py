@@ -191,6 +191,47 @@ def assemble_rows(latent, idx, src_row, src_col, g_rows, h, w, g_off_y, g_off_x,
           _dev(v_rows, None, "v_rows"), V, Sh, Sw, vPH, vPW, v_off_y, v_off_x, _code(g_rows, "g_rows"), _stream())
 
 
+def assemble_rows_x(latent, idx, src_row, src_col, g_rows, h, w, g_off_y, g_off_x, gframe, low, v_rows, win_y0, win_x0, Sh,
+                    Sw, v_off_y, v_off_x, vframe, extra, pad_value):
+    """``assemble_rows`` for model rows of C + E channels (see ed_assemble_rows_x): ``extra`` f32 [B,E,H,W] goes through the index
+    map of each row's latent into channels C.., ``pad_value`` f32 [E] (device) fills them where the latent reads the frame.
+    g_rows [(K*2*B),C+E,gPH,gPW], v_rows [(V*B),C+E,vPH,vPW]; ``low`` stays [K,B,C,h,w]."""
+    if not isinstance(latent, torch.Tensor) or latent.dim() != 4:
+        _reject(f"assemble_rows_x: latent must be an f32 [B,C,H,W] tensor on the MI355X; no CPU fallback (got "
+                f"{tuple(getattr(latent, 'shape', ()))})")
+    B, C, H, W = latent.shape
+    if not isinstance(extra, torch.Tensor) or extra.dim() != 4 or extra.shape[1] < 1 or \
+            (extra.shape[0], extra.shape[2], extra.shape[3]) != (B, H, W):
+        _reject(f"assemble_rows_x: extra must be f32 [{B},E,{H},{W}] with E >= 1, got {tuple(getattr(extra, 'shape', ()))}")
+    E = int(extra.shape[1])
+    if not isinstance(pad_value, torch.Tensor) or tuple(pad_value.shape) != (E,):
+        _reject(f"assemble_rows_x: pad_value must be an f32 [{E}] device tensor, got {tuple(getattr(pad_value, 'shape', ()))}")
+    K, V = idx.shape[0], win_y0.numel()
+    gr, C2, gPH, gPW = g_rows.shape
+    vr, C3, vPH, vPW = v_rows.shape
+    if not (gr == K * 2 * B and vr == V * B and C2 == C + E == C3 and g_rows.dtype == v_rows.dtype):
+        _reject(f"assemble_rows_x: rows must be [{K * 2 * B},{C + E},..] and [{V * B},{C + E},..] of one dtype, got "
+                f"{tuple(g_rows.shape)} {g_rows.dtype} / {tuple(v_rows.shape)} {v_rows.dtype}")
+    assert idx.shape[1] == h * w and src_row.numel() == 2 * h and src_col.numel() == 2 * w and win_x0.numel() == V
+    assert g_off_y + h <= gPH and g_off_x + w <= gPW and v_off_y + Sh <= vPH and v_off_x + Sw <= vPW
+    if gframe is not None:
+        assert tuple(gframe.shape) == (C, gPH, gPW)
+    if vframe is not None:
+        assert tuple(vframe.shape) == (C, vPH, vPW)
+    if low is not None:
+        assert tuple(low.shape) == (K, B, C, h, w)
+    _call("ed_assemble_rows_x", _dev(latent, torch.float32, "latent"), B, C, H, W, _dev(idx, torch.uint8, "idx"),
+          _dev(src_row, torch.int32), _dev(src_col, torch.int32), _opt(gframe, torch.float32, "gframe"),
+          _dev(g_rows, None, "g_rows"), _opt(low, torch.float32, "low"), K, h, w, gPH, gPW, g_off_y, g_off_x,
+          _dev(win_y0, torch.int32), _dev(win_x0, torch.int32), _opt(vframe, torch.float32, "vframe"),
+          _dev(v_rows, None, "v_rows"), V, Sh, Sw, vPH, vPW, v_off_y, v_off_x, _code(g_rows, "g_rows"),
+          _dev(extra, torch.float32, "extra"), E, _dev(pad_value, torch.float32, "pad_value"), _stream())
+    # algorithmic bytes: every row element written once, one fp32 read per element, the picks and `low`
+    n_rows = (gr * gPH * gPW + vr * vPH * vPW) * (C + E)
+    TIMER.note_work("ed_assemble_rows_x", nbytes=float(n_rows * g_rows.element_size() + 4 * (n_rows - gr * gPH * gPW * (C + E) // 2)
+                                                       + K * h * w + (0 if low is None else 4 * low.numel())))
+
+
 PREDICTION_TYPES = {"epsilon": 0, "v_prediction": 1}  # ED_PRED_EPSILON / ED_PRED_V
 
 
@@ -1377,6 +1418,31 @@ def u8_to_vae_input(img, dtype=torch.float32):
     out = torch.empty((1, 3, H, W), dtype=dtype, device=img.device)
     _call("ed_u8_to_vae_input", p_img, H, W, _dev(out, dtype, "out"), _DTYPE[dtype], _stream())
     TIMER.note_work("ed_u8_to_vae_input", nbytes=float(3 * H * W * (1 + out.element_size())))
+    return out
+
+
+def u8_to_vae_input_masked(img, mask, dtype=torch.float32, threshold=128):
+    """``u8_to_vae_input`` with the hole blanked: exactly +0.0 where ``mask`` uint8 [H,W] is >= ``threshold``, 2 * (v / 255) - 1
+    elsewhere -> [1,3,H,W] of ``dtype``; what the masked-image latent of a 9-channel inpainting UNet is encoded from.
+    See ed_u8_to_vae_input_masked."""
+    p_img = _dev(img, torch.uint8, "img")
+    if img.dim() != 3 or img.shape[2] != 3:
+        _reject(f"img must be uint8 [H,W,3], got {tuple(img.shape)}")
+    H, W = int(img.shape[0]), int(img.shape[1])
+    if not (1 <= H <= VAE_INPUT_MAX_DIM and 1 <= W <= VAE_INPUT_MAX_DIM):
+        _reject(f"img: H and W must be in 1..{VAE_INPUT_MAX_DIM}, got {H} x {W}")
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or tuple(mask.shape) != (H, W):
+        _reject(f"u8_to_vae_input_masked: mask must be uint8 [{H},{W}], got {getattr(mask, 'dtype', type(mask).__name__)} "
+                f"{tuple(getattr(mask, 'shape', ()))}")
+    threshold = int(threshold)
+    if not 1 <= threshold <= 255:
+        _reject(f"u8_to_vae_input_masked: threshold must be in 1..255, got {threshold}")
+    if dtype not in _DTYPE:
+        _reject(f"u8_to_vae_input_masked: unsupported dtype {dtype}")
+    out = torch.empty((1, 3, H, W), dtype=dtype, device=img.device)
+    _call("ed_u8_to_vae_input_masked", p_img, _dev(mask, torch.uint8, "mask"), threshold, H, W, _dev(out, dtype, "out"),
+          _DTYPE[dtype], _stream())
+    TIMER.note_work("ed_u8_to_vae_input_masked", nbytes=float(H * W * (4 + 3 * out.element_size())))
     return out
 
 

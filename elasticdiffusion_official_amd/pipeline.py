@@ -4,7 +4,8 @@ elastic_diffusion_w_controlnet.py): same constructor and ``generate_image`` surf
 reference's CPU path, but one image is a *program* (a generator, ``_program``) whose timestep is
 
     host   : pick-index draws (torch CPU generator, ED:501-544) + pad-strip reseed replay (ED:359)   -- no device sync
-    HIP    : ed_assemble_rows       -> ONE model-input batch: K CFG pairs + V views (all d x d)
+    HIP    : ed_assemble_rows       -> ONE model-input batch: K CFG pairs + V views (all d x d); ed_assemble_rows_x when the UNet
+                                       is a 9-channel inpainting model (mask + masked-image latent behind every row's latent)
     yield  : ONE UNet forward for the whole batch (hipGraph replay; rows optionally sharded over ranks and all-gathered
              over RCCL; with several images in flight the rows of all pending calls are fused, per-row timesteps)
     HIP    : ed_phase_epilogue      -> unpad, fill, scatter, CFG + DDIM [, RRG] in one launch
@@ -99,6 +100,34 @@ def check_img2img_arguments(num_inference_steps, init_image=None, strength=1.0, 
 
 
 MASK_MODES = ("binary", "graded")
+
+# Input channels of an inpainting UNet: noisy latent (4) | latent mask (1) | masked-image latent (4)
+INPAINT_IN_CHANNELS = 9
+
+
+def check_inpaint_unet_arguments(in_channels, init_image=None, mask_image=None, mask_mode="binary", controlnet=False,
+                                 latent_size=None):
+    """The argument rules of a 9-channel inpainting UNet, pure host code that runs before anything is
+    launched -> is this the 9-channel path?  ValueError: ``in_channels`` other than 4 or 9; with 9, a run without both
+    ``init_image`` and ``mask_image``, ``mask_mode="graded"``, a ControlNet, or pictures that are not 8-bit (the hole is blanked in
+    the init picture's bytes through the pixel mask: a float ``init_image`` or a mask at latent resolution carries neither)."""
+    if in_channels == 4:
+        return False
+    if in_channels != INPAINT_IN_CHANNELS:
+        raise ValueError(f"unet.config.in_channels must be 4 or {INPAINT_IN_CHANNELS} (an inpainting UNet), got {in_channels!r}")
+    if controlnet:
+        raise ValueError("a 9-channel inpainting UNet with a ControlNet is not supported")
+    if init_image is None or mask_image is None:
+        raise ValueError("a 9-channel inpainting UNet needs both init_image and mask_image (its extra input channels are the "
+                         "mask and the encoding of the picture with the hole blanked)")
+    if mask_mode == "graded":
+        raise ValueError('mask_mode="graded" is not supported with a 9-channel inpainting UNet (there is no blend to release)')
+    at_latent_size = (isinstance(mask_image, torch.Tensor) and mask_image.dtype in (torch.bool, torch.uint8)
+                      and latent_size is not None and tuple(mask_image.shape) == tuple(latent_size))
+    if not _is_8bit_picture(init_image, 3) or not _is_8bit_picture(mask_image, 1) or at_latent_size:
+        raise ValueError("a 9-channel inpainting UNet needs an 8-bit init_image (RGB PIL image, uint8 [H,W,3]) and an 8-bit "
+                         "picture mask_image (L PIL image, uint8 [H,W]) at pixel resolution")
+    return True
 
 
 def _is_8bit_picture(image, channels):
@@ -318,6 +347,7 @@ class ElasticDiffusion(nn.Module):
         self.last_init_latents = None  # z0 of the last image started with ``init_image`` (its encoded, scaled latent)
         self.last_init_pixels = None   # uint8 [height,width,3]: the (resized) 8-bit init picture of the last such image, on the device
         self.last_pixel_mask = None    # uint8 [height,width]: its (resized, blurred) 8-bit picture mask, on the device
+        self.last_masked_image_latents = None  # zm of the last image on a 9-channel UNet (the blanked picture's scaled latent)
 
     @staticmethod
     def _model_layout(module):
@@ -553,15 +583,18 @@ class ElasticDiffusion(nn.Module):
 
     # ---- one estimation phase (ED:1016-1035 or ED:1043-1056) ---------------------------------------
     def _phase_steps(self, P, x, ti, K, g, drop_p, emb, cond=None, direct=True, rrg_w=None, rrg_norm=0.0, frames=None,
-                     rescale=None):
+                     rescale=None, extras=None):
         """Generator: pre-model glue -> ``yield _ModelCall`` (receives the model output rows) -> post-model glue;
         returns (prev, x0, info).  ``direct``: assemble straight into the hipGraph's static input (one image in flight,
         one rank); otherwise into a scratch batch the driver concatenates / the sharder slices.  ``rrg_w``: this is the
         last phase of a timestep with Reduced-Resolution Guidance active -- with FUSED_GLUE the epilogue then also
         produces info["x_next"] = prev + RRG term (ED:1061-1078).  ``rescale`` (a ``_Rescale``): the guided model output is
         std-rescaled before the DDIM update -- one moments reduction over the same rows, then the rescale-aware kernels;
-        with ``rrg_w`` the reduced-resolution pair gets its own ratio (info["ratio_low"])."""
+        with ``rrg_w`` the reduced-resolution pair gets its own ratio (info["ratio_low"]).  ``extras`` = (extra [B,E,Hl,Wl],
+        pad_value [E]) on a 9-channel inpainting UNet: the model rows carry C + E channels, the extra ones registered to each row's
+        latent (``ops.assemble_rows_x``); everything after the model call is unchanged."""
         B, C = x.shape[:2]
+        CR = C if extras is None else C + extras[0].shape[1]  # channels of a model INPUT row
         dev, mdt = self.device, self.model_dtype
         n_g, n_v = 2 * K * B, P.views.V * B
         # host draws first (they never wait for the GPU)
@@ -582,14 +615,20 @@ class ElasticDiffusion(nn.Module):
         low = torch.empty(K, B, C, P.h, P.w, device=dev, dtype=torch.float32)
         direct = direct and P.one_batch and self.sharder.world_size == 1
         if P.one_batch:
-            shape = (n_g + n_v, C, P.gpad.PH, P.gpad.PW)
+            shape = (n_g + n_v, CR, P.gpad.PH, P.gpad.PW)
             rows = (self._runner.input_rows(shape, mdt, dev, None if cond is None else cond[K], *emb[K]) if direct
                     else torch.empty(shape, device=dev, dtype=mdt))
             g_rows, v_rows = rows[:n_g], rows[n_g:]
         else:
-            g_rows = torch.empty(n_g, C, P.gpad.PH, P.gpad.PW, device=dev, dtype=mdt)
-            v_rows = torch.empty(n_v, C, P.vpad.PH, P.vpad.PW, device=dev, dtype=mdt)
-        if FUSED_GLUE:
+            g_rows = torch.empty(n_g, CR, P.gpad.PH, P.gpad.PW, device=dev, dtype=mdt)
+            v_rows = torch.empty(n_v, CR, P.vpad.PH, P.vpad.PW, device=dev, dtype=mdt)
+        if extras is not None:
+            if FUSED_GLUE:
+                ops.assemble_rows_x(x, idx, P.src_row, P.src_col, g_rows, P.h, P.w, P.gpad.top, P.gpad.left, gframe, low,
+                                    v_rows, P.win_y0, P.win_x0, P.views.Sh, P.views.Sw, P.vpad.top, P.vpad.left, vframe, *extras)
+            else:
+                self._assemble_unfused_x(P, x, idx, K, g_rows, v_rows, gframe, vframe, low, *extras)
+        elif FUSED_GLUE:
             ops.assemble_rows(x, idx, P.src_row, P.src_col, g_rows, P.h, P.w, P.gpad.top, P.gpad.left, gframe, low,
                               v_rows, P.win_y0, P.win_x0, P.views.Sh, P.views.Sw, P.vpad.top, P.vpad.left, vframe)
         else:
@@ -753,7 +792,7 @@ class ElasticDiffusion(nn.Module):
         self.last_init_pixels = u8
         return ops.u8_to_vae_input(u8, vdt), (src if src != (height, width) else None)
 
-    def _latent_mask(self, mask, height, width, resized_from=None, mask_blur=0.0, graded=False):
+    def _latent_mask(self, mask, height, width, resized_from=None, mask_blur=0.0, graded=False, raw=None):
         """``mask_image`` -> uint8 (Hl, Wl) on the device, 1 = repaint, 0 = keep; with ``graded`` the level map instead, the
         sampled byte itself (a uint8 tensor at latent resolution is the level map, a bool one 0 / 255).  The 8-bit picture mask
         at height x width, blurred by ``ops.gaussian_blur_u8`` when ``mask_blur`` > 0 (Pillow's ``GaussianBlur`` bytes), is
@@ -761,7 +800,9 @@ class ElasticDiffusion(nn.Module):
         (Hl, Wl) is taken as the latent mask (non-zero = repaint); an 8-bit picture (L PIL image, uint8 [H,W] / [H,W,1]) of
         height x width is sampled at the top-left pixel of every latent cell and compared with 128 (torch's nearest
         ``interpolate`` of the mask binarised at 0.5).  A picture that has the size ``resized_from`` of an init image that
-        was resized is first resized on the HOST with PIL's NEAREST filter -- a rare path, one pass over the mask's bytes."""
+        was resized is first resized on the HOST with PIL's NEAREST filter -- a rare path, one pass over the mask's bytes.
+        ``raw``: a list that receives the picture mask at height x width BEFORE the blur (what a 9-channel UNet's masked image is
+        blanked through)."""
         s = self.vae_scale_factor
         Hl, Wl = height // s, width // s
         self.last_pixel_mask = None
@@ -786,6 +827,8 @@ class ElasticDiffusion(nn.Module):
             u8 = torch.from_numpy(np.ascontiguousarray(u8))
         u8 = u8.to(self.device).contiguous()
         u8 = u8.view(u8.shape[0], u8.shape[1])       # [H,W,1] from ``_u8_image``, [H,W] from the host resize
+        if raw is not None:
+            raw.append(u8)
         if mask_blur > 0:
             u8 = ops.gaussian_blur_u8(u8, mask_blur)
         self.last_pixel_mask = u8
@@ -793,8 +836,11 @@ class ElasticDiffusion(nn.Module):
 
     def _img2img_start(self, S, B, init_image, mask_image, mask_blur=0.0, graded=False):
         """The initial latent of an image-to-image run: encode, sample the posterior, noise to the first executed timestep.
-        Host RNG order: posterior noise, then the initial noise, both (B,C,Hl,Wl) fp32.  -> (x, z0, noise, latent mask | None)"""
+        Host RNG order: posterior noise, then the initial noise, both (B,C,Hl,Wl) fp32.  -> (x, z0, noise, latent mask | None)
+        On a 9-channel UNet (``S.inpaint9``) the unblurred picture mask is kept as ``self._raw_pixel_mask`` for
+        ``_inpaint9_extras``, which draws next."""
         P = S.P
+        raw = [] if getattr(S, "inpaint9", False) else None
         s = self.vae_scale_factor
         pix, resized_from = self._init_pixels(init_image, P.Hl * s, P.Wl * s)
         if pix.shape[0] not in (1, B):
@@ -802,7 +848,8 @@ class ElasticDiffusion(nn.Module):
         mask = None
         self.last_pixel_mask = None
         if mask_image is not None:
-            mask = self._latent_mask(mask_image, P.Hl * s, P.Wl * s, resized_from, mask_blur, graded)
+            mask = self._latent_mask(mask_image, P.Hl * s, P.Wl * s, resized_from, mask_blur, graded, raw)
+        self._raw_pixel_mask = raw[0] if raw else None
         dist = self.vae.encode(pix).latent_dist
         shape = (B, S.C, P.Hl, P.Wl)
         if tuple(dist.mean.shape[1:]) != shape[1:]:
@@ -820,6 +867,55 @@ class ElasticDiffusion(nn.Module):
         z0, x = ops.img2img_init(mean, std, eps, noise, self.vae.config.scaling_factor, a, b)
         return x, z0, noise, mask
 
+    def _inpaint9_extras(self, S, B, mask):
+        """The five extra input channels of a 9-channel inpainting UNet -> (extra f32 [B,5,Hl,Wl],
+        pad_value f32 [5]): the latent mask as 0.0 / 1.0 (1 = repaint; after ``mask_blur``) and zm, the scaled posterior sample
+        of the init picture with the hole blanked through the UNBLURRED pixel mask.  One host draw (1,C,Hl,Wl), taken after
+        ``_img2img_start``'s two, broadcast over the prompts.  Once per image: two launches and one VAE encode."""
+        P = S.P
+        vdt = next(self.vae.parameters()).dtype
+        masked = ops.u8_to_vae_input_masked(self.last_init_pixels, self._raw_pixel_mask, vdt, 128)
+        self._raw_pixel_mask = None
+        dist = self.vae.encode(masked).latent_dist
+        shape = (1, S.C, P.Hl, P.Wl)
+        if tuple(dist.mean.shape) != shape:
+            raise ValueError(f"the VAE encodes the masked image to {tuple(dist.mean.shape)}, the loop runs on {shape}")
+        h0 = time.perf_counter()
+        eps_host = self._stager.host(shape, torch.float32)
+        eps_host.normal_()
+        self.host_s["noise"] += time.perf_counter() - h0
+        eps = self._stager.upload(eps_host, self.device)
+        # ed_img2img_init's z0 output alone is (mean + std * eps) * sf, the restatement's expression; its x output is not used
+        zm, _ = ops.img2img_init(dist.mean.contiguous(), dist.std.contiguous(), eps, eps, self.vae.config.scaling_factor, 1.0, 0.0)
+        self.last_masked_image_latents = zm
+        extra = torch.cat([mask.to(torch.float32).view(1, 1, P.Hl, P.Wl).expand(B, -1, -1, -1), zm.expand(B, -1, -1, -1)], dim=1)
+        pad_value = torch.tensor([1.0] + [0.0] * S.C, dtype=torch.float32).to(self.device)
+        return extra.contiguous(), pad_value
+
+    def _assemble_unfused_x(self, P, x, idx, K, g_rows, v_rows, gframe, vframe, low, extra, pad_value):
+        """``FUSED_GLUE`` off on a 9-channel UNet: the latent channels through ed_pick_assemble / ed_gather_views as always, the
+        extra channels by torch indexing from the same tables -- bit-equal to ``ops.assemble_rows_x`` (a gather and one rounding)."""
+        B, C = x.shape[:2]
+        E = extra.shape[1]
+        mdt = g_rows.dtype
+        g4 = torch.empty(g_rows.shape[0], C, P.gpad.PH, P.gpad.PW, device=x.device, dtype=mdt)
+        v4 = torch.empty(v_rows.shape[0], C, P.vpad.PH, P.vpad.PW, device=x.device, dtype=mdt)
+        ops.pick_assemble(x, idx, P.src_row, P.src_col, g4, P.h, P.w, P.gpad.top, P.gpad.left, gframe, low)
+        ops.gather_views(x, v4, P.win_y0, P.win_x0, P.views.Sh, P.views.Sw, P.vpad.top, P.vpad.left, vframe)
+        pad = pad_value.to(mdt).view(1, E, 1, 1)
+        g_rows[:, :C], v_rows[:, :C] = g4, v4
+        g_rows[:, C:], v_rows[:, C:] = pad, pad
+        q = idx.view(K, P.h, P.w).long()
+        sy = P.src_row.long()[2 * torch.arange(P.h, device=x.device).view(1, -1, 1) + (q >> 1)]     # [K,h,w]
+        sx = P.src_col.long()[2 * torch.arange(P.w, device=x.device).view(1, 1, -1) + (q & 1)]
+        picked = extra[:, :, sy, sx].permute(2, 0, 1, 3, 4).to(mdt)                                  # [K,B,E,h,w]
+        top, left = P.gpad.top, P.gpad.left
+        g_rows.view(K, 2, B, C + E, P.gpad.PH, P.gpad.PW)[:, :, :, C:, top:top + P.h, left:left + P.w] = picked[:, None]
+        top, left, Sh, Sw = P.vpad.top, P.vpad.left, P.views.Sh, P.views.Sw
+        vr = v_rows.view(P.views.V, B, C + E, P.vpad.PH, P.vpad.PW)
+        for v, (y0, x0) in enumerate(zip(P.views.win_y0, P.views.win_x0)):
+            vr[v, :, C:, top:top + Sh, left:left + Sw] = extra[:, :, int(y0):int(y0) + Sh, int(x0):int(x0) + Sw].to(mdt)
+
     def _blend_known(self, S, x, mask, z0, noise, j, graded=False):
         """x <- where(mask, x, known(j)) in place: the kept region of the init image at the noise level of timestep index ``j``
         (the SAME initial noise at every step), the clean z0 after the last one.  ``graded``: ``mask`` is the level map and a
@@ -836,12 +932,19 @@ class ElasticDiffusion(nn.Module):
         a, b = self.scheduler.add_noise_coefficients(self._timesteps[j])
         return ops.inpaint_blend(x, mask, z0, noise, a, b)
 
+    def _check_inpaint9(self, height, width, init_image=None, mask_image=None, mask_mode="binary"):
+        """``check_inpaint_unet_arguments`` for this pipeline's UNet and ControlNet at a run's size"""
+        s = self.vae_scale_factor
+        return check_inpaint_unet_arguments(self.unet.config.in_channels, init_image, mask_image, mask_mode,
+                                            self.controlnet is not None, (height // s, width // s))
+
     # ---- the loop (ED:953-1078) --------------------------------------------------------------------
     def _setup_run(self, height, width, num_inference_steps, guidance_scale, resampling_steps, new_p, rrg_stop_t,
                    rrg_init_weight, rrg_scherduler_cls, cosine_scale, repaint_sampling, controlnet_conditioning_scale,
                    guidance_rescale=0.0, strength=1.0):
         """Everything of one ``generate_image`` call that does not depend on the prompt, the seed or the condition
         image: geometry tables, schedules, the noised pad-background frames.  Shared by all images in flight."""
+        inpaint9 = self.unet.config.in_channels == INPAINT_IN_CHANNELS  # (the callers checked the arguments: _check_inpaint9)
         ops.rescale_coefficients(guidance_rescale)  # ValueError outside [0, 1], before anything is launched
         t_start = DDIMSchedule.img2img_window(num_inference_steps, strength)  # ValueError likewise
         self._mark("start")
@@ -855,7 +958,9 @@ class ElasticDiffusion(nn.Module):
             S.rrg = rrg_scherduler_cls(steps=n_rrg, cosine_scale=cosine_scale, factor=rrg_init_weight)
         else:
             S.rrg = rrg_scherduler_cls(steps=n_rrg, start_val=rrg_init_weight, stop_val=0)
-        S.C = C = self.unet.config.in_channels
+        # the latent has the model's OUTPUT channels everywhere; only the input rows of a 9-channel inpainting UNet are wider
+        S.inpaint9 = inpaint9
+        S.C = C = getattr(self.unet.config, "out_channels", 4) if inpaint9 else self.unet.config.in_channels
         dev = self.device
         ts = self.scheduler.set_timesteps(num_inference_steps)
         S.T = len(ts)
@@ -928,6 +1033,10 @@ class ElasticDiffusion(nn.Module):
         else:
             x, z0, noise0, mask = self._img2img_start(S, B, init_image, mask_image, mask_blur, graded)
         self.last_init_latents = z0
+        extras = None
+        if S.inpaint9:  # the model conditions on the mask and the blanked picture: nothing is pasted back (diffusers' num_channels_unet == 9)
+            extras = self._inpaint9_extras(S, B, mask)
+            mask = None
         emb = {K: self._embed_rows(K, P.views.V, un, co, pun, pco) for K in S.Ks}
         cond = None
         if condition_image is not None:
@@ -944,7 +1053,7 @@ class ElasticDiffusion(nn.Module):
             rrg_w = w_i if w_i > 10 else None  # ED:1061-1062
             two_phase = S.repaint and i < S.T - 1
             prev, x0, info = yield from self._phase_steps(P, x, i, S.R + 1, S.guidance, S.drop_p, emb, cond, direct,
-                                                          None if two_phase else rrg_w, S.norm, frames, rescale)
+                                                          None if two_phase else rrg_w, S.norm, frames, rescale, extras)
             if logs is not None and logs["init_low"] is None:
                 # ED:1023-1024: taken right after the FIRST direction estimate, i.e. before the RePaint phase replaces
                 # ``info`` with the one of the undone sample (ED:1043)
@@ -956,7 +1065,7 @@ class ElasticDiffusion(nn.Module):
                 x = self._undo(prev, i + 1)
                 cfg = S.guidance / 3
                 prev, x0, info = yield from self._phase_steps(P, x, i, 1, cfg, S.drop_p, emb, cond, direct, rrg_w, S.norm,
-                                                              frames, rescale)
+                                                              frames, rescale, extras)
             if logs is not None:  # verbose image logs (ED:1058-1059, 1073-1076)
                 if i % self.log_freq == 0:
                     logs["x0"].append(x0.clone())
@@ -1018,10 +1127,16 @@ class ElasticDiffusion(nn.Module):
         mask and the 8-bit init picture stay on the device as ``last_pixel_mask`` / ``last_init_pixels``.
 
         ``min_chunks`` (keyword-only): encode prompt and negative prompt to at least this many 77-token
-        chunks (a chunking ``text_encoder`` only) -- what a job of ``generate_latents_interleaved`` is encoded with."""
+        chunks (a chunking ``text_encoder`` only) -- what a job of ``generate_latents_interleaved`` is encoded with.
+
+        A UNet with 9 input channels (an inpainting checkpoint) needs an 8-bit ``init_image`` and picture
+        ``mask_image``: every model row is ``cat([latent, mask, masked-image latent])`` with the extras sampled where the row's
+        latent was (``ops.assemble_rows_x``), one more host draw is made for the masked-image latent
+        (``last_masked_image_latents``), and the kept region is NOT pasted back in latent space."""
         check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
         mask_blur = check_soft_inpaint_arguments(init_image, mask_image, mask_blur, mask_mode,
                                                  latent_size=(height // self.vae_scale_factor, width // self.vae_scale_factor))
+        self._check_inpaint9(height, width, init_image, mask_image, mask_mode)
         S = self._setup_run(height, width, num_inference_steps, guidance_scale, resampling_steps, new_p, rrg_stop_t,
                             rrg_init_weight, rrg_scherduler_cls, cosine_scale, repaint_sampling,
                             controlnet_conditioning_scale, guidance_rescale, strength)
@@ -1045,7 +1160,8 @@ class ElasticDiffusion(nn.Module):
 
         ``jobs`` = list of dicts {prompts, negative_prompts="", seed, condition_image=None, init_image=None,
         mask_image=None, mask_blur=0.0, mask_mode="binary"}; ``strength`` is a setting of the call like the other schedule parameters, and jobs with and without
-        an init image may mix (at ``strength`` 1: below it every job needs one).  Each job is one
+        an init image may mix (at ``strength`` 1: below it every job needs one; on a 9-channel inpainting UNet every job carries
+        both ``init_image`` and ``mask_image``).  Each job is one
         ``_program`` with its own host RNG stream (``_HostRng``: exactly the stream ``seed_everything(seed)`` +
         ``generate_latents`` would consume, so every image's latents are those of running it alone, up to the model's
         own batch-shape dependent rounding).  Per tick, the pending model calls of all live programs -- e.g. the 20-row
@@ -1070,6 +1186,7 @@ class ElasticDiffusion(nn.Module):
             check_soft_inpaint_arguments(job.get("init_image"), job.get("mask_image"), job.get("mask_blur", 0.0),
                                          job.get("mask_mode", "binary"),
                                          latent_size=(height // self.vae_scale_factor, width // self.vae_scale_factor))
+            self._check_inpaint9(height, width, job.get("init_image"), job.get("mask_image"), job.get("mask_mode", "binary"))
         S = self._setup_run(height, width, num_inference_steps, guidance_scale, resampling_steps, new_p, rrg_stop_t,
                             rrg_init_weight, rrg_scherduler_cls, cosine_scale, repaint_sampling,
                             controlnet_conditioning_scale, guidance_rescale, strength)
@@ -1169,6 +1286,8 @@ class ElasticDiffusion(nn.Module):
         noise_pred_text = cond, its std ratio computed on the device.
         -> (PIL image of the first sample, {"inter_x0": [pred_original_sample every log_freq steps]})"""
         ops.rescale_coefficients(guidance_rescale)
+        if self.unet.config.in_channels != 4:
+            raise ValueError("generate() drives a 4-channel UNet: a bare latent has no mask or masked-image rows")
         dev, mdt = self.device, self.model_dtype
         x = latent.to(dev, torch.float32).contiguous()
         B, C, h, w = x.shape
@@ -1228,7 +1347,7 @@ class ElasticDiffusion(nn.Module):
             dec = torch.cat([decode_fn(z[k:k + 1]) for z in latents for k in range(len(z))])
             return self._to_pil(_make_grid(dec.clamp(0, 1))[None])[0]
 
-        if logs["init_low"] is not None:
+        if logs["init_low"] is not None and self.unet.config.in_channels == 4:  # (no plain-CFG global image on an inpainting UNet)
             un, co, pun, pco = logs["embeds"]
             image_log["global_img"], info = self.generate(logs["init_low"], torch.cat([un, co]), torch.cat([pun, pco]),
                                                           guidance_scale=guidance_scale, guidance_rescale=guidance_rescale)
@@ -1290,6 +1409,7 @@ class ElasticDiffusion(nn.Module):
         check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
         check_soft_inpaint_arguments(init_image, mask_image, mask_blur, mask_mode, composite, output_type, grid,
                                      latent_size=(height // self.vae_scale_factor, width // self.vae_scale_factor))
+        self._check_inpaint9(height, width, init_image, mask_image, mask_mode)
         z = self.generate_latents(prompts, negative_prompts, height, width, num_inference_steps, guidance_scale,
                                   resampling_steps, new_p, rrg_stop_t, rrg_init_weight, rrg_scherduler_cls,
                                   cosine_scale, repaint_sampling, progress, condition_image,
@@ -1474,6 +1594,7 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
         check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
         check_soft_inpaint_arguments(init_image, mask_image, mask_blur, mask_mode, composite, output_type, grid,
                                      latent_size=(height // self.vae_scale_factor, width // self.vae_scale_factor))
+        self._check_inpaint9(height, width, init_image, mask_image, mask_mode)
         if condition_image is None:
             raise ValueError("condition_image is required (EDC:1183-1193)")
         h, w = self.get_downsample_size(height, width)

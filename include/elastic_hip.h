@@ -316,6 +316,24 @@ int ed_assemble_rows(const float* latent, int B, int C, int H, int W, const uint
                      int dtype, void* stream);
 
 /*
+ * ed_assemble_rows_x -- ed_assemble_rows for a model whose input rows carry E extra channels behind the C latent channels (the
+ * 9-channel inpainting UNets: E = 5, the latent mask and the masked-image latent).  An addition, no
+ * signature change, so still ABI v13.  Arguments as ed_assemble_rows, plus
+ *   extra      f32 [B,E,H,W]  at the latent's resolution; no alignment condition
+ *   pad_value  f32 [E]        (device) what channel C + e holds wherever a latent channel reads the frame (or 0 without one)
+ * g_rows [(K*2*B),C+E,gPH,gPW] and v_rows [(V*B),C+E,vPH,vPW].  Channels 0..C-1 and `low` ([K,B,C,h,w]: the latent channels only)
+ * are bit-identical to ed_assemble_rows; channel C + e is the SAME gather applied to extra[:, e] -- the pick (idx, src_row, src_col) of
+ * that resampling step in a global row, the window (win_y0, win_x0) in a view row -- converted to `dtype` the same way.  One launch;
+ * the 4-wide forms under ed_assemble_rows' conditions, the same bits as the scalar forms.  extra / pad_value NULL, E < 1 or a
+ * window that does not fit its row are hipErrorInvalidValue before any launch.
+ */
+int ed_assemble_rows_x(const float* latent, int B, int C, int H, int W, const uint8_t* idx, const int32_t* src_row,
+                       const int32_t* src_col, const float* gframe, void* g_rows, float* low, int K, int h, int w, int gPH,
+                       int gPW, int g_off_y, int g_off_x, const int32_t* win_y0, const int32_t* win_x0,
+                       const float* vframe, void* v_rows, int V, int Sh, int Sw, int vPH, int vPW, int v_off_y, int v_off_x,
+                       int dtype, const float* extra, int E, const float* pad_value, void* stream);
+
+/*
  * ed_phase_epilogue -- everything between the model call and the next latent in one launch: ed_unpad_direction +
  * ed_fill_directions + ed_scatter_centres + ed_cfg_ddim_step and, when x_next != NULL, ed_rrg_update
  * (ED:429-443, 633-647 x K, 688, 852-861, 1031/1053 + scheduler.step, 886-940 + 1078).  Every output element is a gather
@@ -637,6 +655,16 @@ int ed_img2img_init(const void* mean, const void* std, int dtype, const float* e
 int ed_mask_to_latent(const uint8_t* src, int H, int W, int scale, int threshold, uint8_t* mask, int Hl, int Wl, void* stream);
 int ed_inpaint_blend(const float* x, const uint8_t* mask, const float* z0, const float* noise, float a, float b, int clean,
                      float* out, int planes, int64_t HW, void* stream);
+
+/*
+ * ed_u8_to_vae_input_masked (an addition, still ABI v13) -- the picture with the hole blanked, what a
+ * 9-channel inpainting UNet's masked-image latent is encoded from: ed_u8_to_vae_input where mask[y, x] < threshold, exactly +0.0
+ * where mask[y, x] >= threshold (a select).  img uint8 [H, W, 3], mask uint8 [H, W], threshold in 1..255 (128 = diffusers'
+ * mask < 0.5 on the byte / 255), out [1, 3, H, W] of `dtype`.  4 pixels per thread when H * W % 4 == 0 and the pointers allow it
+ * (img and mask on 4 bytes, out on 16), one element per thread otherwise, the same bits either way.
+ */
+int ed_u8_to_vae_input_masked(const uint8_t* img, const uint8_t* mask, int threshold, int H, int W, void* out, int dtype,
+                              void* stream);
 
 /*
  * ---- soft-edged inpainting (additions, no signature change, so still ABI v13): the mask blurred with

@@ -1,0 +1,473 @@
+"""-m gpu: inpainting with a 9-channel UNet through the HIP path.
+
+Bars:
+  * ``ed_assemble_rows_x`` and ``ed_u8_to_vae_input_masked`` against the plain-gather / torch-CPU restatements of
+    tests/inpaint9_cpu.py: BIT-EXACT, 4-wide and scalar forms alike; channels 0..3 and ``low`` bit-equal to ``ed_assemble_rows``;
+  * end-to-end latents against ``Inpaint9Oracle``: the project's rel-L2 < 1e-4 and an identical host RNG end state (section 18.8);
+    fused and un-fused glue bit-equal to each other; interleaved vs alone 1e-5;
+  * the real reduced-width 9-channel UNet against the fp64 specification: tests/test_sd_spec_gpu.py's bar for the 4-channel model of
+    the same family and dtype (its ``judge``: e_prod <= 1.5 e_spec + 2 ulp), imported, not restated.
+"""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import ddim_variants as V
+from tests import inpaint9_cpu as N
+from tests import sd_spec as S
+from tests.fakes import FakeUNet, FakeVAE, synthetic_text_embeds
+from tests.golden import cases
+from tests.test_hip_parity import DEV, dev_i32, rel_l2
+from tests.test_img2img import half_mask, synthetic_image
+from tests.test_scheduler_variants_gpu import V_TRAILING_ZSNR
+
+pytestmark = pytest.mark.gpu
+
+EPS = dict()
+
+
+def _ops():
+    from elasticdiffusion_official_amd import ops
+    return ops
+
+
+def _misaligned(t):
+    """a device copy of ``t`` that starts one element past a 16-byte boundary"""
+    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=DEV)
+    view = buf[1:].view(t.shape)
+    view.copy_(t)
+    assert view.data_ptr() % 16 != 0 and view.is_contiguous()
+    return view
+
+
+# ---------------------------------------------------------------------------------------------------
+# ed_assemble_rows_x
+# ---------------------------------------------------------------------------------------------------
+GEOMETRIES = {  # Hl, Wl, h, w, model size d
+    "padded": (64, 128, 32, 64, 64),      # the smallest padded geometry of the parity tests: H-pad strips in the global rows; 4-wide forms
+    "no_pad": (64, 64, 64, 64, 64),       # nothing padded, one view
+    "overlap": (67, 97, 44, 64, 64),      # 12 overlapping views, odd latent width (source rows on no alignment), fractional reduction
+    "scalar": (33, 30, 33, 30, 64),       # w = Sw = 30: the scalar forms, pad strips on both axes of both parts
+}
+ROW_CASES = [(1, 3, 5, torch.float32), (2, 1, 5, torch.bfloat16), (1, 1, 1, torch.float16), (2, 3, 5, torch.float16)]   # B, K, E, dtype
+
+
+@pytest.mark.parametrize("B,K,E,dtype", ROW_CASES)
+@pytest.mark.parametrize("geo", list(GEOMETRIES))
+def test_assemble_rows_x_bit_exact(geo, B, K, E, dtype):
+    from elasticdiffusion_official_amd import geometry, host_rng
+    ops = _ops()
+    Hl, Wl, h, w, d = GEOMETRIES[geo]
+    C = 4
+    pp, vp = geometry.PickPlan(Hl, Wl, h, w), geometry.ViewPlan(Hl, Wl, d // 2, d // 2, d // 2)
+    gpad, vpad = geometry.PadPlan(h, w, d), geometry.PadPlan(vp.Sh, vp.Sw, d)
+    assert gpad.padded == (geo in ("padded", "overlap", "scalar")) and vpad.padded == (geo == "scalar")
+    g = torch.Generator().manual_seed(Hl * 131 + Wl + K + E)
+    x = torch.randn(B, C, Hl, Wl, generator=g)
+    extra = torch.randn(B, E, Hl, Wl, generator=g) * 3
+    pad_value = torch.tensor([0.37, -2.5, 1.0, 0.0, 7.25][:E])              # not just 0 / 1
+    gframe = torch.randn(C, gpad.PH, gpad.PW, generator=g) if gpad.padded else None
+    vframe = torch.randn(C, vpad.PH, vpad.PW, generator=g) if vpad.padded else None
+    torch.manual_seed(17)
+    idx = host_rng.PickSampler(h * w).draw(K, 0.7, lambda: None, stamp=torch.empty(h * w, 4, dtype=torch.int8))
+    want_g, want_v, want_low = N.assemble_rows_x(
+        x, idx, pp.src_row, pp.src_col, h, w, (gpad.PH, gpad.PW, gpad.top, gpad.left), gframe, vp.win_y0, vp.win_x0, vp.Sh, vp.Sw,
+        (vpad.PH, vpad.PW, vpad.top, vpad.left), vframe, extra, pad_value, dtype)
+    n_g, n_v = 2 * K * B, vp.V * B
+    dv = lambda t: None if t is None else t.to(DEV)
+    xd, ed, pd, idxd, gfd, vfd = dv(x), dv(extra), dv(pad_value), dv(idx), dv(gframe), dv(vframe)
+    sr, sc, wy, wx = dev_i32(pp.src_row), dev_i32(pp.src_col), dev_i32(vp.win_y0), dev_i32(vp.win_x0)
+
+    def run(extra_t, g_rows=None, v_rows=None, gf=gfd, vf=vfd):
+        g_rows = torch.full((n_g, C + E, gpad.PH, gpad.PW), 9.0, device=DEV, dtype=dtype) if g_rows is None else g_rows
+        v_rows = torch.full((n_v, C + E, vpad.PH, vpad.PW), 9.0, device=DEV, dtype=dtype) if v_rows is None else v_rows
+        low = torch.full((K, B, C, h, w), 9.0, device=DEV)
+        ops.assemble_rows_x(xd, idxd, sr, sc, g_rows, h, w, gpad.top, gpad.left, gf, low, v_rows, wy, wx, vp.Sh, vp.Sw, vpad.top,
+                            vpad.left, vf, extra_t, pd)
+        return g_rows, v_rows, low
+
+    g_rows, v_rows, low = run(ed)
+    assert torch.equal(g_rows.cpu(), want_g) and torch.equal(v_rows.cpu(), want_v) and torch.equal(low.cpu(), want_low)
+    # channels 0..3 and low: ed_assemble_rows on the same inputs, bit for bit
+    g4 = torch.full((n_g, C, gpad.PH, gpad.PW), 9.0, device=DEV, dtype=dtype)
+    v4 = torch.full((n_v, C, vpad.PH, vpad.PW), 9.0, device=DEV, dtype=dtype)
+    low4 = torch.full((K, B, C, h, w), 9.0, device=DEV)
+    ops.assemble_rows(xd, idxd, sr, sc, g4, h, w, gpad.top, gpad.left, gfd, low4, v4, wy, wx, vp.Sh, vp.Sw, vpad.top, vpad.left, vfd)
+    assert torch.equal(g_rows[:, :C], g4) and torch.equal(v_rows[:, :C], v4) and torch.equal(low, low4)
+    # the CFG pair of every resampling step carries identical rows, extras included
+    pairs = g_rows.view(K, 2, B, C + E, gpad.PH, gpad.PW)
+    assert torch.equal(pairs[:, 0], pairs[:, 1])
+    # a misaligned ``extra`` view: the same bits (the extras are read one element at a time in both forms)
+    g2, v2, _ = run(_misaligned(extra))
+    assert torch.equal(g2, g_rows) and torch.equal(v2, v_rows)
+    # misaligned OUTPUT rows force the scalar forms: the same bits as the 4-wide ones
+    g3, v3, low3 = run(ed, _misaligned(torch.zeros(n_g, C + E, gpad.PH, gpad.PW, dtype=dtype)),
+                       _misaligned(torch.zeros(n_v, C + E, vpad.PH, vpad.PW, dtype=dtype)))
+    assert torch.equal(g3, g_rows) and torch.equal(v3, v_rows) and torch.equal(low3, low)
+    # inf in the pad region of the frames stays in the latent channels
+    if gpad.padded or vpad.padded:
+        gi = None if gfd is None else torch.full_like(gfd, float("inf"))
+        vi = None if vfd is None else torch.full_like(vfd, float("inf"))
+        g5, v5, _ = run(ed, gf=gi, vf=vi)
+        assert torch.equal(g5[:, C:], g_rows[:, C:]) and torch.equal(v5[:, C:], v_rows[:, C:])
+        assert bool(torch.isfinite(g5[:, C:].float()).all()) and bool(torch.isfinite(v5[:, C:].float()).all())
+        assert bool(torch.isinf(g5[:, :C].float()).any()) == gpad.padded
+    # without frames the latent channels pad with zeros and the extras still with their constants
+    if gpad.padded:
+        g6, _, _ = run(ed, gf=None, vf=None)
+        assert torch.equal(g6[:, C:], g_rows[:, C:])
+        assert torch.equal(g6[:, :C, :gpad.top], torch.zeros_like(g6[:, :C, :gpad.top]))
+        for e in range(E):
+            assert torch.equal(g6[:, C + e, :gpad.top].float().cpu(), torch.full_like(g6[:, C + e, :gpad.top].float().cpu(),
+                                                                                      float(pad_value[e].to(dtype))))
+
+
+def test_assemble_rows_x_rejections_leave_the_launch_state_clean():
+    from elasticdiffusion_official_amd import _hip, geometry
+    ops = _ops()
+    Hl, Wl, h, w, d = GEOMETRIES["padded"]
+    pp, vp = geometry.PickPlan(Hl, Wl, h, w), geometry.ViewPlan(Hl, Wl, d // 2, d // 2, d // 2)
+    gpad, vpad = geometry.PadPlan(h, w, d), geometry.PadPlan(vp.Sh, vp.Sw, d)
+    x = torch.randn(1, 4, Hl, Wl, device=DEV)
+    extra = torch.randn(1, 5, Hl, Wl, device=DEV)
+    pv = torch.tensor([1.0, 0, 0, 0, 0], device=DEV)
+    idx = torch.zeros(1, h * w, dtype=torch.uint8, device=DEV)
+    sr, sc, wy, wx = dev_i32(pp.src_row), dev_i32(pp.src_col), dev_i32(vp.win_y0), dev_i32(vp.win_x0)
+    g_rows = torch.full((2, 9, gpad.PH, gpad.PW), 9.0, device=DEV)
+    v_rows = torch.full((vp.V, 9, vpad.PH, vpad.PW), 9.0, device=DEV)
+    low = torch.empty(1, 1, 4, h, w, device=DEV)
+
+    def call(extra_t=extra, pv_t=pv, g=g_rows, lat=x):
+        ops.assemble_rows_x(lat, idx, sr, sc, g, h, w, gpad.top, gpad.left, None, low, v_rows, wy, wx, vp.Sh, vp.Sw, vpad.top,
+                            vpad.left, None, extra_t, pv_t)
+
+    with pytest.raises(RuntimeError, match="extra must be"):
+        call(extra[:, :, :-1].contiguous())                   # wrong extent
+    with pytest.raises(RuntimeError, match="extra must be"):
+        call(extra[:, :0].contiguous())                       # E = 0
+    with pytest.raises(RuntimeError, match="extra must be"):
+        call(None)
+    with pytest.raises(RuntimeError, match="pad_value must be"):
+        call(pv_t=None)
+    with pytest.raises(RuntimeError, match="pad_value must be"):
+        call(pv_t=pv[:4].contiguous())
+    with pytest.raises(RuntimeError, match="rows must be"):
+        call(g=g_rows[:, :8].contiguous())                    # rows without room for the extras
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        call(extra.cpu())
+    with pytest.raises(RuntimeError, match="float32"):
+        call(extra.half())
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        call(lat=x.cpu())
+    assert ops._LAUNCH["device"] is None
+    assert bool((g_rows == 9.0).all()) and bool((v_rows == 9.0).all())       # nothing was launched
+    # the C entry point itself: null extra / pad_value and E = 0 are hipErrorInvalidValue (1) before any launch
+    L = _hip.lib()
+    s = torch.cuda.current_stream().cuda_stream
+
+    def raw(extra_p, E, pv_p):
+        return L.ed_assemble_rows_x(x.data_ptr(), 1, 4, Hl, Wl, idx.data_ptr(), sr.data_ptr(), sc.data_ptr(), None, g_rows.data_ptr(),
+                                    low.data_ptr(), 1, h, w, gpad.PH, gpad.PW, gpad.top, gpad.left, wy.data_ptr(), wx.data_ptr(), None,
+                                    v_rows.data_ptr(), vp.V, vp.Sh, vp.Sw, vpad.PH, vpad.PW, vpad.top, vpad.left, 0, extra_p, E, pv_p, s)
+
+    assert raw(None, 5, pv.data_ptr()) == 1 and raw(extra.data_ptr(), 0, pv.data_ptr()) == 1 and raw(extra.data_ptr(), 5, None) == 1
+    torch.cuda.synchronize()
+    assert bool((g_rows == 9.0).all()) and bool((v_rows == 9.0).all())
+    call()                                                    # the launch state is clean again
+    assert not bool((g_rows == 9.0).any())
+
+
+# ---------------------------------------------------------------------------------------------------
+# ed_u8_to_vae_input_masked
+# ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
+@pytest.mark.parametrize("H,W", [(32, 32), (13, 19), (8, 64)])
+def test_u8_to_vae_input_masked_bit_exact(H, W, dtype):
+    """32x32 and 8x64 take the 4-pixel form, 13x19 (a width that is no multiple of 4, an odd pixel count) the scalar one; every
+    byte value occurs at every one of the 12 byte positions on BOTH sides of the mask (32x32), mask bytes 0 / 127 / 128 / 255"""
+    ops = _ops()
+    g = torch.Generator().manual_seed(H * 1000 + W)
+    if (H, W) == (32, 32):
+        img = torch.stack([torch.roll(torch.arange(256, dtype=torch.uint8), k) for k in range(12)]).t().contiguous().view(32, 32, 3)
+    else:
+        img = torch.randint(0, 256, (H, W, 3), generator=g, dtype=torch.uint8)
+    vals = torch.tensor([0, 127, 128, 255], dtype=torch.uint8)
+    masks = [vals[torch.randint(0, 4, (H, W), generator=g)], torch.zeros(H, W, dtype=torch.uint8),
+             torch.full((H, W), 255, dtype=torch.uint8)]
+    masks.append(255 - masks[0])        # the complementary side: 0 <-> 255, 127 <-> 128
+    for m in masks:
+        want = N.to_vae_input_masked(img.numpy(), m.numpy(), dtype)
+        got = ops.u8_to_vae_input_masked(img.to(DEV), m.to(DEV), dtype)
+        assert got.dtype == dtype and tuple(got.shape) == (1, 3, H, W)
+        assert torch.equal(got.cpu(), want)
+        hole = (m >= 128)[None, None].expand(1, 3, H, W)
+        assert not bool(torch.signbit(got.cpu()[hole]).any()) and bool((got.cpu()[hole] == 0).all())      # +0.0
+        # misaligned sources: the scalar form, the same bits
+        assert torch.equal(ops.u8_to_vae_input_masked(_misaligned(img), m.to(DEV), dtype).cpu(), want)
+        assert torch.equal(ops.u8_to_vae_input_masked(img.to(DEV), _misaligned(m), dtype).cpu(), want)
+    # all-kept is ed_u8_to_vae_input
+    assert torch.equal(ops.u8_to_vae_input_masked(img.to(DEV), masks[1].to(DEV), dtype), ops.u8_to_vae_input(img.to(DEV), dtype))
+
+
+def test_u8_to_vae_input_masked_rejections():
+    ops = _ops()
+    img = torch.zeros(8, 8, 3, dtype=torch.uint8, device=DEV)
+    m = torch.zeros(8, 8, dtype=torch.uint8, device=DEV)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        ops.u8_to_vae_input_masked(img.cpu(), m)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        ops.u8_to_vae_input_masked(img, m.cpu())
+    with pytest.raises(RuntimeError, match=r"\[H,W,3\]"):
+        ops.u8_to_vae_input_masked(img[:, :, :2].contiguous(), m)
+    with pytest.raises(RuntimeError, match="mask must be uint8"):
+        ops.u8_to_vae_input_masked(img, m[:4].contiguous())
+    with pytest.raises(RuntimeError, match="mask must be uint8"):
+        ops.u8_to_vae_input_masked(img, m.bool())
+    with pytest.raises(RuntimeError, match="threshold"):
+        ops.u8_to_vae_input_masked(img, m, threshold=0)
+    assert ops._LAUNCH["device"] is None
+    assert bool((ops.u8_to_vae_input_masked(img, m) == -1).all())
+
+
+# ---------------------------------------------------------------------------------------------------
+# end to end
+# ---------------------------------------------------------------------------------------------------
+NAME = "cfg2_sd_512x1024"
+
+
+def _pipe(name, sched_kw=EPS, unet=None, text_encoder=None, **extra):
+    from elasticdiffusion_official_amd import ElasticDiffusion
+    from elasticdiffusion_official_amd.schedule import DDIMSchedule
+    c = cases.E2E_CASES[name]
+    return ElasticDiffusion(DEV, c["sd"], view_batch_size=c["vbs"], unet=unet or N.FakeUNet9(c["sample"]), vae=FakeVAE(),
+                            text_encoder=text_encoder or V.embed_fn(False), scheduler=DDIMSchedule(**sched_kw), **extra)
+
+
+def _loop_kw(name):
+    c = cases.E2E_CASES[name]
+    return dict(height=c["H"], width=c["W"], num_inference_steps=c["steps"], resampling_steps=c["R"],
+                **dict(cases.E2E_KW, **c.get("kw", {})))
+
+
+def _inputs(name):
+    c = cases.E2E_CASES[name]
+    return synthetic_image(c["H"], c["W"], seed=c["seed"]), half_mask(c["H"], c["W"])
+
+
+_ORACLE, _GPU = {}, {}
+
+
+def _oracle_run(name, sched_kw, strength, gr):
+    """The CPU restatement's (latent, RNG tail, z0, zm) for one case, computed once and shared."""
+    key = (name, tuple(sorted(sched_kw.items())), strength, gr)
+    if key not in _ORACLE:
+        c = cases.E2E_CASES[name]
+        orc = N.Inpaint9Oracle(N.FakeUNet9(c["sample"]), FakeVAE(), V.DDIMVariants(**sched_kw), V.embed_fn(False), sd_version=c["sd"],
+                               view_batch_size=c["vbs"])
+        img, mask = _inputs(name)
+        orc.seed_everything(c["seed"])
+        z = orc.generate_latent("p", "", **_loop_kw(name), guidance_rescale=gr, init_image=img, strength=strength, mask_image=mask)
+        _ORACLE[key] = (z, torch.rand(4), orc.last_init_latents, orc.last_masked_image_latents)
+    return _ORACLE[key]
+
+
+E2E = [
+    (NAME, EPS, 1.0, 0.0),                             # the padded RePaint geometry: 64x128 latent, H-pad strips in the global rows
+    (NAME, EPS, 0.5, 0.0),                             # the last 2 of 4 steps
+    ("tall_1024x512_norepaint", EPS, 1.0, 0.0),        # without RePaint
+    (NAME, V_TRAILING_ZSNR, 1.0, 0.7),                 # v-prediction, zero terminal SNR, guidance rescale
+]
+
+
+@pytest.mark.parametrize("fused", [True, False])
+@pytest.mark.parametrize("name,sched_kw,strength,gr", E2E)
+def test_end_to_end_vs_cpu_restatement(name, sched_kw, strength, gr, fused):
+    from elasticdiffusion_official_amd import ops, pipeline
+    want, otail, oz0, ozm = _oracle_run(name, sched_kw, strength, gr)
+    img, mask = _inputs(name)
+    c = cases.E2E_CASES[name]
+    pipeline.FUSED_GLUE = fused
+    ops.TIMER.start()
+    try:
+        pipe = _pipe(name, sched_kw)
+        pipe.seed_everything(c["seed"])
+        z = pipe.generate_latents("p", "", **_loop_kw(name), guidance_rescale=gr, init_image=img, strength=strength,
+                                  mask_image=mask).cpu()
+        tail = torch.rand(4)
+    finally:
+        pipeline.FUSED_GLUE = True
+        counts = {k: v[0] for k, v in ops.TIMER.stop().items()}
+    err = rel_l2(z, want)
+    print(f"{name} {sorted(sched_kw)} strength={strength} gr={gr} fused={fused}: rel-L2 {err:.3e}, "
+          f"z0 {rel_l2(pipe.last_init_latents, oz0):.3e}, zm {rel_l2(pipe.last_masked_image_latents, ozm):.3e}")
+    assert z.shape[1] == 4 and bool(torch.isfinite(z).all())
+    assert err < 1e-4, err
+    assert torch.equal(tail, otail)
+    assert rel_l2(pipe.last_init_latents, oz0) < 1e-5 and rel_l2(pipe.last_masked_image_latents, ozm) < 1e-5
+    assert tuple(pipe.last_masked_image_latents.shape) == (1, 4, c["H"] // 8, c["W"] // 8)
+    # what ran: never the blend; one extended assembly per phase (fused), the once-per-image kernels once
+    T = c["steps"]
+    n = T - N.window(T, strength)
+    two_phase = sum(1 for i in range(T - n, T) if _loop_kw(name)["repaint_sampling"] and c["R"] > 0 and i < T - 1)
+    assert counts.get("ed_inpaint_blend", 0) == 0 and counts.get("ed_inpaint_blend_level", 0) == 0
+    assert counts["ed_u8_to_vae_input"] == 1 and counts["ed_u8_to_vae_input_masked"] == 1 and counts["ed_mask_to_latent"] == 1
+    assert counts["ed_img2img_init"] == 2
+    assert counts.get("ed_undo_step", 0) == two_phase
+    assert "ed_assemble_rows" not in counts
+    if fused:
+        assert counts["ed_assemble_rows_x"] == n + two_phase
+    else:
+        assert "ed_assemble_rows_x" not in counts and counts["ed_pick_assemble"] == n + two_phase
+    # fused and un-fused glue: the same bits
+    key = (name, tuple(sorted(sched_kw.items())), strength, gr)
+    if key in _GPU:
+        assert torch.equal(_GPU[key], z)
+    _GPU[key] = z
+
+
+def test_a_4_channel_run_launches_what_it_always_launched():
+    """the same init image and mask on the 4-channel fake UNet: section 18's counts, none of the new entry points"""
+    from elasticdiffusion_official_amd import ops
+    c = cases.E2E_CASES[NAME]
+    img, mask = _inputs(NAME)
+    counts = {}
+    for label, extra in (("plain", {}), ("masked", dict(init_image=img, mask_image=mask))):
+        pipe = _pipe(NAME, unet=FakeUNet(c["sample"]))
+        pipe.seed_everything(c["seed"])
+        ops.TIMER.start()
+        try:
+            pipe.generate_latents("p", "", **_loop_kw(NAME), **extra)
+        finally:
+            counts[label] = {k: v[0] for k, v in ops.TIMER.stop().items()}
+        assert pipe.last_masked_image_latents is None
+    phases = 2 * c["steps"] - 1
+    for label in counts:
+        assert not any(k in counts[label] for k in ("ed_assemble_rows_x", "ed_u8_to_vae_input_masked")), counts[label]
+        glue = {k: v for k, v in counts[label].items() if k in ("ed_assemble_rows", "ed_undo_step") or "epilogue" in k}
+        assert glue == {"ed_assemble_rows": phases, "ed_phase_epilogue": phases, "ed_undo_step": c["steps"] - 1}, counts[label]
+    added = {k: v for k, v in counts["masked"].items() if k not in counts["plain"]}
+    assert added == {"ed_u8_to_vae_input": 1, "ed_img2img_init": 1, "ed_mask_to_latent": 1, "ed_inpaint_blend": phases}, added
+    assert {k: v for k, v in counts["masked"].items() if k in counts["plain"]} == counts["plain"]
+
+
+def test_interleaved_two_jobs_match_each_alone():
+    kw = _loop_kw(NAME)
+    img, mask = _inputs(NAME)
+    img2 = synthetic_image(*img.shape[:2], seed=21)
+
+    def embed(prompts):  # stateless (the programs' calls interleave); the values V.embed_fn alternates between
+        (un, pun), (co, pco) = synthetic_text_embeds(1)
+        p = prompts[0] if isinstance(prompts, (list, tuple)) else prompts
+        return (un, pun) if p == "" else (co, pco)
+
+    pipe = _pipe(NAME, text_encoder=embed)
+    jobs = [dict(prompts="p", negative_prompts="", seed=cases.E2E_CASES[NAME]["seed"], init_image=img, mask_image=mask),
+            dict(prompts="p", negative_prompts="", seed=11, init_image=img2, mask_image=mask)]
+    alone = []
+    for job in jobs:
+        pipe.seed_everything(job["seed"])
+        alone.append(pipe.generate_latents("p", "", **kw, init_image=job["init_image"], mask_image=job["mask_image"]).clone())
+    got = pipe.generate_latents_interleaved(jobs, in_flight=2, **kw)
+    for z, want in zip(got, alone):
+        assert rel_l2(z, want) < 1e-5, rel_l2(z, want)
+    assert rel_l2(got[0], _oracle_run(NAME, EPS, 1.0, 0.0)[0]) < 1e-4
+    assert not torch.equal(got[0], got[1])
+    with pytest.raises(ValueError, match="init_image and mask_image"):      # every job of a 9-channel UNet carries both
+        pipe.generate_latents_interleaved(jobs + [dict(prompts="p", seed=3)], in_flight=2, **kw)
+
+
+def test_pipeline_argument_rules_and_composite():
+    from PIL import Image
+    from elasticdiffusion_official_amd import ElasticDiffusionControlNet, ops
+    from tests.fakes import FakeControlNet
+    c = cases.E2E_CASES[NAME]
+    pipe, bad = _pipe(NAME), _pipe(NAME)
+    bad.unet.config.in_channels = 5
+    cn = ElasticDiffusionControlNet(DEV, c["sd"], view_batch_size=c["vbs"], unet=N.FakeUNet9(c["sample"]), vae=FakeVAE(),
+                                    text_encoder=V.embed_fn(False), controlnet=FakeControlNet())
+    kw = dict(_loop_kw(NAME), num_inference_steps=2, resampling_steps=1)
+    img, mask = _inputs(NAME)
+    ops.TIMER.start()
+    try:
+        for call in (pipe.generate_latents, pipe.generate_image):
+            with pytest.raises(ValueError, match="init_image and mask_image"):
+                call("p", "", **kw)
+            with pytest.raises(ValueError, match="init_image and mask_image"):
+                call("p", "", **kw, init_image=img)
+            with pytest.raises(ValueError, match="graded"):
+                call("p", "", **kw, init_image=img, mask_image=mask, mask_mode="graded")
+            with pytest.raises(ValueError, match="8-bit"):
+                call("p", "", **kw, init_image=img, mask_image=torch.ones(c["H"] // 8, c["W"] // 8, dtype=torch.bool))
+        with pytest.raises(ValueError, match="in_channels"):
+            bad.generate_latents("p", "", **kw, init_image=img, mask_image=mask)
+        with pytest.raises(ValueError, match="ControlNet"):
+            cn.generate_image("p", "", torch.zeros(1, 3, 256, 512), **kw, init_image=img, mask_image=mask)
+    finally:
+        launched = ops.TIMER.stop()
+    assert not launched                      # every rule was checked before any launch
+    assert ops._LAUNCH["device"] is None
+    # composite: the init bytes wherever the feathered mask is 0; outpaint_canvas feeds the same path
+    pipe.seed_everything(3)
+    out, _ = pipe.generate_image("p", "", **kw, init_image=Image.fromarray(img), mask_image=Image.fromarray(mask), mask_blur=4.0,
+                                 composite=True, progress=lambda it: it)
+    res = np.asarray(out[0])
+    pm = pipe.last_pixel_mask.cpu().numpy()
+    assert res.shape == img.shape and 0 < int((pm == 0).sum()) < pm.size and 0 < int(((pm > 0) & (pm < 255)).sum())
+    assert np.array_equal(res[pm == 0], img[pm == 0])
+    assert not np.array_equal(res[pm == 255], img[pm == 255])
+    canvas, cmask = pipe.outpaint_canvas(img[:, 64:-64], 64, 0, 64, 0)
+    pipe.seed_everything(3)
+    z = pipe.generate_latents("p", "", **kw, init_image=canvas, mask_image=cmask)
+    assert tuple(z.shape) == (1, 4, c["H"] // 8, c["W"] // 8) and bool(torch.isfinite(z).all())
+
+
+def test_cli_with_an_inpaint_sd_version(tmp_path):
+    from PIL import Image
+    from elasticdiffusion_official_amd.__main__ import main
+    p, q = str(tmp_path / "init.png"), str(tmp_path / "mask.png")
+    Image.fromarray(synthetic_image(96, 128, seed=1)).save(p)
+    Image.fromarray(half_mask(96, 128, s=1)).save(q)
+    common = ["--H", "512", "--W", "512", "--steps", "2", "--resampling_steps", "1", "--outdir", str(tmp_path), "--seed", "3",
+              "--prompt", "a test prompt", "--view_batch_size", "4", "--exp", "i9"]
+    d = main(["--sd_version", "1.5-inpaint", *common, "--init_image", p, "--strength", "1.0", "--mask_image", q])
+    a = np.asarray(Image.open(os.path.join(d, "0.png")), dtype=np.float32)
+    assert a.shape == (512, 512, 3) and np.isfinite(a).all() and a.std() > 0
+    assert "sd_version: 1.5-inpaint" in open(os.path.join(d, "args.txt")).read()
+    with pytest.raises(SystemExit):
+        main(["--sd_version", "1.5-inpaint", *common])                                  # no init image / mask
+    with pytest.raises(SystemExit):
+        main(["--sd_version", "1.5-inpaint", *common, "--init_image", p])               # no mask
+    with pytest.raises(SystemExit):
+        main(["--sd_version", "3.0-inpaint", *common, "--init_image", p, "--mask_image", q])
+
+
+# ---------------------------------------------------------------------------------------------------
+# the real reduced-width 9-channel UNet against the fp64 specification
+# ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=lambda d: str(d).replace("torch.", ""))
+@pytest.mark.parametrize("fam", ["sd15", "sdxl"])
+def test_9_channel_unet_forward_vs_the_fp64_spec(fam, dtype):
+    """tests/test_sd_spec_gpu.py::test_unet_forward's judgement (its ``judge``, FACTOR, floors, input size, parameter rounding) on the
+    9-channel configuration of the same family: per-row timesteps and a scalar timestep"""
+    from elasticdiffusion_official_amd import models as M, ops
+    from tests import test_sd_spec_gpu as G
+    cfg = M.unet_config(fam, small=True, in_channels=9)
+    usd = G._rounded(M.UNet2DConditionModel(**cfg), 21, dtype)
+    raw = S.unet_inputs(cfg, G.NET_HW, seed=7)
+    i64 = {k: (v.to(dtype).double() if isinstance(v, torch.Tensor) and v.is_floating_point() else v) for k, v in raw.items()}
+    if raw["added"] is not None:
+        i64["added"] = dict(text_embeds=raw["added"]["text_embeds"].to(dtype).double(), time_ids=raw["added"]["time_ids"])
+    u64, gpu_sd = G._sides(usd, "")
+    assert i64["sample"].shape[1] == 9
+    with torch.no_grad():
+        ref = {"per-row": S.unet_forward(u64, cfg, i64["sample"], i64["t"], i64["context"], i64["added"]),
+               "scalar": S.unet_forward(u64, cfg, i64["sample"], i64["t"][0], i64["context"], i64["added"])}
+    m = G._load(M.UNet2DConditionModel(**cfg), usd, dtype, cl=M.CHANNELS_LAST)
+    i = G._to_dev(i64, dtype)
+    for case, t in (("per-row", i["t"]), ("scalar", i["t"][0])):
+        G.judge(ops, f"{fam} 9-channel UNet {G._name(dtype)}, {case}",
+                lambda: m(i["sample"], t, encoder_hidden_states=i["context"], added_cond_kwargs=i["added"]).sample,
+                lambda: S.unet_forward(gpu_sd, cfg, i["sample"], t, i["context"], i["added"]), ref[case],
+                expect=G._whole_expect(M), whole=True, library_conv=True)
