@@ -18,6 +18,7 @@ import torch.nn.functional as F
 from oracle import elastic_oracle as eo
 from oracle.ddim import DDIMOracle
 from tests.fakes import FakeControlNet, FakeUNet, FakeVAE, synthetic_text_embeds
+from tests.glue_geometries import FUSED_ROWS, PICK_ROWS, SCALAR_IMAGES, VIEW_ROWS, misaligned
 from tests.golden import cases
 
 pytestmark = pytest.mark.gpu
@@ -44,6 +45,7 @@ def rel_l2(a, b):
 # ---------------------------------------------------------------------------------------------------
 VIEW_CASES = [(64, 128, 64, None), (128, 256, 128, None), (256, 256, 128, None), (135, 240, 64, None),
               (96, 96, 64, 48), (67, 97, 64, None), (32, 64, 64, None), (128, 192, 128, 32)]
+VIEW_CASES += VIEW_ROWS  # crop widths / pad offsets that are no multiple of 4: the scalar gather (tests/glue_geometries.py)
 
 
 @pytest.mark.parametrize("Hl,Wl,sample,patch", VIEW_CASES)
@@ -70,6 +72,23 @@ def test_gather_views_and_scatter_centres_bit_exact(Hl, Wl, sample, patch, B):
     out = torch.empty(vp.V * B, 4, vp.Sh, vp.Sw, device=DEV)
     ops.gather_views(x.to(DEV), out, dev_i32(vp.win_y0), dev_i32(vp.win_x0), vp.Sh, vp.Sw)
     assert torch.equal(out.cpu(), want)
+    # the padded-view call of the pipeline (views smaller than the model): the crop at its offset inside the noise frame, every
+    # model dtype; expected by plain slicing, 16-bit values by torch's own round-to-nearest-even
+    vpad = geometry.PadPlan(vp.Sh, vp.Sw, sample)
+    if vpad.padded:
+        frame = torch.randn(4, vpad.PH, vpad.PW, generator=g)
+        want_p = frame.unsqueeze(0).repeat(vp.V * B, 1, 1, 1)
+        want_p[:, :, vpad.top:vpad.top + vp.Sh, vpad.left:vpad.left + vp.Sw] = want
+        for dtype in (torch.float32, torch.float16, torch.bfloat16):
+            out_p = torch.full((vp.V * B, 4, vpad.PH, vpad.PW), 9.0, device=DEV, dtype=dtype)
+            ops.gather_views(x.to(DEV), out_p, dev_i32(vp.win_y0), dev_i32(vp.win_x0), vp.Sh, vp.Sw, vpad.top, vpad.left,
+                             frame.to(DEV))
+            assert torch.equal(out_p.cpu(), want_p.to(dtype)), dtype
+        out_z = torch.full((vp.V * B, 4, vpad.PH, vpad.PW), 9.0, device=DEV)   # without a frame the pad region is zero
+        ops.gather_views(x.to(DEV), out_z, dev_i32(vp.win_y0), dev_i32(vp.win_x0), vp.Sh, vp.Sw, vpad.top, vpad.left)
+        want_z = torch.zeros_like(want_p)
+        want_z[:, :, vpad.top:vpad.top + vp.Sh, vpad.left:vpad.left + vp.Sw] = want
+        assert torch.equal(out_z.cpu(), want_z)
 
     # scatter: predictions with exact zeros sprinkled in, so the value-based first-writer rule is exercised
     pred = torch.randn(vp.V * B, 4, vp.Sh, vp.Sw, generator=g)
@@ -89,6 +108,7 @@ def test_gather_views_and_scatter_centres_bit_exact(Hl, Wl, sample, patch, B):
 
 PICK_CASES = [(64, 128, 32, 64), (128, 256, 64, 128), (64, 64, 64, 64), (135, 240, 36, 64), (96, 96, 64, 64),
               (67, 97, 44, 64), (256, 256, 128, 128)]
+PICK_CASES += PICK_ROWS  # w / pad offsets that are no multiple of 4: the scalar pick and unpad kernels (tests/glue_geometries.py)
 
 
 @pytest.mark.parametrize("Hl,Wl,h,w", PICK_CASES)
@@ -210,6 +230,82 @@ def test_rrg_update_bit_exact(Hl, Wl, h, w, weight):
                    dev_i32(pp.up_col), out, np.float32(10.0 / 3), sb, sa, np.float32(2.0 / (4 * Hl * Wl)),
                    np.float32(weight))
     assert torch.equal(out.cpu(), want)
+
+
+# The flat kernels hold n = B*4*H*W elements, always a multiple of 4: their scalar forms (k_cfg_ddim_s, k_undo_s, k_rrg_update at
+# W % 4 == 0) run only when an operand accessed 16 bytes at a time is not 16-byte aligned.  Same arithmetic per element, so the
+# same bits as the all-aligned launch -- which the tests above hold to the oracle.
+FLAT_SHAPE = (2, 4, 16, 24)
+
+
+@pytest.mark.parametrize("rescale", [False, True])
+@pytest.mark.parametrize("prediction_type", ["epsilon", "v_prediction"])
+def test_cfg_ddim_misaligned_operand_bit_equal(prediction_type, rescale):
+    _, ops, schedule = _gpu_mods()
+    sch = schedule.DDIMSchedule()
+    coef = sch.step_coefficients(sch.set_timesteps(50)[7])
+    g = torch.Generator().manual_seed(41)
+    ins = [torch.randn(FLAT_SHAPE, generator=g).to(DEV) for _ in range(3)]   # local, direction, x
+    kw = dict(prediction_type=prediction_type)
+    if rescale:
+        kw.update(ratio=torch.tensor([0.8, 1.1], device=DEV), guidance_rescale=0.7)
+    prev, x0 = torch.empty(FLAT_SHAPE, device=DEV), torch.empty(FLAT_SHAPE, device=DEV)
+    assert ops.cfg_ddim_step_width(*ins, prev, x0, kw.get("ratio")) == 4
+    ops.cfg_ddim_step(*ins, prev, x0, np.float32(10.0 / 3), *coef, **kw)
+    assert bool(torch.isfinite(prev).all()) and bool(torch.isfinite(x0).all())
+    for k in range(5):                                                       # one operand off a 16-byte boundary at a time
+        args = list(ins) + [torch.full(FLAT_SHAPE, 9.0, device=DEV), torch.full(FLAT_SHAPE, 9.0, device=DEV)]
+        args[k] = misaligned(args[k])
+        assert ops.cfg_ddim_step_width(*args, kw.get("ratio")) == 1
+        ops.cfg_ddim_step(*args, np.float32(10.0 / 3), *coef, **kw)
+        assert torch.equal(args[3], prev) and torch.equal(args[4], x0), k
+
+
+def test_undo_step_misaligned_operand_bit_equal():
+    _, ops, schedule = _gpu_mods()
+    sch = schedule.DDIMSchedule()
+    ts = sch.set_timesteps(200)                                              # 5 sub-steps: the 4-unrolled loop and its tail
+    coef = sch.undo_coefficients(ts[3]).to(DEV)
+    n_sub = coef.numel() // 2
+    g = torch.Generator().manual_seed(43)
+    x = torch.randn(FLAT_SHAPE, generator=g).to(DEV)
+    noise = torch.randn((n_sub,) + FLAT_SHAPE, generator=g).to(DEV)
+    want = ops.undo_step(x, noise, coef, torch.empty(FLAT_SHAPE, device=DEV))
+    assert n_sub == 5 and bool(torch.isfinite(want).all()) and not torch.equal(want, x)
+    for k in range(3):
+        args = [x, noise, torch.full(FLAT_SHAPE, 9.0, device=DEV)]
+        args[k] = misaligned(args[k])
+        got = ops.undo_step(args[0], args[1], coef, args[2])
+        assert torch.equal(got, want), k
+
+
+@pytest.mark.parametrize("rescale", [False, True])
+@pytest.mark.parametrize("prediction_type", ["epsilon", "v_prediction"])
+def test_rrg_update_misaligned_operand_bit_equal(prediction_type, rescale):
+    geometry, ops, schedule = _gpu_mods()
+    sch = schedule.DDIMSchedule()
+    sb, sa = sch.step_coefficients(sch.set_timesteps(50)[7])[:2]
+    B, C, H, W = FLAT_SHAPE
+    h, w = 8, 13
+    g = torch.Generator().manual_seed(47)
+    prev, x0 = (torch.randn(FLAT_SHAPE, generator=g).to(DEV) for _ in range(2))
+    low, unc, ldir = (torch.randn(B, C, h, w, generator=g).to(DEV) for _ in range(3))
+    up = dev_i32(geometry.nearest_index_map(h, H)), dev_i32(geometry.nearest_index_map(w, W))
+    tail = (np.float32(10.0 / 3), sb, sa, np.float32(2.0 / (4 * H * W)), np.float32(437.53))
+    kw = dict(prediction_type=prediction_type)
+    if rescale:
+        kw.update(ratio_low=torch.tensor([0.8, 1.1], device=DEV), guidance_rescale=0.7)
+    want = ops.rrg_update(prev, x0, low, unc, ldir, *up, torch.empty(FLAT_SHAPE, device=DEV), *tail, **kw)
+    assert bool(torch.isfinite(want).all()) and not torch.equal(want, prev)
+    for k in range(3):
+        args = [prev, x0, torch.full(FLAT_SHAPE, 9.0, device=DEV)]
+        args[k] = misaligned(args[k])
+        got = ops.rrg_update(args[0], args[1], low, unc, ldir, *up, args[2], *tail, **kw)
+        assert torch.equal(got, want), k
+    # the reduced-resolution operands are read one element at a time in both forms: no alignment condition
+    got = ops.rrg_update(prev, x0, misaligned(low), misaligned(unc), misaligned(ldir), *up,
+                         torch.full(FLAT_SHAPE, 9.0, device=DEV), *tail, **kw)
+    assert torch.equal(got, want)
 
 
 @pytest.mark.parametrize("name", list(cases.G7_CASES))
@@ -350,18 +446,39 @@ def _embed_fn_batch(B, xl=False):
     ("1.5", 64, 256, 512, 1, 2, None),      # latent 32x64: one dimension smaller than the model -> padded VIEWS too
     ("1.5", 64, 1080, 1920, 1, 1, None),    # windows do not tile: overlapping centres, fractional reduction 135 -> 36
     ("XL1.0", 128, 1024, 1536, 2, 1, 96),   # SDXL geometry, custom patch size, two prompts
+    # sizes whose rows leave the 4-wide kernels (tests/glue_geometries.py: SCALAR_IMAGES, classes (px4, gx4))
+    SCALAR_IMAGES["ff_one_view"] + (1, 1, None),    # 512x304: FF, one padded view, both pad offsets 13
+    SCALAR_IMAGES["ff_views"] + (2, 2, None),       # 768x432: FF, Sw = 54 at offset 5, w = 36 at offset 14
+    SCALAR_IMAGES["ft"] + (2, 2, None),             # 520x256: FT, w = 31
+    SCALAR_IMAGES["tf"] + (1, 1, None),             # 528x272: TF, Sw = 34 at offset 15
+    SCALAR_IMAGES["ff_xl"] + (1, 1, None),          # 1024x600 SDXL: FF, offset 26
+    SCALAR_IMAGES["ft_many"] + (1, 1, None),        # 1920x1080 portrait: FT, 40 views overlapping on both axes
 ])
 def test_edge_geometries_and_prompt_batches_vs_oracle(sd, sample, H, W, B, R, patch):
     """No golden for these: the oracle runs on the CPU in the test (seconds).  rel-L2 < 1e-4, identical RNG end state."""
+    _edge_run_vs_oracle(sd, sample, H, W, B, R, patch)
+
+
+def test_controlnet_condition_views_at_an_odd_pad_offset_vs_oracle():
+    """768x432 with a ControlNet: the condition rows are cut by ed_gather2d for views of Sw = 54 at v_off_x = 5 and picks of
+    w = 36 at g_off_x = 14 (pixel offsets 40 and 112), next to latent rows assembled by the scalar forms.  The bar of
+    test_edge_geometries_and_prompt_batches_vs_oracle."""
+    _edge_run_vs_oracle(*SCALAR_IMAGES["ff_views"], 1, 1, None, controlnet=True)
+
+
+def _edge_run_vs_oracle(sd, sample, H, W, B, R, patch, controlnet=False):
     from elasticdiffusion_official_amd import ElasticDiffusion
     xl = sd.startswith("XL")
     kw = dict(height=H, width=W, num_inference_steps=2, guidance_scale=10.0, resampling_steps=R, new_p=0.3,
               rrg_stop_t=0.4, rrg_init_weight=1000, cosine_scale=10.0, repaint_sampling=True)
+    if controlnet:
+        ds = eo.get_downsample_size(H, W, sd)
+        kw.update(condition_image=cases.synthetic_condition(ds[0] * 8, ds[1] * 8), controlnet_conditioning_scale=0.2)
     prompts = ["p%d" % i for i in range(B)]
     pipe = ElasticDiffusion(DEV, sd, view_batch_size=3, unet=FakeUNet(sample, xl=xl), vae=FakeVAE(),
-                            text_encoder=_embed_fn_batch(B, xl))
+                            text_encoder=_embed_fn_batch(B, xl), controlnet=FakeControlNet() if controlnet else None)
     orc = eo.ElasticOracle(FakeUNet(sample, xl=xl), FakeVAE(), DDIMOracle(), _embed_fn_batch(B, xl), sd_version=sd,
-                           view_batch_size=3, pooled_dim=16 if xl else None)
+                           view_batch_size=3, pooled_dim=16 if xl else None, controlnet=FakeControlNet() if controlnet else None)
     if patch is not None:
         pipe.set_view_config(patch)
         orc.set_view_config(patch)
@@ -416,10 +533,12 @@ FUSED_CASES = [  # Hl, Wl, h, w, model size d, patch
     (64, 128, 32, 64, 64, None),      # cfg2: padded global rows
     (128, 256, 64, 128, 128, None),   # cfg3
     (256, 256, 128, 128, 128, None),  # cfg4: 16 views, no padding
-    (67, 97, 44, 64, 64, None),       # ragged: overlapping centres, fractional reduction, scalar (non-x4) paths
+    (67, 97, 44, 64, 64, None),       # ragged: overlapping centres, fractional reduction, odd latent width; w = gPW = Sw = 64 and
+                                      # no x offsets, so every row kernel is 4-wide here (only ed_rrg_update is scalar, W = 97)
     (32, 64, 32, 64, 64, None),       # views smaller than the model: padded VIEW rows too, separate row shapes
     (96, 96, 64, 64, 64, 48),         # custom patch size
 ]
+FUSED_CASES += FUSED_ROWS  # the scalar classes (px4, gx4) = FF, FT, TF of ed_assemble_rows and odd offsets in the epilogue
 
 
 @pytest.mark.parametrize("Hl,Wl,h,w,d,patch", FUSED_CASES)

@@ -19,6 +19,7 @@ import torch
 from tests import ddim_variants as V
 from tests import img2img_cpu as I
 from tests.fakes import FakeUNet, FakeVAE, synthetic_text_embeds
+from tests.glue_geometries import misaligned as _misaligned
 from tests.golden import cases
 from tests.test_hip_parity import DEV, rel_l2
 from tests.test_img2img import half_mask, synthetic_image
@@ -34,15 +35,6 @@ NEW_ENTRY_POINTS = ("ed_u8_to_vae_input", "ed_img2img_init", "ed_mask_to_latent"
 def _ops():
     from elasticdiffusion_official_amd import ops
     return ops
-
-
-def _misaligned(t):
-    """a device copy of ``t`` that starts one element past a 16-byte boundary"""
-    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=DEV)
-    view = buf[1:].view(t.shape)
-    view.copy_(t)
-    assert view.data_ptr() % 16 != 0 and view.is_contiguous()
-    return view
 
 
 # ---------------------------------------------------------------------------------------------------

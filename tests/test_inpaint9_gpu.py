@@ -18,6 +18,7 @@ from tests import ddim_variants as V
 from tests import inpaint9_cpu as N
 from tests import sd_spec as S
 from tests.fakes import FakeUNet, FakeVAE, synthetic_text_embeds
+from tests.glue_geometries import SCALAR_GEOMETRIES, misaligned as _misaligned
 from tests.golden import cases
 from tests.test_hip_parity import DEV, dev_i32, rel_l2
 from tests.test_img2img import half_mask, synthetic_image
@@ -33,15 +34,6 @@ def _ops():
     return ops
 
 
-def _misaligned(t):
-    """a device copy of ``t`` that starts one element past a 16-byte boundary"""
-    buf = torch.empty(t.numel() + 1, dtype=t.dtype, device=DEV)
-    view = buf[1:].view(t.shape)
-    view.copy_(t)
-    assert view.data_ptr() % 16 != 0 and view.is_contiguous()
-    return view
-
-
 # ---------------------------------------------------------------------------------------------------
 # ed_assemble_rows_x
 # ---------------------------------------------------------------------------------------------------
@@ -50,6 +42,8 @@ GEOMETRIES = {  # Hl, Wl, h, w, model size d
     "no_pad": (64, 64, 64, 64, 64),       # nothing padded, one view
     "overlap": (67, 97, 44, 64, 64),      # 12 overlapping views, odd latent width (source rows on no alignment), fractional reduction
     "scalar": (33, 30, 33, 30, 64),       # w = Sw = 30: the scalar forms, pad strips on both axes of both parts
+    "ft": SCALAR_GEOMETRIES["ft"],        # w = 31: scalar picks next to 4-wide views (tests/glue_geometries.py)
+    "tf": SCALAR_GEOMETRIES["tf"],        # Sw = 34 at v_off_x = 15: 4-wide picks next to scalar views
 }
 ROW_CASES = [(1, 3, 5, torch.float32), (2, 1, 5, torch.bfloat16), (1, 1, 1, torch.float16), (2, 3, 5, torch.float16)]   # B, K, E, dtype
 
@@ -63,7 +57,7 @@ def test_assemble_rows_x_bit_exact(geo, B, K, E, dtype):
     C = 4
     pp, vp = geometry.PickPlan(Hl, Wl, h, w), geometry.ViewPlan(Hl, Wl, d // 2, d // 2, d // 2)
     gpad, vpad = geometry.PadPlan(h, w, d), geometry.PadPlan(vp.Sh, vp.Sw, d)
-    assert gpad.padded == (geo in ("padded", "overlap", "scalar")) and vpad.padded == (geo == "scalar")
+    assert gpad.padded == (geo in ("padded", "overlap", "scalar", "ft", "tf")) and vpad.padded == (geo in ("scalar", "ft", "tf"))
     g = torch.Generator().manual_seed(Hl * 131 + Wl + K + E)
     x = torch.randn(B, C, Hl, Wl, generator=g)
     extra = torch.randn(B, E, Hl, Wl, generator=g) * 3
