@@ -24,6 +24,8 @@ as A1111's emphasis syntax; both act on the CLIP encoders of ``--weights`` (the 
 ``--sd_version 1.5-inpaint`` / ``2.0-inpaint`` / ``XL1.0-inpaint`` builds the 9-channel inpainting UNet of the family (what the
 inpainting checkpoints carry; a ``--weights`` snapshot with a 9-channel ``conv_in`` selects it by itself): it needs ``--init_image``
 and a mask, and conditions on the mask and the blanked picture instead of pasting the kept region back.
+``--lora PATH[:SCALE]`` (repeatable) merges a LoRA adapter file into the weights after the models are built, in the order given
+(DESIGN.md section 23); SCALE defaults to 1.
 """
 import argparse
 import os
@@ -99,7 +101,21 @@ def build_parser():
                     "(concatenated on the token axis) instead of truncating at 75 tokens; 1 = the reference's truncation")
     ap.add_argument("--prompt_weighting", type=_bool, default=False, help="true: (word), [word], (word:1.3) scale the "
                     "embeddings of their tokens (A1111 syntax); false: brackets are literal text")
+    ap.add_argument("--lora", action="append", default=[], metavar="PATH[:SCALE]", help="merge this LoRA adapter "
+                    "(*.safetensors; diffusers, PEFT or kohya keys) into the UNet / CLIP weights at SCALE (default 1); repeatable, "
+                    "applied in the order given")
     return ap
+
+
+def _lora_arg(text):
+    """``PATH[:SCALE]`` -> (path, scale); a trailing ``:x`` counts as the scale only when x reads as a number"""
+    path, sep, tail = text.rpartition(":")
+    if sep and path:
+        try:
+            return path, float(tail)
+        except ValueError:
+            pass
+    return text, 1.0
 
 
 INPAINT_VERSIONS = ("1.5-inpaint", "2.0-inpaint", "XL1.0-inpaint")
@@ -122,6 +138,10 @@ def main(argv=None):
     if opt.max_prompt_chunks < 1:
         raise SystemExit(f"--max_prompt_chunks must be >= 1, got {opt.max_prompt_chunks}")
     from .pipeline import check_img2img_arguments
+    loras = [_lora_arg(v) for v in opt.lora]
+    for path, _ in loras:
+        if not os.path.isfile(path):
+            raise SystemExit(f"--lora: no such file {path!r}")
     pads = None
     if opt.outpaint is not None:
         if opt.mask_image or not opt.init_image:
@@ -173,6 +193,9 @@ def main(argv=None):
     else:
         sd = ElasticDiffusion(device, opt.sd_version, verbose=opt.verbose, log_freq=opt.log_freq,
                               view_batch_size=opt.view_batch_size, low_vram=opt.low_vram, **kw)
+    for path, scale in loras:
+        name = sd.load_lora(path, scale)
+        print(f"LoRA {name!r} merged at scale {scale:g}: {sd.loras[-1][2]} tensors")
     if opt.init_image:
         from PIL import Image
         extra["init_image"], extra["strength"] = Image.open(opt.init_image).convert("RGB"), opt.strength

@@ -14,7 +14,7 @@ import torch  # noqa: F401  (must be imported before the .so so libamdhip64 is a
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT_DIR = os.path.dirname(PKG_DIR)
 SOURCES = [os.path.join(PKG_DIR, "csrc", n) for n in ("elastic_kernels.hip", "unet_kernels.hip", "attention_kernels.hip", "gemm_kernels.hip", "vae_kernels.hip",
-                                                       "canny_kernels.hip", "resize_kernels.hip", "mask_kernels.hip")]
+                                                       "canny_kernels.hip", "resize_kernels.hip", "mask_kernels.hip", "lora_kernels.hip")]
 SRC = SOURCES[0]
 INCLUDE = os.path.join(ROOT_DIR, "include")
 SO_PATH = os.path.join(PKG_DIR, "libelastic_hip.so")
@@ -109,6 +109,7 @@ SIGNATURES = {
     "ed_inpaint_blend_level": [_vp, _vp, _i, _vp, _vp, _f, _f, _i, _vp, _i, _i64, _vp],
     "ed_composite_u8": [_vp, _vp, _vp, _vp, _i, _i, _vp],
     "ed_canvas_pad_u8": [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
+    "ed_lora_merge": [_vp, _vp, _i, _i, _i64, _vp],
 }
 
 _LIB = None

@@ -1670,3 +1670,33 @@ def canvas_pad_u8(img, left, top, right, bottom):
           _dev(mask, torch.uint8, "mask"), _stream())
     TIMER.note_work("ed_canvas_pad_u8", nbytes=float(Ho * Wo * 7))
     return canvas, mask
+
+
+def lora_merge(table):
+    """Merge every touched weight of one model from its pristine copy and its active adapters: ONE launch over ``table``
+    (``lora.LoraTable``, uploaded: ``host`` int64 on the CPU and ``dev`` its device copy; layout in include/elastic_hip.h).  The
+    tensors the table points to (``table.keep``) are checked here -- on the device of the table, base and destination dense in the
+    same order, fp32 factors of matching extents -- and every word of the table again by ed_lora_merge before it launches."""
+    host, dev = getattr(table, "host", None), getattr(table, "dev", None)
+    p_dev = _dev(dev, torch.int64, "table.dev")
+    if not isinstance(host, torch.Tensor) or host.is_cuda or host.dtype != torch.int64 or not host.is_contiguous() or \
+            host.shape != dev.shape or host.numel() != 8 * table.n_tensors + 4 * table.n_adapters:
+        _reject("table.host must be the int64 CPU tensor table.dev was copied from (8 words per tensor, 4 per adapter)")
+    for base, dst, adapters in table.keep:
+        for t, what in ((base, "base"), (dst, "destination")):
+            if not isinstance(t, torch.Tensor) or t.device != dev.device:
+                _reject(f"lora_merge: {what} must be a tensor on {dev.device}; no CPU fallback")
+            if not (t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last))):
+                _reject(f"lora_merge: {what} must be dense in contiguous or channels-last order")
+        if base.shape != dst.shape or base.dtype != dst.dtype or base.stride() != dst.stride() or base.numel() >= 2 ** 31:
+            _reject(f"lora_merge: base {tuple(base.shape)} {base.dtype} and destination {tuple(dst.shape)} {dst.dtype} must agree "
+                    "in shape, strides and dtype, below 2^31 elements")
+        N = int(base.shape[0])
+        for up, down, _ in adapters:
+            _dev(up, torch.float32, "up")
+            _dev(down, torch.float32, "down")
+            if up.dim() != 2 or down.dim() != 2 or up.shape[0] != N or up.shape[1] != down.shape[0] or \
+                    down.shape[1] * N != base.numel():
+                _reject(f"lora_merge: up {tuple(up.shape)} / down {tuple(down.shape)} do not fit a weight of {tuple(base.shape)}")
+    _call("ed_lora_merge", host.data_ptr(), p_dev, table.n_tensors, table.n_adapters, table.n_tiles, _stream())
+    TIMER.note_work("ed_lora_merge", flops=table.flops, nbytes=table.nbytes)

@@ -398,6 +398,67 @@ class ElasticDiffusion(nn.Module):
     def model_dtype(self):
         return next(self.unet.parameters()).dtype
 
+    # ---- LoRA adapters, merged into the weights ----------------------------------
+    def _lora_state(self):
+        """The adapter state, made on first use: a pipeline that never loads an adapter allocates and launches nothing for it."""
+        st = self.__dict__.get("_lora")
+        if st is None:
+            from . import lora, models
+            encs = list(getattr(self.text_encoder, "encoders", None) or [])
+            targets = {"unet": self.unet, "text_encoder": encs[0] if encs else None,
+                       "text_encoder_2": encs[1] if len(encs) > 1 else None}
+            cfg = None
+            if isinstance(self.unet, models.UNet2DConditionModel):
+                try:  # block structure only (layers per block, attention placement): the same at full and reduced width
+                    cfg = models.unet_config(models.family(self.sd_version))
+                except ValueError:
+                    cfg = None
+            st = self.__dict__["_lora"] = lora.LoraState(targets, self.device, cfg)
+        return st
+
+    def _lora_change(self, fn):
+        """Run one change of adapter state.  The merge kernel writes the weights through raw pointers, so afterwards the captured
+        graphs (a replay reads derived weight copies at fixed addresses and runs no Python) are dropped and the hoisted
+        cross-attention k|v re-projected; the derived-weight caches of the written models are dropped by ``LoraState.merge``."""
+        if self.__dict__.get("_live_jobs"):
+            raise RuntimeError("LoRA state cannot change while generate_latents_interleaved has images in flight")
+        with torch.cuda.device(self.device):
+            out = fn(self._lora_state())
+        self._runner.entries.clear()
+        self._runner.new_image()
+        return out
+
+    @torch.no_grad()
+    def load_lora(self, source, scale=1.0, name=None, text_encoder=True):
+        """Merge a LoRA adapter (a ``*.safetensors`` file or a state dict; diffusers / PEFT, legacy diffusers and kohya key
+        spellings, kohya SDXL files in SGM block names) into the UNet and -- with ``text.ClipTextEncoder`` encoders -- the CLIP
+        weights, at ``scale``.  Every key must name a Linear / Conv2d weight of fitting shape or nothing is applied.
+        ``text_encoder=False`` drops the text-encoder keys.  Several adapters add up, each weight rounded once from its pristine
+        copy.  ControlNet weights are never touched.  Returns the adapter's name (default: the file's base name)."""
+        return self._lora_change(lambda st: st.load(source, scale, name, text_encoder))[0]
+
+    @torch.no_grad()
+    def set_lora_scale(self, scale, name=None):
+        """New scale for the adapter ``name`` (None: all of them): one table rewrite and one merge launch per touched model.
+        Scale 0 gives the original weights back bit for bit."""
+        self._lora_change(lambda st: st.set_scale(scale, name))
+
+    @torch.no_grad()
+    def unload_lora(self, name=None):
+        """Remove the adapter ``name`` (None: all): the weights are re-merged from their pristine copies, which are freed for
+        every tensor no remaining adapter touches."""
+        if not self.loras:
+            if name is not None:
+                raise KeyError(f"no LoRA adapter named {name!r}; none is loaded")
+            return
+        self._lora_change(lambda st: st.unload(name))
+
+    @property
+    def loras(self):
+        """[(name, scale, tensors touched)] in load order"""
+        st = self.__dict__.get("_lora")
+        return [] if st is None else st.listing()
+
     @torch.no_grad()
     def get_text_embeds(self, prompt, min_chunks=None):
         """ED:254-265.  With no CLIP weights available the default is a deterministic synthetic embedding per prompt
@@ -1221,45 +1282,49 @@ class ElasticDiffusion(nn.Module):
             live.append([j, prog, rng, call])
 
         self.job_events = {}  # job -> [start event, end event] on this device's stream (``job_latencies``)
-        while queue and len(live) < max(1, in_flight):
-            start(queue.pop(0))
-        self.ticks = 0
-        while live:
-            # one fused forward per group of shape-compatible pending calls (normally exactly one group)
-            groups = {}
-            for ent in live:
-                c = ent[3]
-                groups.setdefault((tuple(c.rows.shape[1:]), c.cond is None, tuple(c.text.shape[1:])), []).append(ent)
-            for ents in groups.values():
-                calls = [e[3] for e in ents]
-                sizes = [c.rows.shape[0] for c in calls]
-                if len(calls) == 1:
-                    c = calls[0]
-                    outs = [self._run_model(c.rows, c.t, c.text, c.pooled, c.cond, fresh_side=True)]
-                else:
-                    rows = torch.cat([c.rows for c in calls])
-                    t = torch.cat([c.t.reshape(1).expand(n) for c, n in zip(calls, sizes)])
-                    text = torch.cat([c.text for c in calls])
-                    pooled = torch.cat([c.pooled for c in calls])
-                    cond = None if calls[0].cond is None else torch.cat([c.cond for c in calls])
-                    outs = self._run_model(rows, t, text, pooled, cond, fresh_side=True).split(sizes)
-                self.ticks += 1
-                for ent, out in zip(ents, outs):
-                    j, prog, rng = ent[0], ent[1], ent[2]
-                    try:
-                        with rng:
-                            ent[3] = prog.send(out)
-                    except StopIteration as stop:
-                        results[j] = stop.value
-                        live.remove(ent)
-                        if on_done is not None:
-                            on_done(j, stop.value)
-                        with torch.cuda.device(self.device):
-                            ev1 = torch.cuda.Event(enable_timing=True)
-                            ev1.record(torch.cuda.current_stream(self.device))
-                        self.job_events[j][1] = ev1
-                        if queue:
-                            start(queue.pop(0))
+        self._live_jobs = live  # a change of LoRA state is refused while this list is non-empty (``_lora_change``)
+        try:
+            while queue and len(live) < max(1, in_flight):
+                start(queue.pop(0))
+            self.ticks = 0
+            while live:
+                # one fused forward per group of shape-compatible pending calls (normally exactly one group)
+                groups = {}
+                for ent in live:
+                    c = ent[3]
+                    groups.setdefault((tuple(c.rows.shape[1:]), c.cond is None, tuple(c.text.shape[1:])), []).append(ent)
+                for ents in groups.values():
+                    calls = [e[3] for e in ents]
+                    sizes = [c.rows.shape[0] for c in calls]
+                    if len(calls) == 1:
+                        c = calls[0]
+                        outs = [self._run_model(c.rows, c.t, c.text, c.pooled, c.cond, fresh_side=True)]
+                    else:
+                        rows = torch.cat([c.rows for c in calls])
+                        t = torch.cat([c.t.reshape(1).expand(n) for c, n in zip(calls, sizes)])
+                        text = torch.cat([c.text for c in calls])
+                        pooled = torch.cat([c.pooled for c in calls])
+                        cond = None if calls[0].cond is None else torch.cat([c.cond for c in calls])
+                        outs = self._run_model(rows, t, text, pooled, cond, fresh_side=True).split(sizes)
+                    self.ticks += 1
+                    for ent, out in zip(ents, outs):
+                        j, prog, rng = ent[0], ent[1], ent[2]
+                        try:
+                            with rng:
+                                ent[3] = prog.send(out)
+                        except StopIteration as stop:
+                            results[j] = stop.value
+                            live.remove(ent)
+                            if on_done is not None:
+                                on_done(j, stop.value)
+                            with torch.cuda.device(self.device):
+                                ev1 = torch.cuda.Event(enable_timing=True)
+                                ev1.record(torch.cuda.current_stream(self.device))
+                            self.job_events[j][1] = ev1
+                            if queue:
+                                start(queue.pop(0))
+        finally:
+            self._live_jobs = None
         self.last_latents = results[-1] if results else None
         self.host_s["blocked_ahead_of_gpu"] = self._stager.waited
         self._mark("loop_done")

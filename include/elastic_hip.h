@@ -701,6 +701,38 @@ int ed_composite_u8(const float* decoded, const uint8_t* init, const uint8_t* ma
 int ed_canvas_pad_u8(const uint8_t* img, int H, int W, int left, int top, int right, int bottom, uint8_t* canvas, uint8_t* mask,
                      void* stream);
 
+/*
+ * ---- LoRA adapters merged into the weights (an addition, still ABI v13).
+ *
+ * ed_lora_merge -- ONE launch writes every touched weight of a model from its pristine copy and its active adapters.  A weight is a
+ *   dense row-major [N, K] matrix in its physical memory order (N = output features / channels, K = input features, or kh * kw * Cin
+ *   in the memory order of a convolution weight: channels-last [N, kh, kw, Cin] for the 16-bit UNet).  Adapters j of the tensor in
+ *   table order:
+ *       W[n, k] = rn_dtype( f32(base[n, k]) + s ),    s = sum_j c_j * ( sum_q up_j[n, q] * down_j[q, k] )
+ *   inner and outer sum are fp32 fmaf chains from +0 (q ascending, then j ascending), then one fp32 add and ONE rounding to the
+ *   weight's type.  An element's bits depend on its own tensor's records only, not on the rest of the table.  A tensor whose adapter
+ *   range is empty is a plain copy of its base.
+ *
+ *   The table is one array of int64 words; the caller keeps it twice with identical contents: `table_host` in HOST memory (the one
+ *   pointer of this ABI that is not a device pointer; every word of it is checked before anything is launched) and `table_dev` in
+ *   device memory (what the kernel reads; 8-byte aligned).  The pointers INSIDE the table are device pointers.
+ *     words [8 t, 8 t + 8), t in [0, n_tensors)                   -- tensor record:
+ *       0 base   const void*, dtype elements, N * K of them        4 dtype  ED_F32 / ED_F16 / ED_BF16 (base and dst alike)
+ *       1 dst    void*, the weight's own storage; != base          5 a0     first adapter record of this tensor
+ *       2 N      >= 1                                              6 a1     one past its last; a0 == a1: copy base -> dst
+ *       3 K      >= 1, N * K < 2^31                                7 tile0  sum of the tile counts of the tensors before it
+ *     words [8 n_tensors + 4 a, 8 n_tensors + 4 a + 4), a in [0, n_adapters)   -- adapter record:
+ *       0 up     const float* [N, r]      1 down   const float* [r, K] (K in the weight's physical order)
+ *       2 r      1 .. 65536               3 c      the bits of the fp32 coefficient in the low 32 bits (finite), high bits 0
+ *   A tensor has ceil(N / 64) * ceil(K / 128) tiles (ED_LORA_TILE_N x ED_LORA_TILE_K); n_tiles is their sum over the table (the
+ *   grid).  The adapter ranges of consecutive tensors are consecutive (tensor 0 starts at 0, the last ends at n_adapters).  A null
+ *   or misaligned pointer, a dtype code, an extent, a range, a tile0 or an n_tiles that breaks these rules is hipErrorInvalidValue
+ *   and nothing is launched.
+ */
+enum { ED_LORA_TENSOR_WORDS = 8, ED_LORA_ADAPTER_WORDS = 4, ED_LORA_TILE_N = 64, ED_LORA_TILE_K = 128 };
+int ed_lora_merge(const int64_t* table_host, const int64_t* table_dev, int n_tensors, int n_adapters, int64_t n_tiles,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif
