@@ -26,6 +26,9 @@ inpainting checkpoints carry; a ``--weights`` snapshot with a 9-channel ``conv_i
 and a mask, and conditions on the mask and the blanked picture instead of pasting the kept region back.
 ``--lora PATH[:SCALE]`` (repeatable) merges a LoRA adapter file into the weights after the models are built, in the order given
 (DESIGN.md section 23); SCALE defaults to 1.
+``--ip_adapter PATH[:SCALE]`` installs a base IP-Adapter and takes the image prompt either as a picture,
+``--ip_adapter_image FILE`` with ``--image_encoder DIR`` (a local CLIPVisionModelWithProjection), or as CLIP image embeddings,
+``--ip_adapter_embeds FILE`` (``.pt`` / ``.npy``).
 """
 import argparse
 import os
@@ -104,7 +107,22 @@ def build_parser():
     ap.add_argument("--lora", action="append", default=[], metavar="PATH[:SCALE]", help="merge this LoRA adapter "
                     "(*.safetensors; diffusers, PEFT or kohya keys) into the UNet / CLIP weights at SCALE (default 1); repeatable, "
                     "applied in the order given")
+    ap.add_argument("--ip_adapter", type=str, default=None, metavar="PATH[:SCALE]", help="install this base IP-Adapter "
+                    "(*.safetensors, *.bin, *.pt) at SCALE (default 1); needs --ip_adapter_image or --ip_adapter_embeds")
+    ap.add_argument("--ip_adapter_image", type=str, default=None, help="the image prompt (a picture; needs --image_encoder)")
+    ap.add_argument("--ip_adapter_embeds", type=str, default=None, help="the image prompt as CLIP image embeddings "
+                    "[1, clip_dim]: a .pt (torch.save of a tensor) or .npy file")
+    ap.add_argument("--image_encoder", type=str, default=None, help="local directory of a transformers "
+                    "CLIPVisionModelWithProjection, for --ip_adapter_image")
     return ap
+
+
+def _load_embeds(path):
+    if path.endswith(".npy"):
+        return torch.from_numpy(np.load(path, allow_pickle=False)).float()
+    if path.endswith(".pt"):
+        return torch.load(path, map_location="cpu", weights_only=True).float()
+    raise SystemExit(f"--ip_adapter_embeds takes a .pt or .npy file, got {path!r}")
 
 
 def _lora_arg(text):
@@ -142,6 +160,21 @@ def main(argv=None):
     for path, _ in loras:
         if not os.path.isfile(path):
             raise SystemExit(f"--lora: no such file {path!r}")
+    ip = None
+    if opt.ip_adapter is not None:
+        ip = _lora_arg(opt.ip_adapter)
+        if (opt.ip_adapter_image is None) == (opt.ip_adapter_embeds is None):
+            raise SystemExit("--ip_adapter needs exactly one of --ip_adapter_image / --ip_adapter_embeds")
+        if opt.ip_adapter_image is not None and opt.image_encoder is None:
+            raise SystemExit("--ip_adapter_image needs --image_encoder (a local CLIPVisionModelWithProjection directory)")
+        for flag, path in (("--ip_adapter", ip[0]), ("--ip_adapter_image", opt.ip_adapter_image),
+                           ("--ip_adapter_embeds", opt.ip_adapter_embeds)):
+            if path is not None and not os.path.isfile(path):
+                raise SystemExit(f"{flag}: no such file {path!r}")
+        if opt.image_encoder is not None and not os.path.isdir(opt.image_encoder):
+            raise SystemExit(f"--image_encoder: no such directory {opt.image_encoder!r}")
+    elif opt.ip_adapter_image or opt.ip_adapter_embeds or opt.image_encoder:
+        raise SystemExit("--ip_adapter_image / --ip_adapter_embeds / --image_encoder need --ip_adapter")
     pads = None
     if opt.outpaint is not None:
         if opt.mask_image or not opt.init_image:
@@ -196,6 +229,14 @@ def main(argv=None):
     for path, scale in loras:
         name = sd.load_lora(path, scale)
         print(f"LoRA {name!r} merged at scale {scale:g}: {sd.loras[-1][2]} tensors")
+    if ip is not None:
+        name = sd.load_ip_adapter(ip[0], ip[1], image_encoder=opt.image_encoder)
+        print(f"IP-Adapter {name!r} installed at scale {ip[1]:g}: {sd.ip_adapter[2]} image tokens")
+        if opt.ip_adapter_image:
+            from PIL import Image
+            extra["ip_adapter_image"] = Image.open(opt.ip_adapter_image).convert("RGB")
+        else:
+            extra["ip_adapter_image_embeds"] = _load_embeds(opt.ip_adapter_embeds)
     if opt.init_image:
         from PIL import Image
         extra["init_image"], extra["strength"] = Image.open(opt.init_image).convert("RGB"), opt.strength

@@ -110,6 +110,8 @@ SIGNATURES = {
     "ed_composite_u8": [_vp, _vp, _vp, _vp, _i, _i, _vp],
     "ed_canvas_pad_u8": [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
     "ed_lora_merge": [_vp, _vp, _i, _i, _i64, _vp],
+    "ed_flash_attention_ip": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f, _f, _vp],
+    "ed_u8_to_clip_input": [_vp, _i, _i, _i, _i, _i, _vp, _f, _f, _f, _f, _f, _f, _vp],
 }
 
 _LIB = None

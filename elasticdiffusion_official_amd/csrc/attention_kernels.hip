@@ -941,6 +941,144 @@ k_flash_attn_smallkv(const Params p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// IP-Adapter decoupled cross attention: the small-KV kernel with one more 32-key block for the image
+// tokens and a second softmax over that block alone.
+//   out = softmax(q k_t^T s) v_t + ip_scale * softmax(q k_i^T s) v_i
+// k / v hold Nt text rows followed by Ni image rows.  Text rows are staged into blocks 0 .. NKB - 1 exactly as
+// k_flash_attn_smallkv stages them (rows >= Nt zero and masked), image rows into block NKB (rows >= Ni zero and masked), so
+// every block belongs to one softmax and the 16 extra scores of a query row are one more accumulator.  The text term is the
+// small-KV kernel's arithmetic operation for operation -- the same MFMA chains over the same blocks, the maximum and the sum
+// over the text blocks only, inv_t applied once at the store -- so at ip_scale = 0 the result is that kernel's, bit for bit
+// (the image term is then a finite value times zero, and x + (+-0) = x for every x an accumulator started at +0 can hold).
+// Six blocks: 192 x (72 + 96) x 2 = 64 512 B of LDS, two workgroups per CU as before.
+// ---------------------------------------------------------------------------------------------------------------------
+struct ParamsIp {
+  Params p;        // p.Nk = Nt (text keys)
+  int Ni;          // image keys, 1 .. 32
+  float ip_scale;
+};
+
+template <typename T, int NKB>
+__global__ void __launch_bounds__(256, 2)
+k_flash_attn_ip(const ParamsIp pi) {
+  __shared__ SmemSmall<NKB + 1> sm;
+  const Params& p = pi.p;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int ln = lane & 31, hi = lane >> 5;
+  const int nqg = p.nqb;
+  const int bh = blockIdx.x / nqg, qgrp = blockIdx.x - bh * nqg;
+  const int b = bh / p.H, h = bh - b * p.H;
+  const uint16_t* qg = p.q + b * p.q_sb + h * D;
+  const uint16_t* kg = p.k + b * p.k_sb + h * D;
+  const uint16_t* vg = p.v + b * p.v_sb + h * D;
+  uint16_t* og = p.o + b * p.o_sb + h * D;
+  const int Nt = p.Nk, Ni = pi.Ni;
+
+  // LDS row r < 32 NKB holds text key r (zero from Nt on); LDS row 32 NKB + j holds image key j = memory row Nt + j (zero from Ni on)
+  for (int idx = tid; idx < 32 * (NKB + 1) * 8; idx += 256) {
+    const int row = idx >> 3, col = (idx & 7) * 8;
+    const bool img = row >= 32 * NKB;
+    const int j = row - 32 * NKB;
+    const int src = img ? Nt + j : row;
+    const int lim = img ? Nt + Ni : Nt;   // j < 32 and Ni <= 32: src < lim <=> j < Ni
+    *reinterpret_cast<Vec16*>(&sm.k[row * K_LD + col]) = load_row16(kg, p.k_sn, src, lim, col);
+    *reinterpret_cast<Vec16*>(&sm.v[row * V_LD_TR + col]) = load_row16(vg, p.v_sn, src, lim, col);
+  }
+  __syncthreads();
+  const float sl = p.scale_log2e;
+
+  for (int qb = 0; qb < SK_QBLOCKS; ++qb) {
+    const int q_row = (qgrp * SK_QBLOCKS + qb) * QB + wave * 32 + ln;
+    if ((qgrp * SK_QBLOCKS + qb) * QB + wave * 32 >= p.Nq) break;  // wave-uniform: nothing left for this wave
+    typename T::v8 qf[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) qf[ks] = as_v8<typename T::v8>(load_row16(qg, p.q_sn, q_row, p.Nq, 16 * ks + 8 * hi));
+    f32x16 s[NKB + 1];
+#pragma unroll
+    for (int kb = 0; kb <= NKB; ++kb)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) s[kb][i] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+      for (int kb = 0; kb <= NKB; ++kb) {
+        const Vec16 kf = *reinterpret_cast<const Vec16*>(&sm.k[(32 * kb + ln) * K_LD + 16 * ks + 8 * hi]);
+        s[kb] = T::mfma(as_v8<typename T::v8>(kf), qf[ks], s[kb]);
+      }
+    // text softmax: k_flash_attn_smallkv's, over blocks 0 .. NKB - 1
+    float mx = -INFINITY;
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        if (32 * kb + 8 * (r >> 2) + 4 * hi + (r & 3) >= Nt) s[kb][r] = -INFINITY;
+        mx = fmaxf(mx, s[kb][r]);
+      }
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float mb = mx * sl;
+    float psum = 0.f;
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kb][r], sl, -mb));
+        s[kb][r] = e;
+        psum += e;
+      }
+    psum += __shfl_xor(psum, 32, 64);
+    const float inv = 1.0f / psum;
+    // image softmax: block NKB alone
+    float mxi = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      if (8 * (r >> 2) + 4 * hi + (r & 3) >= Ni) s[NKB][r] = -INFINITY;
+      mxi = fmaxf(mxi, s[NKB][r]);
+    }
+    mxi = fmaxf(mxi, __shfl_xor(mxi, 32, 64));
+    const float mbi = mxi * sl;
+    float psi = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(s[NKB][r], sl, -mbi));
+      s[NKB][r] = e;
+      psi += e;
+    }
+    psi += __shfl_xor(psi, 32, 64);
+    const float invi = 1.0f / psi;
+    f32x16 o[2], oi[2];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) o[0][i] = o[1][i] = oi[0][i] = oi[1][i] = 0.f;
+#pragma unroll
+    for (int st = 0; st < 2 * NKB; ++st) {
+      f32x8 pv;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) pv[j] = s[st >> 1][8 * (st & 1) + j];
+      const typename T::v8 pf = T::pack(pv);
+#pragma unroll
+      for (int db = 0; db < 2; ++db)
+        o[db] = T::mfma(as_v8<typename T::v8>(v_frag_tr(sm.v, lane, hi, st, db)), pf, o[db]);
+    }
+#pragma unroll
+    for (int st = 2 * NKB; st < 2 * NKB + 2; ++st) {
+      f32x8 pv;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) pv[j] = s[NKB][8 * (st & 1) + j];
+      const typename T::v8 pf = T::pack(pv);
+#pragma unroll
+      for (int db = 0; db < 2; ++db)
+        oi[db] = T::mfma(as_v8<typename T::v8>(v_frag_tr(sm.v, lane, hi, st, db)), pf, oi[db]);
+    }
+    // o_t * inv_t + ip_scale * (o_i * inv_i), each product rounded on its own (-ffp-contract=off), then store_o_row's pack with inv = 1
+#pragma unroll
+    for (int db = 0; db < 2; ++db)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) o[db][i] = o[db][i] * inv + pi.ip_scale * (oi[db][i] * invi);
+    store_o_row<T>(og + (int64_t)q_row * p.o_sn, o, 1.0f, hi, q_row < p.Nq);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Round 4: any head dimension that is a multiple of 8 up to 160 (SD 1.x: 8 heads of 40 / 80 / 160; SD 2.x: 64).  Round 3's
 // kernels are head_dim 64 only, so the SD1.5 workload (BASELINE.json configs[1]) still went through SDPA -- AOTriton's
 // `attn_fwd`, 25 % of its GPU time (profiles/r4_s5_bench_cfg2_sd15_512x1024_kernel_stats.csv).  Same design as
@@ -1218,6 +1356,34 @@ int ed_flash_attention(const void* q, const void* k, const void* v, void* out, i
     return (int)hipErrorInvalidValue;
   }
 #undef ED_FA
+  return (int)hipGetLastError();
+}
+
+int ed_flash_attention_ip(const void* q, const void* k, const void* v, void* out, int dtype, int B, int H, int Nq, int Nt, int Ni,
+                          int head_dim, int64_t q_sb, int64_t q_sn, int64_t k_sb, int64_t k_sn, int64_t v_sb, int64_t v_sn,
+                          int64_t o_sb, int64_t o_sn, float scale, float ip_scale, void* stream) {
+  if (head_dim != D || Nt < 1 || Nt > 160 || Ni < 1 || Ni > 32) return (int)hipErrorInvalidValue;
+  if (dtype != ED_BF16 && dtype != ED_F16) return (int)hipErrorInvalidValue;
+  if (B < 0 || H < 0 || Nq < 0) return (int)hipErrorInvalidValue;
+  if (B == 0 || H == 0 || Nq == 0) return 0;
+  if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15u) || ((uintptr_t)out & 7u)) return (int)hipErrorInvalidValue;
+  if ((q_sb | q_sn | k_sb | k_sn | v_sb | v_sn) % 8 || (o_sb | o_sn) % 4) return (int)hipErrorInvalidValue;
+  ParamsIp pi;
+  Params& p = pi.p;
+  p.q = (const uint16_t*)q, p.k = (const uint16_t*)k, p.v = (const uint16_t*)v, p.o = (uint16_t*)out;
+  p.Nq = Nq, p.Nk = Nt, p.H = H, p.BH = B * H, p.nqb = (Nq + QB * SK_QBLOCKS - 1) / (QB * SK_QBLOCKS);
+  p.q_sb = q_sb, p.q_sn = q_sn, p.k_sb = k_sb, p.k_sn = k_sn, p.v_sb = v_sb, p.v_sn = v_sn, p.o_sb = o_sb, p.o_sn = o_sn;
+  p.scale_log2e = scale * 1.44269504088896340736f;
+  pi.Ni = Ni, pi.ip_scale = ip_scale;
+  const int64_t nb = (int64_t)p.BH * p.nqb;
+  if (nb > 0x7fffffff) return (int)hipErrorInvalidValue;
+  const dim3 grid((unsigned)nb), block(256);
+  hipStream_t st = (hipStream_t)stream;
+#define ED_FIP(NKB)                                                           \
+  if (dtype == ED_BF16) k_flash_attn_ip<BF, NKB><<<grid, block, 0, st>>>(pi); \
+  else k_flash_attn_ip<HF, NKB><<<grid, block, 0, st>>>(pi);
+  if (Nt <= 64) { ED_FIP(2) } else if (Nt <= 96) { ED_FIP(3) } else { ED_FIP(5) }
+#undef ED_FIP
   return (int)hipGetLastError();
 }
 

@@ -1033,6 +1033,25 @@ k_u8_to_vae_input(const uint8_t* __restrict__ img, void* __restrict__ out, int64
   st<Tag>(out, t, vae_input_of(img[3 * p + c]));
 }
 
+// ed_u8_to_clip_input: centre crop + CLIPImageProcessor's rescale and normalise of an already resized picture.
+// One thread per output element; x = float(double(v) * (1 / 255)) -- the processor rescales in fp64 and rounds once to fp32 -- then
+// (x - mean_c) / std_c in fp32, each operation rounded on its own.  256 possible x values per channel: nothing worth vectorising at
+// 3 x 224 x 224 elements once per image.
+__global__ void __launch_bounds__(ED_BLOCK)
+k_u8_to_clip_input(const uint8_t* __restrict__ img, int W, int y0, int x0, int S, float* __restrict__ out, float m0, float m1, float m2,
+                   float s0, float s1, float s2) {
+  int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
+  const int64_t SS = (int64_t)S * S;
+  if (t >= 3 * SS) return;
+  const int c = (int)(t / SS);
+  const int64_t p = t - c * SS;
+  const int y = (int)(p / S), x = (int)(p - (int64_t)y * S);
+  const uint32_t v = img[((int64_t)(y0 + y) * W + (x0 + x)) * 3 + c];
+  const float r = (float)((double)v * (1.0 / 255.0));
+  const float mean = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
+  out[t] = __fdiv_rn(__fsub_rn(r, mean), sd);
+}
+
 // ed_u8_to_vae_input_masked: the same value, or +0.0 where the pixel's mask byte is >= threshold (a select, so the zero has no sign
 // to inherit: DESIGN.md section 22.3).  4 pixels per thread: the 4 mask bytes as one aligned dword.
 __device__ __forceinline__ float vae_input_masked_of(uint32_t v, uint32_t m, uint32_t thr) {
@@ -1634,6 +1653,15 @@ int ed_u8_to_vae_input(const uint8_t* img, int H, int W, void* out, int dtype, v
   } else {
     ED_LAUNCH_T(dtype, k_u8_to_vae_input, 3 * HW, img, out, HW);
   }
+  return done();
+}
+
+int ed_u8_to_clip_input(const uint8_t* img, int H, int W, int y0, int x0, int S, float* out, float mean0, float mean1, float mean2,
+                        float std0, float std1, float std2, void* stream) {
+  if (!img || !out || H < 1 || W < 1 || S < 1 || y0 < 0 || x0 < 0) return (int)hipErrorInvalidValue;
+  if ((int64_t)y0 + S > H || (int64_t)x0 + S > W) return (int)hipErrorInvalidValue;  // the crop lies inside the picture
+  if (!(std0 != 0.0f) || !(std1 != 0.0f) || !(std2 != 0.0f)) return (int)hipErrorInvalidValue;
+  ED_LAUNCH(k_u8_to_clip_input, 3 * (int64_t)S * S, img, W, y0, x0, S, out, mean0, mean1, mean2, std0, std1, std2);
   return done();
 }
 

@@ -492,6 +492,20 @@ class Attention(nn.Module):
         self.to_k = nn.Linear(cross_dim or dim, inner, bias=bias)
         self.to_v = nn.Linear(cross_dim or dim, inner, bias=bias)
         self.to_out = nn.ModuleList([nn.Linear(inner, dim), nn.Dropout(0.0)])
+        # IP-Adapter (UNet2DConditionModel.install_ip_adapter): the last ``ip_tokens`` context rows are
+        # image tokens with projections and a softmax of their own.  0 / None: the attention is what it always was.
+        self.to_k_ip = self.to_v_ip = None
+        self.ip_tokens = 0
+        self.ip_scale = 1.0
+
+    def set_ip_adapter(self, to_k_ip=None, to_v_ip=None, tokens=0):
+        """install (two bias-free Linear(cross_dim, inner) and the image-token count) or, without arguments, remove"""
+        for name, mod in (("to_k_ip", to_k_ip), ("to_v_ip", to_v_ip)):
+            if isinstance(getattr(self, name), nn.Module):
+                delattr(self, name)     # out of _modules, so the key leaves state_dict()
+            setattr(self, name, mod)
+        self.ip_tokens = int(tokens) if to_k_ip is not None else 0
+        self.__dict__.pop("_derived", None)
 
     def _fused_weight(self, names, q_scale=None):
         """cat of the projection weights (bias-free in every SD / SDXL attention).
@@ -514,6 +528,13 @@ class Attention(nn.Module):
         w = self._fused_weight(("to_k", "to_v"))
         if out is None:   # the same library call for the first projection and every refresh: one hipBLASLt solution, same bits
             out = torch.empty(context.shape[:-1] + (w.shape[0],), dtype=context.dtype, device=context.device)
+        if self.ip_tokens:
+            # [text rows | image rows]: the text rows through to_k|to_v, the image rows through to_k_ip|to_v_ip, into one tensor
+            # (rows in the order ed_flash_attention_ip reads them).  Same calls for the first projection and every refresh.
+            nt = context.shape[-2] - self.ip_tokens
+            out[..., :nt, :] = torch.matmul(context[..., :nt, :], w.t())
+            out[..., nt:, :] = torch.matmul(context[..., nt:, :], self._fused_weight(("to_k_ip", "to_v_ip")).t())
+            return out
         torch.matmul(context, w.t(), out=out)
         return out
 
@@ -540,6 +561,19 @@ class Attention(nn.Module):
                     q = linear_(x, self.to_q.weight if c is None else self._fused_weight(("to_q",), c))
                     k, v = self.to_k(x), self.to_v(x)
                 o = ops.flash_attention(q, k, v, self.heads, prescaled=c is not None)
+            elif self.ip_tokens:
+                # decoupled cross attention: one launch where ed_flash_attention_ip takes the shape (head dim 64, <= 160 text keys),
+                # else the two attentions through the existing kernels and a torch axpy (correct, not fused)
+                q = linear_(x, self.to_q.weight)
+                if kv is None:
+                    kv = self.project_kv(context)
+                k, v = kv[..., :inner], kv[..., inner:]
+                nt = kv.shape[1] - self.ip_tokens
+                if ops.flash_attention_ip_ok(inner // self.heads, nt, self.ip_tokens):
+                    o = ops.flash_attention_ip(q, k, v, self.heads, nt, self.ip_scale)
+                else:
+                    o = ops.flash_attention(q, k[:, :nt], v[:, :nt], self.heads)
+                    o = o.add_(ops.flash_attention(q, k[:, nt:], v[:, nt:], self.heads), alpha=self.ip_scale)
             else:
                 q = linear_(x, self.to_q.weight)
                 if kv is not None or FUSED_QKV:
@@ -553,6 +587,14 @@ class Attention(nn.Module):
             return linear_res_(o, self.to_out[0].weight, self.to_out[0].bias, residual)
         ctx = x if context is None else context
         q = self.to_q(x).view(B, N, self.heads, -1).transpose(1, 2)
+        if context is not None and self.ip_tokens:
+            if kv is None:
+                kv = self.project_kv(ctx)
+            nt = kv.shape[1] - self.ip_tokens
+            k, v = (t.reshape(B, kv.shape[1], self.heads, -1).transpose(1, 2) for t in (kv[..., :inner], kv[..., inner:]))
+            o = F.scaled_dot_product_attention(q, k[:, :, :nt], v[:, :, :nt])
+            o = o + self.ip_scale * F.scaled_dot_product_attention(q, k[:, :, nt:], v[:, :, nt:])
+            return self.to_out[0](o.transpose(1, 2).reshape(B, N, -1)), False
         if kv is not None:
             k, v = (t.reshape(B, ctx.shape[1], self.heads, -1).transpose(1, 2) for t in (kv[..., :inner], kv[..., inner:]))
         else:
@@ -834,6 +876,38 @@ class _UpBlock(nn.Module):
         return x
 
 
+class ImageProjection(nn.Module):
+    """The base IP-Adapters' image projection (diffusers' ``ImageProjection``): CLIP image embedding [B, clip_dim] ->
+    LayerNorm(Linear(e).reshape(B, Ni, cross_dim)), the Ni image tokens appended to the text tokens."""
+
+    def __init__(self, clip_dim, cross_dim, tokens):
+        super().__init__()
+        self.tokens, self.cross_dim = tokens, cross_dim
+        self.proj = nn.Linear(clip_dim, tokens * cross_dim)
+        self.norm = nn.LayerNorm(cross_dim)
+
+    def forward(self, embeds):
+        return self.norm(self.proj(embeds).reshape(-1, self.tokens, self.cross_dim))
+
+
+def flatten_ip_adapter_state(state):
+    """An IP-Adapter state dict with flat keys, from either form a file holds: already flat (``image_proj.proj.weight``,
+    ``ip_adapter.1.to_k_ip.weight``: safetensors) or nested ``{"image_proj": {...}, "ip_adapter": {...}}`` (the pickled files)."""
+    if not isinstance(state, dict):
+        raise ValueError(f"IP-Adapter state must be a dict of tensors, got {type(state).__name__}")
+    flat = {}
+    for key, val in state.items():
+        if isinstance(val, dict):
+            for sub, t in val.items():
+                flat[f"{key}.{sub}"] = t
+        else:
+            flat[key] = val
+    bad = [k for k, t in flat.items() if not isinstance(t, torch.Tensor)]
+    if bad:
+        raise ValueError(f"IP-Adapter state holds non-tensor entries: {bad[:4]}")
+    return flat
+
+
 class UNet2DConditionModel(nn.Module):
     def __init__(self, sample_size, in_channels, block_out_channels, layers_per_block, attn, transformer_depth, heads,
                  cross_attention_dim, use_linear_projection, addition_time_embed_dim, pooled_projection_dim,
@@ -867,6 +941,8 @@ class UNet2DConditionModel(nn.Module):
             prev = cout
         self.conv_norm_out = nn.GroupNorm(32, boc[0], eps=1e-5)
         self.conv_out = nn.Conv2d(boc[0], out_channels, 3, padding=1)
+        self.ip_tokens = 0          # IP-Adapter image tokens at the end of the context; 0: no adapter installed
+        self.ip_image_proj = None   # the installed adapter's ImageProjection
 
     @property
     def dtype(self):
@@ -895,12 +971,105 @@ class UNet2DConditionModel(nn.Module):
                 out[id(m.attn2)] = m.attn2.project_kv(ctx, None if into is None else into[id(m.attn2)])
         return out
 
+    # ---- IP-Adapter ---------------------------------------------------------------------------------
+    def ip_attentions(self):
+        """The cross attentions in the order an IP-Adapter file numbers them: ``down_blocks`` by index, then ``up_blocks``, then
+        ``mid_block``; within each ``attentions[i].transformer_blocks[j].attn2``.  The n-th takes ``ip_adapter.{2n+1}.*`` --
+        diffusers' ``attn_processors`` enumeration, whose even indices are the parameter-free self attentions."""
+        out = []
+        for blk in list(self.down_blocks) + list(self.up_blocks) + [self.mid_block]:
+            for tr in (blk.attentions or ()):
+                out.extend(tb.attn2 for tb in tr.transformer_blocks)
+        return out
+
+    @torch.no_grad()
+    def install_ip_adapter(self, state):
+        """Install a base IP-Adapter from its state dict (flat ``image_proj.*`` / ``ip_adapter.*`` keys or the nested
+        ``{"image_proj": {...}, "ip_adapter": {...}}`` form).  Every expected key must be present with a fitting shape and no other
+        key may be: otherwise ValueError, and nothing is installed.  Returns the image-token count."""
+        flat = flatten_ip_adapter_state(state)
+        if any(k.startswith("image_proj.latents") or k.startswith("image_proj.layers.") or k.startswith("image_proj.proj_in")
+               for k in flat):
+            raise ValueError("this is an IP-Adapter 'Plus' / FaceID file (Resampler keys such as image_proj.latents): only the base "
+                             "adapters' ImageProjection (image_proj.proj / image_proj.norm) is supported")
+        attns = self.ip_attentions()
+        cross = self.config.cross_attention_dim
+        proj_w = flat.get("image_proj.proj.weight")
+        if proj_w is None or proj_w.dim() != 2:
+            raise ValueError("IP-Adapter: image_proj.proj.weight is missing or not a matrix")
+        if proj_w.shape[0] % cross or not 1 <= proj_w.shape[0] // cross <= ops.IP_MAX_IMAGE_KEYS:
+            raise ValueError(f"IP-Adapter: image_proj.proj has {proj_w.shape[0]} output features: not 1..{ops.IP_MAX_IMAGE_KEYS} "
+                             f"image tokens of cross-attention width {cross}")
+        ni, clip_dim = proj_w.shape[0] // cross, proj_w.shape[1]
+        expected = {"image_proj.proj.weight": (ni * cross, clip_dim), "image_proj.proj.bias": (ni * cross,),
+                    "image_proj.norm.weight": (cross,), "image_proj.norm.bias": (cross,)}
+        for n, a in enumerate(attns):
+            for name in ("to_k_ip", "to_v_ip"):
+                expected[f"ip_adapter.{2 * n + 1}.{name}.weight"] = (a.to_k.out_features, cross)
+        missing = sorted(set(expected) - set(flat))
+        surplus = sorted(set(flat) - set(expected))
+        wrong = sorted(k for k in expected if k in flat and tuple(flat[k].shape) != expected[k])
+        if missing or surplus or wrong:
+            raise ValueError(f"IP-Adapter does not fit this UNet ({len(attns)} cross attentions, width {cross}): "
+                             f"missing {missing[:4]}, unexpected {surplus[:4]}, "
+                             f"wrong shape {[(k, tuple(flat[k].shape), expected[k]) for k in wrong[:4]]}; nothing installed")
+        like = self.conv_in.weight
+
+        def linear(w, b=None):
+            m = nn.Linear(w.shape[1], w.shape[0], bias=b is not None, device=like.device, dtype=like.dtype)
+            m.weight.copy_(w)
+            if b is not None:
+                m.bias.copy_(b)
+            return m.requires_grad_(False)
+        self.remove_ip_adapter()
+        proj = ImageProjection(clip_dim, cross, ni).to(device=like.device, dtype=like.dtype).requires_grad_(False)
+        proj.proj.weight.copy_(flat["image_proj.proj.weight"]), proj.proj.bias.copy_(flat["image_proj.proj.bias"])
+        proj.norm.weight.copy_(flat["image_proj.norm.weight"]), proj.norm.bias.copy_(flat["image_proj.norm.bias"])
+        self.ip_image_proj = proj
+        for n, a in enumerate(attns):
+            a.set_ip_adapter(linear(flat[f"ip_adapter.{2 * n + 1}.to_k_ip.weight"]),
+                             linear(flat[f"ip_adapter.{2 * n + 1}.to_v_ip.weight"]), ni)
+        self.ip_tokens = ni
+        return ni
+
+    def remove_ip_adapter(self):
+        for a in self.ip_attentions():
+            a.set_ip_adapter()
+        if isinstance(self.ip_image_proj, nn.Module):
+            del self.ip_image_proj
+        self.ip_image_proj = None
+        self.ip_tokens = 0
+
+    @property
+    def ip_scale(self):
+        a = self.ip_attentions()
+        return a[0].ip_scale if a else 1.0
+
+    @ip_scale.setter
+    def ip_scale(self, scale):
+        scale = float(scale)
+        if not math.isfinite(scale):
+            raise ValueError(f"IP-Adapter scale must be finite, got {scale}")
+        for a in self.ip_attentions():
+            a.ip_scale = scale
+
+    @torch.no_grad()
+    def ip_image_tokens(self, clip_embeds):
+        """[B, clip_dim] CLIP image embeddings -> [B, Ni, cross_dim] image tokens (a zero embedding gives the unconditional ones)"""
+        if self.ip_image_proj is None:
+            raise ValueError("no IP-Adapter is installed")
+        p = self.ip_image_proj.proj.weight
+        return self.ip_image_proj(clip_embeds.to(device=p.device, dtype=p.dtype))
+
     def forward(self, sample, timestep, encoder_hidden_states=None, added_cond_kwargs=None,
                 down_block_additional_residuals=None, mid_block_additional_residual=None, cross_kv=None, **_):
         x = sample.to(self.dtype)
         if CHANNELS_LAST and x.is_cuda and x.dtype != torch.float32:
             x = x.contiguous(memory_format=torch.channels_last)
         ctx = encoder_hidden_states.to(self.dtype)
+        if self.ip_tokens and ctx.shape[1] <= self.ip_tokens:
+            raise ValueError(f"an IP-Adapter with {self.ip_tokens} image tokens is installed: the context must be [text tokens | image "
+                             f"tokens], got {ctx.shape[1]} tokens in all")
         emb = self.embed(x, timestep, added_cond_kwargs)
         x = self.conv_in(x)
         if getattr(self, "residual_fp32", False) and x.dtype != torch.float32:

@@ -1230,6 +1230,48 @@ def flash_attention(q, k, v, heads, v_path=None, prescaled=False):
     return out
 
 
+IP_MAX_TEXT_KEYS = SMALLKV_MAX_KEYS   # ed_flash_attention_ip: five text blocks of 32 keys ...
+IP_MAX_IMAGE_KEYS = 32                # ... and one image block
+
+
+def flash_attention_ip_ok(head_dim, n_text, n_image):
+    """does ed_flash_attention_ip take this shape?  (models.Attention runs two attentions and a torch axpy otherwise)"""
+    return head_dim == 64 and 1 <= n_text <= IP_MAX_TEXT_KEYS and 1 <= n_image <= IP_MAX_IMAGE_KEYS
+
+
+def flash_attention_ip(q, k, v, heads, n_text, ip_scale):
+    """IP-Adapter decoupled cross attention in one launch: q [B,Nq,H*64], k / v [B,Nt+Ni,H*64] 16-bit with
+    the ``n_text`` = Nt text rows first and the Ni image rows (``to_k_ip`` / ``to_v_ip`` of the image tokens) behind them; strides
+    as ``flash_attention`` -> softmax(q k_t^T / 8) v_t + ip_scale * softmax(q k_i^T / 8) v_i, contiguous [B,Nq,H*64].
+    1 <= Nt <= 160, 1 <= Ni <= 32, head dim 64.  See ed_flash_attention_ip."""
+    B, Nq, HD = q.shape
+    N = k.shape[1]
+    hd = HD // heads
+    n_text, ip_scale = int(n_text), float(ip_scale)
+    if HD != heads * hd or hd != 64 or k.shape != (B, N, HD) or v.shape != (B, N, HD):
+        _reject(f"flash_attention_ip: head_dim must be 64 and shapes consistent (q {tuple(q.shape)}, k {tuple(k.shape)}, "
+                f"v {tuple(v.shape)}, heads {heads})")
+    if not flash_attention_ip_ok(hd, n_text, N - n_text):
+        _reject(f"flash_attention_ip: needs 1 <= text keys <= {IP_MAX_TEXT_KEYS} and 1 <= image keys <= {IP_MAX_IMAGE_KEYS}, "
+                f"got {n_text} and {N - n_text}")
+    if ip_scale != ip_scale or ip_scale in (float("inf"), float("-inf")):
+        _reject(f"flash_attention_ip: ip_scale must be finite, got {ip_scale}")
+    for t, name in ((q, "q"), (k, "k"), (v, "v")):
+        if not t.is_cuda or t.dtype != q.dtype or t.dtype not in (torch.float16, torch.bfloat16) or t.stride(2) != 1:
+            _reject(f"flash_attention_ip: {name} must be a 16-bit tensor on the MI355X with unit last stride; no CPU fallback")
+        if _LAUNCH["device"] is None:
+            _LAUNCH["device"] = t.device
+        elif _LAUNCH["device"] != t.device:
+            _reject(f"flash_attention_ip: {name} lives on {t.device}, q on {_LAUNCH['device']}")
+    out = torch.empty(B, Nq, HD, dtype=q.dtype, device=q.device)
+    TIMER.note_work("ed_flash_attention_ip", flops=4.0 * B * heads * Nq * N * hd,
+                    nbytes=2.0 * q.element_size() * HD * B * (Nq + N))
+    _call("ed_flash_attention_ip", q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _code(q, "q"), B, heads, Nq, n_text,
+          N - n_text, hd, q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0), out.stride(1),
+          hd ** -0.5, ip_scale, _stream())
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # Canny condition extraction (csrc/canny_kernels.hip): pre-processing of one image before the loop, never graph-captured
 # ---------------------------------------------------------------------------------------------------------------------
@@ -1443,6 +1485,36 @@ def u8_to_vae_input_masked(img, mask, dtype=torch.float32, threshold=128):
     _call("ed_u8_to_vae_input_masked", p_img, _dev(mask, torch.uint8, "mask"), threshold, H, W, _dev(out, dtype, "out"),
           _DTYPE[dtype], _stream())
     TIMER.note_work("ed_u8_to_vae_input_masked", nbytes=float(H * W * (4 + 3 * out.element_size())))
+    return out
+
+
+CLIP_IMAGE_MEAN = (0.48145466, 0.4578275, 0.40821073)   # transformers' OPENAI_CLIP_MEAN / OPENAI_CLIP_STD
+CLIP_IMAGE_STD = (0.26862954, 0.26130258, 0.27577711)
+
+
+def clip_resize_size(H, W, size=224):
+    """(H', W') of CLIPImageProcessor's resize: the shortest edge becomes ``size``, the long one int(size * long / short)."""
+    short, long = (H, W) if H <= W else (W, H)
+    new_long = int(size * long / short)
+    return (size, new_long) if H <= W else (new_long, size)
+
+
+def u8_to_clip_input(img, size=224, mean=CLIP_IMAGE_MEAN, std=CLIP_IMAGE_STD):
+    """img uint8 [H,W,3] (RGB, contiguous, both sides >= ``size``: the output of ``resize_u8`` to ``clip_resize_size``) ->
+    fp32 [1,3,size,size]: CLIPImageProcessor's centre crop, rescale and normalise in one launch.  See ed_u8_to_clip_input."""
+    p_img = _dev(img, torch.uint8, "img")
+    if img.dim() != 3 or img.shape[2] != 3:
+        _reject(f"img must be uint8 [H,W,3], got {tuple(img.shape)}")
+    H, W, size = int(img.shape[0]), int(img.shape[1]), int(size)
+    if not (1 <= size <= H <= VAE_INPUT_MAX_DIM and size <= W <= VAE_INPUT_MAX_DIM):
+        _reject(f"u8_to_clip_input: needs 1 <= size <= H, W <= {VAE_INPUT_MAX_DIM}, got size {size} and {H} x {W}")
+    mean, std = [float(m) for m in mean], [float(s) for s in std]
+    if len(mean) != 3 or len(std) != 3 or not all(s > 0 for s in std):
+        _reject("u8_to_clip_input: mean and std are three numbers each, std positive")
+    y0, x0 = (H - size) // 2, (W - size) // 2   # transformers' center_crop: top = (H - size) // 2, left = (W - size) // 2
+    out = torch.empty((1, 3, size, size), dtype=torch.float32, device=img.device)
+    _call("ed_u8_to_clip_input", p_img, H, W, y0, x0, size, _dev(out, torch.float32, "out"), *mean, *std, _stream())
+    TIMER.note_work("ed_u8_to_clip_input", nbytes=float(3 * size * size * 5))
     return out
 
 

@@ -130,6 +130,49 @@ def check_inpaint_unet_arguments(in_channels, init_image=None, mask_image=None, 
     return True
 
 
+def check_ip_adapter_arguments(loaded, has_image_encoder, ip_adapter_image=None, ip_adapter_image_embeds=None):
+    """The argument rules of ``ip_adapter_image`` / ``ip_adapter_image_embeds``, pure host code that runs
+    before anything is launched -> does this run carry an image prompt?  ValueError: an adapter is loaded and no image is given
+    (or both forms are), an image is given without an adapter, ``ip_adapter_image`` without an image encoder."""
+    given = (ip_adapter_image is not None) + (ip_adapter_image_embeds is not None)
+    if not loaded:
+        if given:
+            raise ValueError("ip_adapter_image / ip_adapter_image_embeds given but no IP-Adapter is loaded (load_ip_adapter)")
+        return False
+    if given != 1:
+        raise ValueError("an IP-Adapter is loaded: every image needs exactly one of ip_adapter_image / ip_adapter_image_embeds "
+                         f"({'both' if given else 'neither'} given); unload_ip_adapter() goes back to text-only generation")
+    if ip_adapter_image is not None:
+        if not has_image_encoder:
+            raise ValueError("ip_adapter_image needs the image_encoder given to load_ip_adapter (a CLIP vision model); without one "
+                             "pass ip_adapter_image_embeds")
+        if not _is_8bit_picture(ip_adapter_image, 3):
+            raise ValueError("ip_adapter_image must be an RGB PIL image or a uint8 [H,W,3] array / tensor, got "
+                             f"{type(ip_adapter_image).__name__}")
+    elif not isinstance(ip_adapter_image_embeds, torch.Tensor) or ip_adapter_image_embeds.dim() != 2:
+        raise ValueError("ip_adapter_image_embeds must be a [1 or B, clip_dim] tensor, got "
+                         f"{tuple(getattr(ip_adapter_image_embeds, 'shape', ())) or type(ip_adapter_image_embeds).__name__}")
+    return True
+
+
+def read_ip_adapter(source):
+    """-> (flat state dict, name) of an IP-Adapter: a ``*.safetensors`` file with flat ``image_proj.*`` / ``ip_adapter.*`` keys, a
+    ``*.bin`` / ``*.pt`` file holding the nested ``{"image_proj": {...}, "ip_adapter": {...}}`` form (read with
+    ``torch.load(weights_only=True)``), or a state dict in either form."""
+    import os
+    from .models import flatten_ip_adapter_state
+    if isinstance(source, dict):
+        return flatten_ip_adapter_state(source), "ip_adapter"
+    path = os.fspath(source)
+    name = os.path.splitext(os.path.basename(path))[0]
+    if path.endswith(".safetensors"):
+        from safetensors.torch import load_file
+        return flatten_ip_adapter_state(load_file(path, device="cpu")), name
+    if path.endswith((".bin", ".pt", ".pth")):
+        return flatten_ip_adapter_state(torch.load(path, map_location="cpu", weights_only=True)), name
+    raise ValueError(f"IP-Adapter file must be *.safetensors, *.bin or *.pt, got {path!r}")
+
+
 def _is_8bit_picture(image, channels):
     """is ``image`` what ``_u8_image`` takes as an 8-bit picture: a PIL image or a uint8 array / tensor [H,W,channels]?"""
     if hasattr(image, "convert"):
@@ -459,6 +502,115 @@ class ElasticDiffusion(nn.Module):
         st = self.__dict__.get("_lora")
         return [] if st is None else st.listing()
 
+    # ---- IP-Adapter image prompts ------------------------------------------------
+    def _ip_change(self, fn):
+        """One change of IP-Adapter state: the context grows or shrinks by the image tokens and the scale is a kernel argument a
+        captured graph holds by value, so the graphs are dropped and the hoisted k|v re-projected, as ``_lora_change`` does."""
+        if self.__dict__.get("_live_jobs"):
+            raise RuntimeError("IP-Adapter state cannot change while generate_latents_interleaved has images in flight")
+        with torch.cuda.device(self.device):
+            out = fn()
+        self._runner.entries.clear()
+        self._runner.new_image()
+        return out
+
+    @staticmethod
+    def _image_encoder_callable(image_encoder, device):
+        """``image_encoder`` of ``load_ip_adapter`` -> callable pixel_values [1,3,S,S] fp32 -> [1, clip_dim] embeddings (or None)"""
+        if image_encoder is None:
+            return None
+        if isinstance(image_encoder, (str, bytes)) or hasattr(image_encoder, "__fspath__"):
+            from transformers import CLIPVisionModelWithProjection    # the encoder stays a library model (DESIGN.md section 9)
+            image_encoder = CLIPVisionModelWithProjection.from_pretrained(image_encoder, local_files_only=True)
+        if isinstance(image_encoder, nn.Module) and hasattr(image_encoder, "config") and hasattr(image_encoder.config, "projection_dim"):
+            model = image_encoder.to(device).eval()
+            dt = next(model.parameters()).dtype
+            return lambda pixels: model(pixel_values=pixels.to(dt)).image_embeds
+        if not callable(image_encoder):
+            raise ValueError("image_encoder must be a callable pixel_values -> embeds, a transformers.CLIPVisionModelWithProjection "
+                             f"or a local directory of one, got {type(image_encoder).__name__}")
+        return image_encoder
+
+    @torch.no_grad()
+    def load_ip_adapter(self, source, scale=1.0, image_encoder=None):
+        """Install a base IP-Adapter (``read_ip_adapter``'s sources) into the UNet's cross attentions at ``scale``; every key must
+        fit or nothing is installed (``UNet2DConditionModel.install_ip_adapter``).  ``image_encoder``: what turns
+        ``ip_adapter_image`` into CLIP image embeddings -- a callable pixel_values -> embeds, a
+        ``transformers.CLIPVisionModelWithProjection`` or a local directory of one; without it only
+        ``ip_adapter_image_embeds`` can be given.  One adapter at a time: a second call replaces the first.  Returns its name."""
+        if not hasattr(self.unet, "install_ip_adapter"):
+            raise ValueError(f"this pipeline's UNet ({type(self.unet).__name__}) cannot carry an IP-Adapter")
+        scale = float(scale)
+        if not math.isfinite(scale):
+            raise ValueError(f"IP-Adapter scale must be finite, got {scale}")
+        state, name = read_ip_adapter(source)
+        enc = self._image_encoder_callable(image_encoder, self.device)
+
+        def change():
+            self.unet.install_ip_adapter(state)
+            self.unet.ip_scale = scale
+            self.unet = self._model_layout(self.unet)
+            self._ip = {"name": name, "encoder": enc}
+        self._ip_change(change)
+        return name
+
+    def set_ip_adapter_scale(self, scale):
+        """New weight of the image prompt (0 = the text-only result, bit for bit where the fused kernel runs)"""
+        if self.ip_adapter is None:
+            raise ValueError("no IP-Adapter is loaded")
+
+        def change():
+            self.unet.ip_scale = scale
+        self._ip_change(change)
+
+    def unload_ip_adapter(self):
+        if self.ip_adapter is None:
+            return
+
+        def change():
+            self.unet.remove_ip_adapter()
+            self._ip = None
+        self._ip_change(change)
+
+    @property
+    def ip_adapter(self):
+        """None | (name, scale, image tokens)"""
+        st = self.__dict__.get("_ip")
+        return None if not st else (st["name"], self.unet.ip_scale, self.unet.ip_tokens)
+
+    def _check_ip_adapter(self, ip_adapter_image=None, ip_adapter_image_embeds=None):
+        st = self.__dict__.get("_ip")
+        return check_ip_adapter_arguments(bool(st), bool(st and st["encoder"] is not None), ip_adapter_image,
+                                          ip_adapter_image_embeds)
+
+    def _clip_pixels(self, image, size=224):
+        """``ip_adapter_image`` -> CLIPImageProcessor's pixel_values [1,3,size,size] fp32, on the device: one upload, Pillow's
+        bicubic resize of the shortest edge to ``size`` (``ops.resize_u8``), then centre crop and normalise in one launch."""
+        u8 = self._u8_image(image, 3, "ip_adapter_image")
+        if isinstance(u8, np.ndarray):
+            u8 = torch.from_numpy(np.ascontiguousarray(u8))
+        u8 = u8.to(self.device).contiguous()
+        H, W = int(u8.shape[0]), int(u8.shape[1])
+        new = ops.clip_resize_size(H, W, size)
+        if not all(1 <= n <= ops.RESIZE_MAX_DIM for n in (H, W) + new):
+            raise ValueError(f"ip_adapter_image: cannot resize {(H, W)} to {new} (sides up to {ops.RESIZE_MAX_DIM})")
+        if new != (H, W):
+            u8 = ops.resize_u8(u8, new, "bicubic")
+        return ops.u8_to_clip_input(u8, size)
+
+    def _ip_tokens(self, B, ip_adapter_image=None, ip_adapter_image_embeds=None):
+        """-> (unconditional, conditional) image tokens [B, Ni, cross_dim]: the projection of a zero embedding and of the picture's"""
+        if ip_adapter_image is not None:
+            embeds = self._ip["encoder"](self._clip_pixels(ip_adapter_image))
+        else:
+            embeds = ip_adapter_image_embeds
+        embeds = torch.as_tensor(embeds).to(self.device)
+        clip_dim = self.unet.ip_image_proj.proj.in_features
+        if embeds.dim() != 2 or embeds.shape[0] not in (1, B) or embeds.shape[1] != clip_dim:
+            raise ValueError(f"image embeddings must be [1 or {B}, {clip_dim}], got {tuple(embeds.shape)}")
+        embeds = embeds.expand(B, -1)
+        return self.unet.ip_image_tokens(torch.zeros_like(embeds)), self.unet.ip_image_tokens(embeds)
+
     @torch.no_grad()
     def get_text_embeds(self, prompt, min_chunks=None):
         """ED:254-265.  With no CLIP weights available the default is a deterministic synthetic embedding per prompt
@@ -614,8 +766,13 @@ class ElasticDiffusion(nn.Module):
         # the captured graph cannot read it, but the runner's entries are dropped when the ControlNet changes (set_controlnet)
         out["unet"] = self.unet.cross_attention_kv(txt, out.get("unet"))
         if self.controlnet is not None and hasattr(self.controlnet, "cross_attention_kv"):
-            out["controlnet"] = self.controlnet.cross_attention_kv(txt, out.get("controlnet"))
+            out["controlnet"] = self.controlnet.cross_attention_kv(self._text_part(txt), out.get("controlnet"))
         return out
+
+    def _text_part(self, txt):
+        """The rows a ControlNet is handed: the text tokens alone -- an IP-Adapter's image tokens are the UNet's (section 24)"""
+        ni = getattr(self.unet, "ip_tokens", 0)
+        return txt[:, :txt.shape[1] - ni].contiguous() if ni else txt
 
     def _forward_rows(self, x, t_dev, txt, pl, cond, text_kv=None):
         """ED:413-426 / EDC:476-518 for an arbitrary batch of d x d rows (this is what a hipGraph captures)."""
@@ -628,7 +785,7 @@ class ElasticDiffusion(nn.Module):
             ckw["cross_kv"] = text_kv.get("controlnet")
         if cond is not None:
             cn_kw = {k: v for k, v in kw.items() if k != "cross_kv"}
-            down, mid = self.controlnet(x, t_dev, encoder_hidden_states=txt, controlnet_cond=cond,
+            down, mid = self.controlnet(x, t_dev, encoder_hidden_states=self._text_part(txt), controlnet_cond=cond,
                                         conditioning_scale=self._cn_scale, guess_mode=False, return_dict=False, **cn_kw, **ckw)
             kw["down_block_additional_residuals"], kw["mid_block_additional_residual"] = down, mid
         return self.unet(x, t_dev, encoder_hidden_states=txt, **kw)["sample"].contiguous()
@@ -1062,7 +1219,7 @@ class ElasticDiffusion(nn.Module):
 
     def _program(self, S, prompts, negative_prompts, condition_image=None, trace=None, progress=_identity_progress,
                  direct=True, frames=None, init_image=None, mask_image=None, mask_blur=0.0, mask_mode="binary",
-                 min_chunks=None):
+                 min_chunks=None, ip_adapter_image=None, ip_adapter_image_embeds=None):
         """Generator: the denoising loop of ONE image (ED:981-1078), yielding ``_ModelCall``s; returns the final latent.
         All host RNG draws happen inside, in the reference's order.  ``init_image`` / ``mask_image``: image-to-image and
         inpainting -- the loop starts at timestep index ``S.t_start`` from the noised encoding of the
@@ -1083,6 +1240,12 @@ class ElasticDiffusion(nn.Module):
             raise ValueError(f"text_encoder returned {co.shape[1]} tokens for the prompts and {un.shape[1]} for the negative "
                              "prompts: the two are rows of one model batch and must have the same token count")
         B = len(prompts)
+        if ip_adapter_image is not None or ip_adapter_image_embeds is not None:
+            # image prompt: the context of every row is [text tokens | image tokens] -- conditional rows carry the picture's tokens,
+            # unconditional rows (the V view rows among them, through _embed_rows) the projection of a zero embedding
+            iun, ico = self._ip_tokens(B, ip_adapter_image, ip_adapter_image_embeds)
+            un = torch.cat([un, iun.to(un.dtype)], dim=1)
+            co = torch.cat([co, ico.to(co.dtype)], dim=1)
         # initial latent from the host generator (ED:998-1000)
         z0 = noise0 = mask = None
         graded = mask_mode == "graded"
@@ -1165,7 +1328,7 @@ class ElasticDiffusion(nn.Module):
                          rrg_scherduler_cls=CosineScheduler, cosine_scale=3.0, repaint_sampling=True,
                          progress=_identity_progress, condition_image=None, controlnet_conditioning_scale=1.0,
                          trace=None, guidance_rescale=0.0, init_image=None, strength=1.0, mask_image=None, *, mask_blur=0.0,
-                         mask_mode="binary", min_chunks=None):
+                         mask_mode="binary", min_chunks=None, ip_adapter_image=None, ip_adapter_image_embeds=None):
         """``guidance_rescale`` in [0, 1] (diffusers' keyword; 0 = off): the std rescale of the guided model output of
         arXiv 2305.08891 section 3.4, what zero-terminal-SNR / v-prediction checkpoints are meant to be sampled with
         (DESIGN.md section 17).
@@ -1193,7 +1356,13 @@ class ElasticDiffusion(nn.Module):
         A UNet with 9 input channels (an inpainting checkpoint) needs an 8-bit ``init_image`` and picture
         ``mask_image``: every model row is ``cat([latent, mask, masked-image latent])`` with the extras sampled where the row's
         latent was (``ops.assemble_rows_x``), one more host draw is made for the masked-image latent
-        (``last_masked_image_latents``), and the kept region is NOT pasted back in latent space."""
+        (``last_masked_image_latents``), and the kept region is NOT pasted back in latent space.
+
+        ``ip_adapter_image`` / ``ip_adapter_image_embeds`` (keyword-only): the image prompt of a loaded
+        IP-Adapter (``load_ip_adapter``), exactly one of the two -- an RGB PIL image / uint8 [H,W,3] array or tensor (uploaded
+        once; CLIP's resize, crop and normalise run on the device, then the ``image_encoder``), or its CLIP image embeddings
+        [1 or B, clip_dim]."""
+        self._check_ip_adapter(ip_adapter_image, ip_adapter_image_embeds)
         check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
         mask_blur = check_soft_inpaint_arguments(init_image, mask_image, mask_blur, mask_mode,
                                                  latent_size=(height // self.vae_scale_factor, width // self.vae_scale_factor))
@@ -1204,7 +1373,8 @@ class ElasticDiffusion(nn.Module):
         self._runner.new_image()
         x = self._drive(self._program(S, prompts, negative_prompts, condition_image, trace, progress, direct=True,
                                       init_image=init_image, mask_image=mask_image, mask_blur=mask_blur, mask_mode=mask_mode,
-                                      min_chunks=min_chunks))
+                                      min_chunks=min_chunks, ip_adapter_image=ip_adapter_image,
+                                      ip_adapter_image_embeds=ip_adapter_image_embeds))
         self.last_latents = x
         self.host_s["blocked_ahead_of_gpu"] = self._stager.waited
         self._mark("loop_done")
@@ -1220,7 +1390,7 @@ class ElasticDiffusion(nn.Module):
         """Several images of the SAME size / settings in flight at once (new; the reference has nothing like it).
 
         ``jobs`` = list of dicts {prompts, negative_prompts="", seed, condition_image=None, init_image=None,
-        mask_image=None, mask_blur=0.0, mask_mode="binary"}; ``strength`` is a setting of the call like the other schedule parameters, and jobs with and without
+        mask_image=None, mask_blur=0.0, mask_mode="binary", ip_adapter_image=None, ip_adapter_image_embeds=None}; ``strength`` is a setting of the call like the other schedule parameters, and jobs with and without
         an init image may mix (at ``strength`` 1: below it every job needs one; on a 9-channel inpainting UNet every job carries
         both ``init_image`` and ``mask_image``).  Each job is one
         ``_program`` with its own host RNG stream (``_HostRng``: exactly the stream ``seed_everything(seed)`` +
@@ -1235,6 +1405,12 @@ class ElasticDiffusion(nn.Module):
         Prompt length: the rows of all jobs share one text tensor, so with a chunking ``text_encoder`` every job is encoded to
         n chunks, n = the largest chunk count over the prompts and negative prompts of ALL jobs of the call: a job equals the
         same job run alone through ``generate_latents(..., min_chunks=n)``."""
+        carrying = [job.get("ip_adapter_image") is not None or job.get("ip_adapter_image_embeds") is not None for job in jobs]
+        if any(carrying) and not all(carrying):
+            raise ValueError("either every job of a call carries an image prompt (ip_adapter_image / ip_adapter_image_embeds) or "
+                             "none does: the rows of all jobs share one context width")
+        for job in jobs:
+            self._check_ip_adapter(job.get("ip_adapter_image"), job.get("ip_adapter_image_embeds"))
         n_chunks = None
         for job in jobs:
             n = self._prompt_chunks(job["prompts"], job.get("negative_prompts", ""))
@@ -1276,7 +1452,9 @@ class ElasticDiffusion(nn.Module):
             prog = self._program(S, job["prompts"], job.get("negative_prompts", ""), job.get("condition_image"),
                                  direct=False, frames=frames, init_image=job.get("init_image"),
                                  mask_image=job.get("mask_image"), mask_blur=float(job.get("mask_blur", 0.0)),
-                                 mask_mode=job.get("mask_mode", "binary"), min_chunks=n_chunks)
+                                 mask_mode=job.get("mask_mode", "binary"), min_chunks=n_chunks,
+                                 ip_adapter_image=job.get("ip_adapter_image"),
+                                 ip_adapter_image_embeds=job.get("ip_adapter_image_embeds"))
             with rng:
                 call = next(prog)
             live.append([j, prog, rng, call])
@@ -1464,13 +1642,16 @@ class ElasticDiffusion(nn.Module):
                        rrg_scherduler_cls=CosineScheduler, cosine_scale=3.0, repaint_sampling=True,
                        progress=_default_progress, tiled_decoder=False, grid=False, guidance_rescale=0.0, *,
                        condition_image=None, controlnet_conditioning_scale=1.0, output_type="pil", init_image=None,
-                       strength=1.0, mask_image=None, mask_blur=0.0, mask_mode="binary", composite=False):
+                       strength=1.0, mask_image=None, mask_blur=0.0, mask_mode="binary", composite=False,
+                       ip_adapter_image=None, ip_adapter_image_embeds=None):
         """ED:953-965 signature (ControlNet keywords of EDC:1120-1134 are keyword-only here), then ``guidance_rescale``
         (diffusers' keyword) and, keyword-only, ``init_image`` / ``strength`` / ``mask_image`` / ``mask_blur`` / ``mask_mode``
         (see ``generate_latents``) and ``composite``: paste every decoded picture over the 8-bit init picture through the
         (blurred) pixel mask, ``PIL.Image.composite``'s bytes, in the launch that converts the floats to 8 bit
         (``ops.composite_u8``) -- where the mask is 0 the result IS the init picture.
+        ``ip_adapter_image`` / ``ip_adapter_image_embeds``: the image prompt of a loaded IP-Adapter (see ``generate_latents``).
         Returns ``(images, image_log)``; images are PIL by default, a float tensor with ``output_type='pt'``."""
+        self._check_ip_adapter(ip_adapter_image, ip_adapter_image_embeds)
         check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
         check_soft_inpaint_arguments(init_image, mask_image, mask_blur, mask_mode, composite, output_type, grid,
                                      latent_size=(height // self.vae_scale_factor, width // self.vae_scale_factor))
@@ -1479,7 +1660,8 @@ class ElasticDiffusion(nn.Module):
                                   resampling_steps, new_p, rrg_stop_t, rrg_init_weight, rrg_scherduler_cls,
                                   cosine_scale, repaint_sampling, progress, condition_image,
                                   controlnet_conditioning_scale, guidance_rescale=guidance_rescale, init_image=init_image,
-                                  strength=strength, mask_image=mask_image, mask_blur=mask_blur, mask_mode=mask_mode)
+                                  strength=strength, mask_image=mask_image, mask_blur=mask_blur, mask_mode=mask_mode,
+                                  ip_adapter_image=ip_adapter_image, ip_adapter_image_embeds=ip_adapter_image_embeds)
         dec = self.tiled_decode if tiled_decoder else self.decode_latents
         image_log = self._image_log(dec, guidance_scale, guidance_rescale) if self.verbose else {}  # ED:1092-1118 (before the final decode)
         imgs = torch.cat([dec(z[i:i + 1]) for i in range(len(z))])  # decode_bs = 1 (ED:1090, 1121)
@@ -1655,7 +1837,8 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
                        rrg_scherduler_cls=CosineScheduler, cosine_scale=3.0, repaint_sampling=True,
                        progress=_default_progress, tiled_decoder=False, grid=False, guidance_rescale=0.0, *,
                        output_type="pil", init_image=None, strength=1.0, mask_image=None, mask_blur=0.0, mask_mode="binary",
-                       composite=False):
+                       composite=False, ip_adapter_image=None, ip_adapter_image_embeds=None):
+        self._check_ip_adapter(ip_adapter_image, ip_adapter_image_embeds)
         check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
         check_soft_inpaint_arguments(init_image, mask_image, mask_blur, mask_mode, composite, output_type, grid,
                                      latent_size=(height // self.vae_scale_factor, width // self.vae_scale_factor))
@@ -1670,4 +1853,5 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
                                       cosine_scale, repaint_sampling, progress, tiled_decoder, grid, guidance_rescale,
                                       condition_image=cond, controlnet_conditioning_scale=controlnet_conditioning_scale,
                                       output_type=output_type, init_image=init_image, strength=strength,
-                                      mask_image=mask_image, mask_blur=mask_blur, mask_mode=mask_mode, composite=composite)
+                                      mask_image=mask_image, mask_blur=mask_blur, mask_mode=mask_mode, composite=composite,
+                                      ip_adapter_image=ip_adapter_image, ip_adapter_image_embeds=ip_adapter_image_embeds)

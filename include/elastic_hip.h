@@ -473,6 +473,22 @@ int ed_flash_attention(const void* q, const void* k, const void* v, void* out, i
                        int64_t o_sb, int64_t o_sn, float scale, int v_path, void* stream);
 
 /*
+ * ed_flash_attention_ip -- IP-Adapter decoupled cross attention in one launch (an addition, no
+ * signature change, so still ABI v13):
+ *       out = softmax(q k_t^T scale) v_t + ip_scale * softmax(q k_i^T scale) v_i
+ *   k, v dtype [B, Nt + Ni, H, 64]: the Nt text rows first, then the Ni image rows (to_k_ip / to_v_ip projections of the image
+ *   tokens); q, out, dtype, strides and alignment as ed_flash_attention.  head_dim = 64 only, 1 <= Nt <= 160, 1 <= Ni <= 32;
+ *   anything else returns hipErrorInvalidValue before any launch.  A sibling of the small-KV kernel (v_path 8): text keys in 2 / 3 /
+ *   5 blocks of 32 for Nt <= 64 / 96 / 160 and the image keys in one further block, two independent single-pass softmaxes, two
+ *   fp32 accumulators, combined as fl(o_t * inv_t) + fl(ip_scale * fl(o_i * inv_i)) and rounded once to dtype.  The text term is
+ *   the small-KV kernel's operation for operation: at ip_scale = 0 the output equals ed_flash_attention(v_path 8) on the text rows
+ *   alone bit for bit.
+ */
+int ed_flash_attention_ip(const void* q, const void* k, const void* v, void* out, int dtype, int B, int H, int Nq, int Nt, int Ni,
+                          int head_dim, int64_t q_sb, int64_t q_sn, int64_t k_sb, int64_t k_sn, int64_t v_sb, int64_t v_sn,
+                          int64_t o_sb, int64_t o_sn, float scale, float ip_scale, void* stream);
+
+/*
  * ed_groupnorm_f32 -- GroupNorm (+SiLU) of an fp32 NCHW activation: the VAE's normalisation layers (AutoencoderKL inside
  * ED:270 decode / ED:350 encode; fp32 like the reference keeps it, ED:328).  HW % 4 == 0.  Two launches: partial sums over
  * 64 K-element chunks of every (sample, group), then an apply pass whose blocks combine their group's partials in double.
@@ -650,6 +666,11 @@ int ed_resize_cols_u8(const uint8_t* src, int H, int WC_bytes, int src_pitch, co
  *   side not taken is never combined arithmetically.  out may be x (in place).
  */
 int ed_u8_to_vae_input(const uint8_t* img, int H, int W, void* out, int dtype, void* stream);
+/* ed_u8_to_clip_input -- CLIPImageProcessor after its resize: centre crop, rescale, normalise in one launch.
+ *   img uint8 [H, W, 3] (interleaved RGB), crop origin (y0, x0) with y0 + S <= H and x0 + S <= W (else hipErrorInvalidValue),
+ *   out f32 [3, S, S] (planar) = (float(double(v) * (1 / 255)) - mean_c) / std_c, the subtraction and the division in fp32. */
+int ed_u8_to_clip_input(const uint8_t* img, int H, int W, int y0, int x0, int S, float* out, float mean0, float mean1, float mean2,
+                        float std0, float std1, float std2, void* stream);
 int ed_img2img_init(const void* mean, const void* std, int dtype, const float* eps, const float* noise, float sf, float a,
                     float b, float* z0, float* x, int64_t n, void* stream);
 int ed_mask_to_latent(const uint8_t* src, int H, int W, int scale, int threshold, uint8_t* mask, int Hl, int Wl, void* stream);
