@@ -112,6 +112,10 @@ SIGNATURES = {
     "ed_lora_merge": [_vp, _vp, _i, _i, _i64, _vp],
     "ed_flash_attention_ip": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f, _f, _vp],
     "ed_u8_to_clip_input": [_vp, _i, _i, _i, _i, _i, _vp, _f, _f, _f, _f, _f, _f, _vp],
+    "ed_cfg_ddim_step_ms": [_vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _i64, _i, _vp, _f, _f, _i, _vp, _vp],
+    "ed_phase_epilogue_ms": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                             _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f,
+                             _f, _f, _f, _f, _i, _vp, _vp, _f, _f, _vp, _vp],
 }
 
 _LIB = None

@@ -477,43 +477,64 @@ __device__ __forceinline__ float rescaled(float m, float r, float gr, float omgr
   return __fadd_rn(__fmul_rn(gr, __fmul_rn(m, r)), __fmul_rn(omgr, m));
 }
 
-template <bool VP, bool GR = false>
+// The step variant (compile-time): ST_DDIM is the eta = 0 DDIM update and the code it was before the variant
+// existed.  ST_MS1 / ST_MS2 are DPM-Solver++(2M), midpoint form, first / second order: x0 is the same pred_x0 of the same guided
+// output, and with the host's scalars c_x = sigma_prev / sigma_t (in `sp`), b = alpha_prev * (exp(-h) - 1) (in `sd`), hb = 0.5 * b and
+// r_inv = h / h0:   prev = (c_x * x - b * x0) - hb * (r_inv * (x0 - x0_hist)),   left to right, every product rounded on its own; the
+// first-order form stops after the first bracket and never reads the history.  Which of the two runs is the host's choice per launch.
+enum { ST_DDIM = 0, ST_MS1 = 1, ST_MS2 = 2 };
+
+struct Multistep {
+  const float* x0_hist;  // the previous timestep's x0 at the output element's index (ST_MS2 only)
+  float hb, r_inv;
+};
+
+template <bool VP, bool GR = false, int ST = ST_DDIM>
 __device__ __forceinline__ void ddim_one(float l, float d, float xv, float g, float sb, float sa, float sp, float sd,
-                                         float& prev, float& x0, float r = 0.0f, float gr = 0.0f, float omgr = 0.0f) {
+                                         float& prev, float& x0, float r = 0.0f, float gr = 0.0f, float omgr = 0.0f,
+                                         float x0h = 0.0f, float hb = 0.0f, float r_inv = 0.0f) {
   float m = rescaled<GR>(__fadd_rn(l, __fmul_rn(g, d)), r, gr, omgr);
   x0 = pred_x0<VP>(m, xv, sb, sa);
+  if (ST != ST_DDIM) {
+    prev = __fsub_rn(__fmul_rn(sp, xv), __fmul_rn(sd, x0));
+    if (ST == ST_MS2) prev = __fsub_rn(prev, __fmul_rn(hb, __fmul_rn(r_inv, __fsub_rn(x0, x0h))));
+    return;
+  }
   float eps = VP ? __fadd_rn(__fmul_rn(sa, m), __fmul_rn(sb, xv)) : m;
   prev = __fadd_rn(__fmul_rn(sp, x0), __fmul_rn(sd, eps));
 }
 
 // The <VP, true> instantiation is only launched with rs.per % 4 == 0 (cfg_ddim_x4), so the 4 elements of a thread belong to
 // one sample; <VP, false> never reads rs.
-template <bool VP, bool GR = false>
+template <bool VP, bool GR = false, int ST = ST_DDIM>
 __global__ void __launch_bounds__(ED_BLOCK)
 k_cfg_ddim_v4(const float4* __restrict__ local, const float4* __restrict__ dir, const float4* __restrict__ x,
               float4* __restrict__ prev, float4* __restrict__ x0, float g, float sb, float sa, float sp, float sd,
-              int64_t n4, const Rescale rs) {
+              int64_t n4, const Rescale rs, const Multistep ms) {
   int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
   if (t >= n4) return;
   float4 l = local[t], d = dir[t], xv = x[t], p, o;
   const float r = GR ? rs.ratio[(t << 2) / rs.per] : 0.0f;
-  ddim_one<VP, GR>(l.x, d.x, xv.x, g, sb, sa, sp, sd, p.x, o.x, r, rs.gr, rs.omgr);
-  ddim_one<VP, GR>(l.y, d.y, xv.y, g, sb, sa, sp, sd, p.y, o.y, r, rs.gr, rs.omgr);
-  ddim_one<VP, GR>(l.z, d.z, xv.z, g, sb, sa, sp, sd, p.z, o.z, r, rs.gr, rs.omgr);
-  ddim_one<VP, GR>(l.w, d.w, xv.w, g, sb, sa, sp, sd, p.w, o.w, r, rs.gr, rs.omgr);
+  float4 hx = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (ST == ST_MS2) hx = ((const float4*)ms.x0_hist)[t];
+  ddim_one<VP, GR, ST>(l.x, d.x, xv.x, g, sb, sa, sp, sd, p.x, o.x, r, rs.gr, rs.omgr, hx.x, ms.hb, ms.r_inv);
+  ddim_one<VP, GR, ST>(l.y, d.y, xv.y, g, sb, sa, sp, sd, p.y, o.y, r, rs.gr, rs.omgr, hx.y, ms.hb, ms.r_inv);
+  ddim_one<VP, GR, ST>(l.z, d.z, xv.z, g, sb, sa, sp, sd, p.z, o.z, r, rs.gr, rs.omgr, hx.z, ms.hb, ms.r_inv);
+  ddim_one<VP, GR, ST>(l.w, d.w, xv.w, g, sb, sa, sp, sd, p.w, o.w, r, rs.gr, rs.omgr, hx.w, ms.hb, ms.r_inv);
   prev[t] = p;
   x0[t] = o;
 }
 
-template <bool VP, bool GR = false>
+template <bool VP, bool GR = false, int ST = ST_DDIM>
 __global__ void __launch_bounds__(ED_BLOCK)
 k_cfg_ddim_s(const float* __restrict__ local, const float* __restrict__ dir, const float* __restrict__ x,
              float* __restrict__ prev, float* __restrict__ x0, float g, float sb, float sa, float sp, float sd,
-             int64_t n, const Rescale rs) {
+             int64_t n, const Rescale rs, const Multistep ms) {
   int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
   if (t >= n) return;
   float p, o;
-  ddim_one<VP, GR>(local[t], dir[t], x[t], g, sb, sa, sp, sd, p, o, GR ? rs.ratio[t / rs.per] : 0.0f, rs.gr, rs.omgr);
+  ddim_one<VP, GR, ST>(local[t], dir[t], x[t], g, sb, sa, sp, sd, p, o, GR ? rs.ratio[t / rs.per] : 0.0f, rs.gr, rs.omgr,
+                       ST == ST_MS2 ? ms.x0_hist[t] : 0.0f, ms.hb, ms.r_inv);
   prev[t] = p;
   x0[t] = o;
 }
@@ -611,6 +632,15 @@ struct EpilogueArgs {
   float gr, omgr;
 };
 
+// The argument block of the multistep variants (sp / sd then hold c_x / b).  A type of its own: EpilogueArgs, which the DDIM
+// instantiations and k_phase_moments take, keeps its size, so their kernel-argument offsets are what they were.
+struct EpilogueArgsMS : EpilogueArgs {
+  const float* x0_hist;
+  float hb, r_inv;
+};
+template <int ST> struct EpilogueArgsOf { typedef EpilogueArgsMS type; };
+template <> struct EpilogueArgsOf<ST_DDIM> { typedef EpilogueArgs type; };
+
 template <typename Tag>
 __device__ __forceinline__ float direction_at(const EpilogueArgs& a, int b, int c, int Y, int X) {
   int k = last_covering_step(a.stamp, a.inv_row, a.inv_col, a.K, a.w, Y, X);
@@ -652,9 +682,9 @@ __device__ __forceinline__ float uncond_last_at(const EpilogueArgs& a, int b, in
   return ld<Tag>(a.g_out, (((int64_t)(a.K - 1) * 2 + 0) * a.B + b) * a.C * plane + e);
 }
 
-template <typename Tag, bool VP, bool GR = false>
+template <typename Tag, bool VP, bool GR = false, int ST = ST_DDIM>
 __global__ void __launch_bounds__(ED_BLOCK)
-k_phase_epilogue(const EpilogueArgs a) {
+k_phase_epilogue(const typename EpilogueArgsOf<ST>::type a) {
   const int64_t nfull = (int64_t)a.B * a.C * a.H * a.W;
   const int64_t nlow = (int64_t)a.B * a.C * a.h * a.w;
   int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
@@ -680,7 +710,14 @@ k_phase_epilogue(const EpilogueArgs a) {
   float loc = local_at<Tag>(a, b, c, Y, X);
   float d = direction_at<Tag>(a, b, c, Y, X);
   float pv, z0;
-  ddim_one<VP, GR>(loc, d, a.x[t], a.g, a.sb, a.sa, a.sp, a.sd, pv, z0, GR ? a.ratio[b] : 0.0f, a.gr, a.omgr);
+  if constexpr (ST == ST_DDIM) {
+    ddim_one<VP, GR>(loc, d, a.x[t], a.g, a.sb, a.sa, a.sp, a.sd, pv, z0, GR ? a.ratio[b] : 0.0f, a.gr, a.omgr);
+  } else {
+    float x0h = 0.0f;
+    if constexpr (ST == ST_MS2) x0h = a.x0_hist[t];
+    ddim_one<VP, GR, ST>(loc, d, a.x[t], a.g, a.sb, a.sa, a.sp, a.sd, pv, z0, GR ? a.ratio[b] : 0.0f, a.gr, a.omgr, x0h, a.hb,
+                         a.r_inv);
+  }
   a.prev[t] = pv;
   a.x0[t] = z0;
   if (a.direction) a.direction[t] = d;
@@ -1329,6 +1366,15 @@ int ed_assemble_rows_x(const float* latent, int B, int C, int H, int W, const ui
   return done();
 }
 
+// does the history [x0_hist, x0_hist + n) share an element with one of the two outputs of the step?  (they are written while the
+// history of other elements is still being read)
+static inline bool hist_overlaps(const float* x0_hist, const float* prev, const float* x0, int64_t n) {
+  if (!x0_hist) return false;
+  uintptr_t h = (uintptr_t)x0_hist, bytes = (uintptr_t)n * sizeof(float);
+  uintptr_t p = (uintptr_t)prev, o = (uintptr_t)x0;
+  return (h < p + bytes && p < h + bytes) || (h < o + bytes && o < h + bytes);
+}
+
 static int phase_epilogue_launch(bool vp, const void* g_out, const void* v_out, int dtype, const float* x, const int8_t* stamp,
                       const int32_t* inv_row, const int32_t* inv_col, const int32_t* up_row, const int32_t* up_col,
                       const int32_t* down_row, const int32_t* down_col, const int32_t* row_blk, const int32_t* row_src,
@@ -1337,13 +1383,16 @@ static int phase_epilogue_launch(bool vp, const void* g_out, const void* v_out, 
                       int C, int H, int W, int h, int w, int gPH, int gPW, int g_off_y, int g_off_x, int vPH, int vPW,
                       int n_col_blocks, float g, float sqrt_beta_t, float sqrt_alpha_t, float sqrt_alpha_prev,
                       float sqrt_1m_alpha_prev, float rrg_norm, float rrg_weight, void* stream,
-                      const float* ratio = nullptr, const float* ratio_low = nullptr, float gr = 0.0f, float omgr = 0.0f) {
+                      const float* ratio = nullptr, const float* ratio_low = nullptr, float gr = 0.0f, float omgr = 0.0f,
+                      const Multistep* ms = nullptr) {
   int64_t n = (int64_t)B * C * H * W + (int64_t)B * C * h * w;
   if ((int64_t)B * C * H * W == 0) return 0;
   if (x_next && !low_latent) return (int)hipErrorInvalidValue;
   if (ratio && x_next && !ratio_low) return (int)hipErrorInvalidValue;
-  EpilogueArgs a;
+  if (ms && hist_overlaps(ms->x0_hist, prev, x0, (int64_t)B * C * H * W)) return (int)hipErrorInvalidValue;
+  EpilogueArgsMS a;  // launched as its EpilogueArgs base without `ms`
   a.ratio = ratio, a.ratio_low = ratio_low, a.gr = gr, a.omgr = omgr;
+  a.x0_hist = ms ? ms->x0_hist : nullptr, a.hb = ms ? ms->hb : 0.0f, a.r_inv = ms ? ms->r_inv : 0.0f;
   a.g_out = g_out, a.v_out = v_out, a.x = x, a.stamp = stamp;
   a.inv_row = inv_row, a.inv_col = inv_col, a.up_row = up_row, a.up_col = up_col, a.down_row = down_row, a.down_col = down_col;
   a.row_blk = row_blk, a.row_src = row_src, a.col_blk = col_blk, a.col_src = col_src;
@@ -1353,6 +1402,26 @@ static int phase_epilogue_launch(bool vp, const void* g_out, const void* v_out, 
   a.g_off_x = g_off_x, a.vPH = vPH, a.vPW = vPW, a.ncb = n_col_blocks;
   a.g = g, a.sb = sqrt_beta_t, a.sa = sqrt_alpha_t, a.sp = sqrt_alpha_prev, a.sd = sqrt_1m_alpha_prev;
   a.rrg_norm = rrg_norm, a.rrg_weight = rrg_weight;
+  // the multistep variants: <.., ST_MS2> when a history is given, <.., ST_MS1> otherwise (sqrt_alpha_prev / sqrt_1m_alpha_prev
+  // carry c_x / b); without `ms` the launches below are the ones there always were
+#define ED_EPI_MS(T, ST)                                                                                       \
+  if (ratio && vp) k_phase_epilogue<T, true, true, ST><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(a);   \
+  else if (ratio) k_phase_epilogue<T, false, true, ST><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(a);   \
+  else if (vp) k_phase_epilogue<T, true, false, ST><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(a);      \
+  else k_phase_epilogue<T, false, false, ST><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(a);
+#define ED_EPI_MS_T(ST)                        \
+  switch (dtype) {                             \
+    case ED_F32: ED_EPI_MS(F32, ST) break;     \
+    case ED_F16: ED_EPI_MS(F16, ST) break;     \
+    case ED_BF16: ED_EPI_MS(BF16, ST) break;   \
+    default: return (int)hipErrorInvalidValue; \
+  }
+  if (ms) {
+    if (ms->x0_hist) { ED_EPI_MS_T(ST_MS2) } else { ED_EPI_MS_T(ST_MS1) }
+    return done();
+  }
+#undef ED_EPI_MS_T
+#undef ED_EPI_MS
 #define ED_EPI(T)                                                                                        \
   if (ratio && vp) k_phase_epilogue<T, true, true><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(a);  \
   else if (ratio) k_phase_epilogue<T, false, true><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(a);  \
@@ -1433,6 +1502,8 @@ static inline bool cfg_ddim_x4(const float* local, const float* direction, const
          aligned16(prev) && aligned16(x0);
 }
 
+static const Multistep NO_MULTISTEP = {nullptr, 0.0f, 0.0f};
+
 static int cfg_ddim_launch(bool vp, const float* local, const float* direction, const float* x, float* prev, float* x0, float g,
                            float sqrt_beta_t, float sqrt_alpha_t, float sqrt_alpha_prev, float sqrt_one_minus_alpha_prev,
                            int64_t n, void* stream, const Rescale rs = NO_RESCALE) {
@@ -1440,10 +1511,45 @@ static int cfg_ddim_launch(bool vp, const float* local, const float* direction, 
   if (cfg_ddim_x4(local, direction, x, prev, x0, n, rs)) {
     ED_LAUNCH_VP_GR(vp, rs.ratio, k_cfg_ddim_v4, n / 4, (const float4*)local, (const float4*)direction, (const float4*)x,
                     (float4*)prev, (float4*)x0, g, sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev, sqrt_one_minus_alpha_prev,
-                    n / 4, rs);
+                    n / 4, rs, NO_MULTISTEP);
   } else {
     ED_LAUNCH_VP_GR(vp, rs.ratio, k_cfg_ddim_s, n, local, direction, x, prev, x0, g, sqrt_beta_t, sqrt_alpha_t,
-                    sqrt_alpha_prev, sqrt_one_minus_alpha_prev, n, rs);
+                    sqrt_alpha_prev, sqrt_one_minus_alpha_prev, n, rs, NO_MULTISTEP);
+  }
+  return done();
+}
+
+// The multistep launch: the 16-byte form under cfg_ddim_x4's conditions and, with a history, an aligned history; the scalar form
+// otherwise.  <.., ST_MS2> with a history, <.., ST_MS1> without.
+static inline bool cfg_ms_x4(const float* local, const float* direction, const float* x, const float* prev, const float* x0,
+                             int64_t n, const Rescale& rs, const float* x0_hist) {
+  return cfg_ddim_x4(local, direction, x, prev, x0, n, rs) && (!x0_hist || aligned16(x0_hist));
+}
+
+#define ED_LAUNCH_MS(vp, gr, ST, KERNEL, n, ...)                                                               \
+  do {                                                                                                         \
+    if ((gr) && (vp)) KERNEL<true, true, ST><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(__VA_ARGS__);   \
+    else if (gr) KERNEL<false, true, ST><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(__VA_ARGS__);       \
+    else if (vp) KERNEL<true, false, ST><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(__VA_ARGS__);       \
+    else KERNEL<false, false, ST><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(__VA_ARGS__);              \
+  } while (0)
+
+static int cfg_ms_launch(bool vp, const float* local, const float* direction, const float* x, float* prev, float* x0, float g,
+                         float sqrt_beta_t, float sqrt_alpha_t, float c_x, float b, int64_t n, void* stream, const Rescale rs,
+                         const Multistep ms) {
+  if (n == 0) return 0;
+  if (hist_overlaps(ms.x0_hist, prev, x0, n)) return (int)hipErrorInvalidValue;
+  if (cfg_ms_x4(local, direction, x, prev, x0, n, rs, ms.x0_hist)) {
+#define ED_MS_V4(ST)                                                                                                       \
+  ED_LAUNCH_MS(vp, rs.ratio, ST, k_cfg_ddim_v4, n / 4, (const float4*)local, (const float4*)direction, (const float4*)x, \
+               (float4*)prev, (float4*)x0, g, sqrt_beta_t, sqrt_alpha_t, c_x, b, n / 4, rs, ms)
+    if (ms.x0_hist) ED_MS_V4(ST_MS2); else ED_MS_V4(ST_MS1);
+#undef ED_MS_V4
+  } else {
+#define ED_MS_S(ST) \
+  ED_LAUNCH_MS(vp, rs.ratio, ST, k_cfg_ddim_s, n, local, direction, x, prev, x0, g, sqrt_beta_t, sqrt_alpha_t, c_x, b, n, rs, ms)
+    if (ms.x0_hist) ED_MS_S(ST_MS2); else ED_MS_S(ST_MS1);
+#undef ED_MS_S
   }
   return done();
 }
@@ -1641,6 +1747,41 @@ int ed_phase_epilogue_gr(const void* g_out, const void* v_out, int dtype, const 
                                uncond_last, direction, local, K, B, C, H, W, h, w, gPH, gPW, g_off_y, g_off_x, vPH, vPW,
                                n_col_blocks, g, sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev, sqrt_1m_alpha_prev, rrg_norm,
                                rrg_weight, stream, ratio, ratio_low, gr, omgr);
+}
+
+// ---- DPM-Solver++(2M) ------------------------------------------------------------
+int ed_cfg_ddim_step_ms(const float* local, const float* direction, const float* x, float* prev, float* x0, float g,
+                        float sqrt_beta_t, float sqrt_alpha_t, float c_x, float b, float half_b, float r_inv, int64_t n,
+                        int prediction_type, const float* ratio, float gr, float omgr, int B, const float* x0_hist,
+                        void* stream) {
+  if (bad_prediction_type(prediction_type)) return (int)hipErrorInvalidValue;
+  Rescale rs = NO_RESCALE;
+  if (ratio) {
+    if (B <= 0 || n % B) return (int)hipErrorInvalidValue;
+    rs.ratio = ratio, rs.gr = gr, rs.omgr = omgr, rs.per = n / B;
+    if (rs.per == 0) return 0;
+  }
+  Multistep ms = {x0_hist, half_b, r_inv};
+  return cfg_ms_launch(prediction_type == ED_PRED_V, local, direction, x, prev, x0, g, sqrt_beta_t, sqrt_alpha_t, c_x, b, n,
+                       stream, rs, ms);
+}
+
+int ed_phase_epilogue_ms(const void* g_out, const void* v_out, int dtype, const float* x, const int8_t* stamp,
+                         const int32_t* inv_row, const int32_t* inv_col, const int32_t* up_row, const int32_t* up_col,
+                         const int32_t* down_row, const int32_t* down_col, const int32_t* row_blk, const int32_t* row_src,
+                         const int32_t* col_blk, const int32_t* col_src, const float* low_latent, float* prev, float* x0,
+                         float* x_next, float* low_dir, float* uncond_last, float* direction, float* local, int K, int B,
+                         int C, int H, int W, int h, int w, int gPH, int gPW, int g_off_y, int g_off_x, int vPH, int vPW,
+                         int n_col_blocks, float g, float sqrt_beta_t, float sqrt_alpha_t, float c_x, float b, float half_b,
+                         float r_inv, float rrg_norm, float rrg_weight, int prediction_type, const float* ratio,
+                         const float* ratio_low, float gr, float omgr, const float* x0_hist, void* stream) {
+  if (bad_prediction_type(prediction_type)) return (int)hipErrorInvalidValue;
+  Multistep ms = {x0_hist, half_b, r_inv};
+  return phase_epilogue_launch(prediction_type == ED_PRED_V, g_out, v_out, dtype, x, stamp, inv_row, inv_col, up_row, up_col,
+                               down_row, down_col, row_blk, row_src, col_blk, col_src, low_latent, prev, x0, x_next, low_dir,
+                               uncond_last, direction, local, K, B, C, H, W, h, w, gPH, gPW, g_off_y, g_off_x, vPH, vPW,
+                               n_col_blocks, g, sqrt_beta_t, sqrt_alpha_t, c_x, b, rrg_norm, rrg_weight, stream, ratio, ratio_low,
+                               gr, omgr, &ms);
 }
 
 // ---- img2img / inpainting -----------------------------------------------------------------------------

@@ -257,6 +257,25 @@ def _ratio_ptr(ratio, B, name):
     return _dev(ratio, torch.float32, name)
 
 
+def _multistep(multistep, prev, x0, what):
+    """``multistep`` = (c_x, b, half_b, r_inv, x0_hist): the four host scalars of DPMSolverSchedule.multistep_coefficients and the
+    previous timestep's x0 (f32, the outputs' shape), or None in its place for the first-order form -> (floats, x0_hist).
+    A history that shares memory with ``prev`` or ``x0`` is refused: they are written while it is being read."""
+    try:
+        c_x, b, half_b, r_inv, x0_hist = multistep
+        scalars = tuple(float(v) for v in (c_x, b, half_b, r_inv))
+    except (TypeError, ValueError):
+        _reject(f"{what}: multistep must be (c_x, b, half_b, r_inv, x0_hist or None), got {multistep!r}")
+    if x0_hist is not None:
+        if not isinstance(x0_hist, torch.Tensor) or x0_hist.numel() != x0.numel():
+            _reject(f"{what}: x0_hist must be an f32 tensor of {x0.numel()} elements")
+        lo, hi = x0_hist.data_ptr(), x0_hist.data_ptr() + 4 * x0_hist.numel()
+        for t_, name in ((prev, "prev"), (x0, "x0")):
+            if isinstance(t_, torch.Tensor) and t_.data_ptr() < hi and lo < t_.data_ptr() + 4 * t_.numel():
+                _reject(f"{what}: x0_hist overlaps {name} (the history is read while the outputs are written)")
+    return scalars, x0_hist
+
+
 def guidance_moments_workspace(B, n_full, n_low=0, device=None):
     """The partials buffer of guidance_moments / phase_moments for B samples of ``n_full`` elements (+ the
     reduced-resolution pair of ``n_low`` elements): an f64 tensor, allocate once and reuse (launches on one stream)."""
@@ -322,13 +341,14 @@ def phase_moments(g_out, v_out, shape, stamp, pick_tables, view_tables, n_col_bl
 def phase_epilogue(g_out, v_out, x, stamp, pick_tables, view_tables, n_col_blocks, g_off, K, h, w, g, coef, prev, x0,
                    low_dir=None, uncond_last=None, direction=None, local=None, x_next=None, low_latent=None,
                    rrg_norm=0.0, rrg_weight=0.0, prediction_type="epsilon", ratio=None, ratio_low=None,
-                   guidance_rescale=0.0):
+                   guidance_rescale=0.0, multistep=None):
     """unpad_direction + fill_directions + scatter_centres + cfg_ddim_step (+ rrg_update when ``x_next`` is given) in
     one launch (see ed_phase_epilogue / ed_phase_epilogue_pt).  pick_tables = (inv_row, inv_col, up_row, up_col,
     down_row, down_col); view_tables = (row_blk, row_src, col_blk, col_src); coef = DDIMSchedule.step_coefficients(t);
     prediction_type = the scheduler's ("epsilon" or "v_prediction").  ``ratio`` (f32 [B] from phase_moments, with
     ``ratio_low`` when ``x_next`` is given) applies the guidance rescale ``guidance_rescale`` (ed_phase_epilogue_gr);
-    None is the plain launch."""
+    None is the plain launch.  ``multistep`` = (c_x, b, half_b, r_inv, x0_hist or None): the DPM-Solver++(2M) update in the
+    DDIM one's place (ed_phase_epilogue_ms; only coef[:2] are then used); None launches what it always launched."""
     pt = _pred_code(prediction_type)
     B, C, H, W = x.shape
     gr, C2, gPH, gPW = g_out.shape
@@ -348,6 +368,26 @@ def phase_epilogue(g_out, v_out, x, stamp, pick_tables, view_tables, n_col_block
     f32 = torch.float32
     if ratio is None and (ratio_low is not None or float(guidance_rescale) != 0.0):
         _reject("phase_epilogue: guidance_rescale / ratio_low need ratio (phase_moments)")
+    if multistep is not None:
+        ms, x0_hist = _multistep(multistep, prev, x0, "phase_epilogue")
+        if x0_hist is not None and tuple(x0_hist.shape) != tuple(x0.shape):
+            _reject(f"phase_epilogue: x0_hist must have x0's shape {tuple(x0.shape)}, got {tuple(x0_hist.shape)}")
+        gr_f, omgr_f = 0.0, 0.0
+        if ratio is not None:
+            if x_next is not None and ratio_low is None:
+                _reject("phase_epilogue: the fused RRG term with a rescale needs ratio_low")
+            if ratio_low is not None and tuple(ratio_low.shape) != (B,):
+                _reject(f"ratio_low must be f32 [{B}], got {tuple(ratio_low.shape)}")
+            gr_f, omgr_f = rescale_coefficients(guidance_rescale)
+        _call("ed_phase_epilogue_ms", _dev(g_out, None, "g_out"), _dev(v_out, None, "v_out"), _code(g_out, "g_out"),
+              _dev(x, f32, "x"), _dev(stamp, torch.int8, "stamp"), *(_dev(t_, torch.int32) for t_ in pick_tables),
+              *(_dev(t_, torch.int32) for t_ in view_tables), _opt(low_latent, f32, "low_latent"), _dev(prev, f32, "prev"),
+              _dev(x0, f32, "x0"), _opt(x_next, f32, "x_next"), _opt(low_dir, f32, "low_dir"),
+              _opt(uncond_last, f32, "uncond_last"), _opt(direction, f32, "direction"), _opt(local, f32, "local"),
+              K, B, C, H, W, h, w, gPH, gPW, g_off[0], g_off[1], vPH, vPW, n_col_blocks, float(g), float(coef[0]), float(coef[1]),
+              *ms, float(rrg_norm), float(rrg_weight), pt, None if ratio is None else _ratio_ptr(ratio, B, "ratio"),
+              _opt(ratio_low, f32, "ratio_low"), gr_f, omgr_f, _opt(x0_hist, f32, "x0_hist"), _stream())
+        return prev, x0
     if ratio is not None:
         if x_next is not None and ratio_low is None:
             _reject("phase_epilogue: the fused RRG term with a rescale needs ratio_low")
@@ -403,15 +443,31 @@ def fill_directions(dirs, stamp, inv_row, inv_col, up_row, up_col, down_row, dow
 
 
 def cfg_ddim_step(local, direction, x, prev, x0, g, sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev, sqrt_1m_alpha_prev,
-                  prediction_type="epsilon", ratio=None, guidance_rescale=0.0):
+                  prediction_type="epsilon", ratio=None, guidance_rescale=0.0, multistep=None):
     """``ratio`` (f32 [B] from guidance_moments; the buffers are then B equal samples) applies the guidance rescale to
-    local + g * direction before the update (ed_cfg_ddim_step_gr); None is the plain launch."""
+    local + g * direction before the update (ed_cfg_ddim_step_gr); None is the plain launch.  ``multistep`` = (c_x, b, half_b,
+    r_inv, x0_hist or None): the DPM-Solver++(2M) update in the DDIM one's place (ed_cfg_ddim_step_ms; sqrt_alpha_prev and
+    sqrt_1m_alpha_prev are then unused); None launches what it always launched."""
     pt = _pred_code(prediction_type)
     n = x.numel()
     for t in (local, direction, prev, x0):
         assert t.numel() == n
     if ratio is None and float(guidance_rescale) != 0.0:
         _reject("cfg_ddim_step: guidance_rescale needs ratio (guidance_moments)")
+    if multistep is not None:
+        ms, x0_hist = _multistep(multistep, prev, x0, "cfg_ddim_step")
+        B, gr_f, omgr_f = 0, 0.0, 0.0
+        if ratio is not None:
+            B = ratio.numel()
+            if B == 0 or n % B:
+                _reject(f"cfg_ddim_step: {n} elements are not {B} equal samples")
+            gr_f, omgr_f = rescale_coefficients(guidance_rescale)
+        _call("ed_cfg_ddim_step_ms",
+              _dev(local, torch.float32), _dev(direction, torch.float32), _dev(x, torch.float32),
+              _dev(prev, torch.float32), _dev(x0, torch.float32), float(g), float(sqrt_beta_t), float(sqrt_alpha_t), *ms, n, pt,
+              None if ratio is None else _ratio_ptr(ratio, B, "ratio"), gr_f, omgr_f, B,
+              _opt(x0_hist, torch.float32, "x0_hist"), _stream())
+        return prev, x0
     if ratio is not None:
         B = ratio.numel()
         if B == 0 or n % B:

@@ -28,7 +28,7 @@ import torch.nn as nn
 
 from . import geometry, host_rng, ops
 from .graphs import GraphedForward
-from .schedule import CosineScheduler, DDIMSchedule
+from .schedule import SAMPLERS, CosineScheduler, DDIMSchedule, DPMSolverSchedule
 from .sharding import RowSharder
 
 
@@ -103,6 +103,20 @@ MASK_MODES = ("binary", "graded")
 
 # Input channels of an inpainting UNet: noisy latent (4) | latent mask (1) | masked-image latent (4)
 INPAINT_IN_CHANNELS = 9
+
+
+def check_sampler_arguments(sampler=None, solver_order=2, scheduler=None):
+    """ValueError for a ``sampler`` / ``solver_order`` ElasticDiffusion cannot honour (before anything is built): ``sampler`` is
+    None (= "ddim" without a ``scheduler``, the scheduler's own kind with one), "ddim" or "dpmsolver++"; with a ``scheduler``
+    object it has to name that object's kind."""
+    if sampler is not None and sampler not in SAMPLERS:
+        raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
+    if solver_order not in (1, 2):
+        raise ValueError(f"solver_order must be 1 or 2, got {solver_order!r}")
+    if scheduler is not None and sampler is not None:
+        kind = "dpmsolver++" if isinstance(scheduler, DPMSolverSchedule) else "ddim"
+        if kind != sampler:
+            raise ValueError(f"sampler={sampler!r} but the scheduler object given is a {type(scheduler).__name__} ({kind!r})")
 
 
 def check_inpaint_unet_arguments(in_channels, init_image=None, mask_image=None, mask_mode="binary", controlnet=False,
@@ -316,13 +330,18 @@ class ElasticDiffusion(nn.Module):
     network exist in the build environment): ``unet``, ``vae``, ``scheduler``, ``text_encoder`` (callable
     ``prompts -> (embeds, pooled)``), ``controlnet``, ``process_group``.  ``max_prompt_chunks`` / ``prompt_weighting`` are handed
     to ``text.load_clip`` when the CLIP encoders come from ``weights`` (prompts of up to that many 75-token chunks instead of
-    truncation, A1111's ``(word:1.3)`` syntax; both off by default)."""
+    truncation, A1111's ``(word:1.3)`` syntax; both off by default).
+
+    ``sampler`` / ``solver_order`` (keyword-only): ``"dpmsolver++"`` samples with DPM-Solver++(2M) at order
+    ``solver_order`` (1 or 2) on the same timestep grid instead of DDIM -- the update is a variant of the same step launches, reading
+    the previous timestep's x0; passing ``scheduler=DPMSolverSchedule(...)`` does the same.  None / ``"ddim"``: the loop as it was."""
 
     def __init__(self, device, sd_version="2.0", verbose=False, log_freq=5, view_batch_size=1, low_vram=False, *,
                  unet=None, vae=None, scheduler=None, text_encoder=None, controlnet=None, process_group=None,
                  model_dtype=None, weights=None, cache_backgrounds=False, use_graphs=True, residual_fp32=None,
-                 max_prompt_chunks=1, prompt_weighting=False):
+                 max_prompt_chunks=1, prompt_weighting=False, sampler=None, solver_order=2):
         super().__init__()
+        check_sampler_arguments(sampler, solver_order, scheduler)
         device = torch.device(device)
         if device.type == "cuda" and device.index is None and torch.cuda.is_available():
             device = torch.device("cuda", torch.cuda.current_device())
@@ -365,6 +384,8 @@ class ElasticDiffusion(nn.Module):
         self.controlnet = self._model_layout(controlnet.to(device)) if controlnet is not None else None
         if scheduler is None:
             scheduler = DDIMSchedule.from_config_dir(weights) if weights else DDIMSchedule()  # ED:153
+            if sampler == "dpmsolver++":  # the same schedule settings, the multistep update
+                scheduler = DPMSolverSchedule(**vars(scheduler.config), solver_order=solver_order)
         self.scheduler = scheduler
         if text_encoder is None and weights:
             # real UNet/VAE weights with synthetic prompt embeddings would be prompt-independent garbage: a snapshot
@@ -801,7 +822,7 @@ class ElasticDiffusion(nn.Module):
 
     # ---- one estimation phase (ED:1016-1035 or ED:1043-1056) ---------------------------------------
     def _phase_steps(self, P, x, ti, K, g, drop_p, emb, cond=None, direct=True, rrg_w=None, rrg_norm=0.0, frames=None,
-                     rescale=None, extras=None):
+                     rescale=None, extras=None, multistep=None):
         """Generator: pre-model glue -> ``yield _ModelCall`` (receives the model output rows) -> post-model glue;
         returns (prev, x0, info).  ``direct``: assemble straight into the hipGraph's static input (one image in flight,
         one rank); otherwise into a scratch batch the driver concatenates / the sharder slices.  ``rrg_w``: this is the
@@ -810,7 +831,9 @@ class ElasticDiffusion(nn.Module):
         std-rescaled before the DDIM update -- one moments reduction over the same rows, then the rescale-aware kernels;
         with ``rrg_w`` the reduced-resolution pair gets its own ratio (info["ratio_low"]).  ``extras`` = (extra [B,E,Hl,Wl],
         pad_value [E]) on a 9-channel inpainting UNet: the model rows carry C + E channels, the extra ones registered to each row's
-        latent (``ops.assemble_rows_x``); everything after the model call is unchanged."""
+        latent (``ops.assemble_rows_x``); everything after the model call is unchanged.  ``multistep`` (``_multistep_args``): the
+        DPM-Solver++(2M) update of this timestep in the DDIM one's place, in the same launch; None launches what it always did."""
+        ms_kw = {} if multistep is None else dict(multistep=multistep)
         B, C = x.shape[:2]
         CR = C if extras is None else C + extras[0].shape[1]  # channels of a model INPUT row
         dev, mdt = self.device, self.model_dtype
@@ -888,7 +911,7 @@ class ElasticDiffusion(nn.Module):
                                (P.gpad.top, P.gpad.left), K, P.h, P.w, np.float32(g), self._step_coef[ti], prev, x0,
                                low_dir=low_dir, uncond_last=uncond_last, direction=direction, local=local, x_next=x_next,
                                low_latent=low[K - 1] if rrg_w is not None else None, rrg_norm=rrg_norm,
-                               rrg_weight=0.0 if rrg_w is None else np.float32(rrg_w), prediction_type=pt, **rs_kw)
+                               rrg_weight=0.0 if rrg_w is None else np.float32(rrg_w), prediction_type=pt, **rs_kw, **ms_kw)
         else:
             dirs = torch.empty(K, B, C, P.h, P.w, device=dev, dtype=torch.float32)
             ops.unpad_direction(g_out, dirs, uncond_last, P.gpad.top, P.gpad.left)
@@ -903,11 +926,21 @@ class ElasticDiffusion(nn.Module):
                 if ratio_low is not None:  # the pair ops.rrg_update forms (in _program)
                     ops.guidance_moments(uncond_last, low_dir, np.float32(g), ratio_low, rescale.ws)
                 rs_kw = dict(ratio=rescale.ratio, guidance_rescale=rescale.gr)
-            ops.cfg_ddim_step(local, direction, x, prev, x0, np.float32(g), *self._step_coef[ti], prediction_type=pt, **rs_kw)
+            ops.cfg_ddim_step(local, direction, x, prev, x0, np.float32(g), *self._step_coef[ti], prediction_type=pt, **rs_kw,
+                              **ms_kw)
         self.host_s["phase_total"] += time.perf_counter() - h0
         info = {"low_latent": low[K - 1], "uncond_score": uncond_last, "low_direction": low_dir,
                 "direction": direction, "local": local, "init_low": low[0], "x_next": x_next, "ratio_low": ratio_low}
         return prev, x0, info
+
+    def _multistep_args(self, t, hist, is_last):
+        """The ``multistep`` argument of the step kernels at timestep ``t``: None under a DDIM scheduler; under a
+        ``DPMSolverSchedule`` (c_x, b, half_b, r_inv, x0_hist) with ``hist`` = (x0 of the previous timestep, that timestep) or None,
+        the history passed only where the schedule makes the step second order."""
+        if not isinstance(self.scheduler, DPMSolverSchedule):
+            return None
+        coef = self.scheduler.multistep_coefficients(t, None if hist is None else hist[1], is_last)
+        return coef[2:] + (hist[0] if coef[5] != 0.0 else None,)
 
     def _drive(self, program):
         """Run one program alone: every model call is its own (graph-replayed, row-sharded) forward."""
@@ -1272,12 +1305,16 @@ class ElasticDiffusion(nn.Module):
         rescale = None
         if S.guidance_rescale:
             rescale = _Rescale(S.guidance_rescale, B, S.C * P.Hl * P.Wl, S.C * P.h * P.w, self.device)
+        # DPM-Solver++(2M) history, per image: (x0 of the last full-resolution phase of the previous timestep index, its timestep).
+        # The two buffers alternate by themselves: every phase writes a fresh x0, and the one before the last is released here.
+        hist = None
         for i, t in enumerate(progress(self._timesteps[S.t_start:]), start=S.t_start):  # absolute index; t_start = 0 without strength
+            ms = self._multistep_args(t, hist, i == S.T - 1)  # both phases of a timestep step from the same history
             w_i = S.rrg(i)
             rrg_w = w_i if w_i > 10 else None  # ED:1061-1062
             two_phase = S.repaint and i < S.T - 1
             prev, x0, info = yield from self._phase_steps(P, x, i, S.R + 1, S.guidance, S.drop_p, emb, cond, direct,
-                                                          None if two_phase else rrg_w, S.norm, frames, rescale, extras)
+                                                          None if two_phase else rrg_w, S.norm, frames, rescale, extras, ms)
             if logs is not None and logs["init_low"] is None:
                 # ED:1023-1024: taken right after the FIRST direction estimate, i.e. before the RePaint phase replaces
                 # ``info`` with the one of the undone sample (ED:1043)
@@ -1289,7 +1326,8 @@ class ElasticDiffusion(nn.Module):
                 x = self._undo(prev, i + 1)
                 cfg = S.guidance / 3
                 prev, x0, info = yield from self._phase_steps(P, x, i, 1, cfg, S.drop_p, emb, cond, direct, rrg_w, S.norm,
-                                                              frames, rescale, extras)
+                                                              frames, rescale, extras, ms)
+            hist = (x0, t)
             if logs is not None:  # verbose image logs (ED:1058-1059, 1073-1076)
                 if i % self.log_freq == 0:
                     logs["x0"].append(x0.clone())
@@ -1552,6 +1590,7 @@ class ElasticDiffusion(nn.Module):
         if guidance_rescale:
             ws = ops.guidance_moments_workspace(B, C * h * w, 0, dev)
             rs_kw = dict(ratio=torch.empty(B, device=dev, dtype=torch.float32), guidance_rescale=guidance_rescale)
+        hist = None  # DPM-Solver++(2M): the previous iteration's (x0, timestep)
         for i, t in enumerate(ts):
             if pad.padded:  # the reference re-seeds the global generators once per pad strip (ED:359)
                 host_rng.replay_strip_reseeds(len(pad.strips))
@@ -1566,9 +1605,12 @@ class ElasticDiffusion(nn.Module):
             direction = (cnd - uncond).contiguous()
             if rs_kw:
                 ops.guidance_moments(uncond, direction, np.float32(guidance_scale), rs_kw["ratio"], ws, text=cnd)
+            ms = self._multistep_args(t, hist, i == len(ts) - 1)
             ops.cfg_ddim_step(uncond, direction, x, prev, x0, np.float32(guidance_scale),
                               *self.scheduler.step_coefficients(t),
-                              prediction_type=self.scheduler.config.prediction_type, **rs_kw)
+                              prediction_type=self.scheduler.config.prediction_type, **rs_kw,
+                              **({} if ms is None else dict(multistep=ms)))
+            hist = (x0, t)
             x = prev
             if i % self.log_freq == 0:
                 inter.append(x0.cpu())

@@ -9,6 +9,9 @@ Only *scalars* are produced here -- every per-element operation of ``scheduler.s
 What a ``scheduler_config.json`` may say and is honoured (DESIGN.md section 14 writes the definitions out):
 ``prediction_type`` epsilon / v_prediction, ``timestep_spacing`` leading / linspace / trailing and
 ``rescale_betas_zero_snr``.  ``clip_sample``, thresholding and ``sample`` prediction are refused.
+
+``DPMSolverSchedule`` is the same schedule with the host scalars of the DPM-Solver++(2M) update; a snapshot's
+``_class_name`` never selects it.
 """
 from types import SimpleNamespace
 
@@ -144,6 +147,56 @@ class DDIMSchedule:
         if len(b) != n_sub:
             raise IndexError("undo_step would index betas past num_train_timesteps (the reference raises too)")
         return torch.stack([(1 - b) ** 0.5, b ** 0.5], dim=1).contiguous()  # fp32 [n_sub, 2]
+
+
+SAMPLERS = ("ddim", "dpmsolver++")
+
+
+class DPMSolverSchedule(DDIMSchedule):
+    """DPM-Solver++(2M) (arXiv 2211.01095; diffusers' ``DPMSolverMultistepScheduler`` with ``algorithm_type="dpmsolver++"``,
+    ``solver_type="midpoint"``, no Karras sigmas, no thresholding) on ``DDIMSchedule``'s timestep grid: the timesteps,
+    ``prev_t = t - n // k``, ``final_alpha_cumprod``, ``add_noise`` and ``undo_step`` scalars are the parent's for every spacing, so
+    everything around the sample update is unchanged.  It accepts and refuses what ``DDIMSchedule`` does.
+
+    ``solver_order`` 1 or 2; ``lower_order_final``: the last step of a run of fewer than 15 steps is first order."""
+
+    def __init__(self, *args, solver_order=2, lower_order_final=True, **kwargs):
+        if solver_order not in (1, 2):
+            raise ValueError(f"solver_order must be 1 or 2, got {solver_order!r}")
+        super().__init__(*args, **kwargs)
+        self.solver_order = int(solver_order)
+        self.lower_order_final = bool(lower_order_final)
+
+    def multistep_coefficients(self, t, t_hist=None, is_last=False):
+        """(sqrt(1-abar_t), sqrt(abar_t), c_x, b, 0.5 * b, r_inv) as python floats holding fp32 values, for the update
+        ``prev = (c_x * x - b * x0) - (0.5 * b) * (r_inv * (x0 - x0_hist))``: with alpha = abar ** 0.5, sigma = (1 - abar) ** 0.5 and
+        lambda = log(alpha) - log(sigma),  h = lambda_prev - lambda_t,  c_x = sigma_prev / sigma_t,  b = alpha_prev * (exp(-h) - 1),
+        r_inv = 1 / ((lambda_t - lambda_{t_hist}) / h).  ``t_hist``: the timestep the history x0 was taken at, None without one.
+        ``r_inv == 0.0`` says that the step is FIRST order (the history is not to be passed): no history, ``solver_order == 1``,
+        the last step (``is_last``) of fewer than 15 under ``lower_order_final``, or abar_prev == 1 / abar_{t_hist} == 0, where
+        h / h0 is infinite."""
+        sqrt_beta_t, sqrt_alpha_t = self.step_coefficients(t)[:2]  # raises for an epsilon model at abar_t = 0, as the DDIM step
+        t = int(t)
+        prev_t = t - self.config.num_train_timesteps // self.num_inference_steps
+        a_t = self.alphas_cumprod[t]
+        a_prev = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
+
+        def lam(a):
+            return torch.log(a ** 0.5) - torch.log((1 - a) ** 0.5)
+
+        h = lam(a_prev) - lam(a_t)
+        c_x = (1 - a_prev) ** 0.5 / (1 - a_t) ** 0.5
+        b = a_prev ** 0.5 * (torch.exp(-h) - 1.0)
+        r_inv = torch.zeros_like(b)
+        second = t_hist is not None and self.solver_order == 2
+        if second and is_last and self.lower_order_final and self.num_inference_steps < 15:
+            second = False
+        if second and (float(a_prev) == 1.0 or float(self.alphas_cumprod[int(t_hist)]) == 0.0):
+            second = False
+        if second:
+            h0 = lam(a_t) - lam(self.alphas_cumprod[int(t_hist)])
+            r_inv = 1.0 / (h0 / h)
+        return (sqrt_beta_t, sqrt_alpha_t) + tuple(float(v) for v in (c_x, b, 0.5 * b, r_inv))
 
 
 class CosineScheduler:

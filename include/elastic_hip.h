@@ -440,6 +440,35 @@ int ed_phase_epilogue_gr(const void* g_out, const void* v_out, int dtype, const 
                          const float* ratio, const float* ratio_low, float gr, float omgr, void* stream);
 
 /*
+ * DPM-Solver++(2M): the multistep update in the places of the DDIM one.
+ *
+ * ed_cfg_ddim_step_ms / ed_phase_epilogue_ms -- the *_gr entry points (same arguments, same x0 = the DDIM step's
+ * pred_original_sample of the guided, rescaled model output, same by-products, same fused RRG term) with the sample update
+ *     prev = (c_x * x - b * x0) - half_b * (r_inv * (x0 - x0_hist))
+ * evaluated left to right in fp32, every product rounded on its own.  The host passes c_x = sigma_prev / sigma_t,
+ * b = alpha_prev * (exp(-h) - 1), half_b = 0.5 * b and r_inv = h / h0 in the places of sqrt_alpha_prev and
+ * sqrt_1m_alpha_prev.  x0_hist f32 [n] (the flat step) / [B,C,H,W] (the epilogue) is the previous timestep's x0 at the output
+ * element's index; NULL launches the first-order form prev = c_x * x - b * x0, which reads neither x0_hist nor half_b / r_inv.
+ * The choice is per launch (two kernel instantiations), never per element.
+ * hipErrorInvalidValue before any launch: a prediction_type other than ED_PRED_*, what the *_gr entry point refuses, and an
+ * x0_hist that shares an element with prev or x0.  The 16-byte form of the flat step runs under ed_cfg_ddim_step_width's
+ * conditions and, with a history, x0_hist 16-byte aligned; the scalar form otherwise.
+ */
+int ed_cfg_ddim_step_ms(const float* local, const float* direction, const float* x, float* prev, float* x0,
+                        float g, float sqrt_beta_t, float sqrt_alpha_t, float c_x, float b, float half_b, float r_inv,
+                        int64_t n, int prediction_type, const float* ratio, float gr, float omgr, int B,
+                        const float* x0_hist, void* stream);
+int ed_phase_epilogue_ms(const void* g_out, const void* v_out, int dtype, const float* x, const int8_t* stamp,
+                         const int32_t* inv_row, const int32_t* inv_col, const int32_t* up_row, const int32_t* up_col,
+                         const int32_t* down_row, const int32_t* down_col, const int32_t* row_blk, const int32_t* row_src,
+                         const int32_t* col_blk, const int32_t* col_src, const float* low_latent, float* prev, float* x0,
+                         float* x_next, float* low_dir, float* uncond_last, float* direction, float* local, int K, int B,
+                         int C, int H, int W, int h, int w, int gPH, int gPW, int g_off_y, int g_off_x, int vPH, int vPW,
+                         int n_col_blocks, float g, float sqrt_beta_t, float sqrt_alpha_t, float c_x, float b, float half_b,
+                         float r_inv, float rrg_norm, float rrg_weight, int prediction_type, const float* ratio,
+                         const float* ratio_low, float gr, float omgr, const float* x0_hist, void* stream);
+
+/*
  * ed_flash_attention -- fused attention forward of the UNet's transformer blocks (what diffusers' AttnProcessor2_0
  * does with F.scaled_dot_product_attention inside `self.unet(...)`, ED:422-426): out = softmax(scale * Q K^T) V per
  * (batch, head), never materialising the Nq x Nk score matrix.  MFMA 32x32x16 (bf16 / f16), online softmax in fp32.
