@@ -30,6 +30,8 @@ and a mask, and conditions on the mask and the blanked picture instead of pastin
 ``--ip_adapter PATH[:SCALE]`` installs a base IP-Adapter and takes the image prompt either as a picture,
 ``--ip_adapter_image FILE`` with ``--image_encoder DIR`` (a local CLIPVisionModelWithProjection), or as CLIP image embeddings,
 ``--ip_adapter_embeds FILE`` (``.pt`` / ``.npy``).
+``--score_pca true`` saves the reference's diagnostic pictures (pca_diffusion_scores.py) every ``--log_freq``
+steps under the script's own names, ``pca_cls_dir_{i}.png`` / ``pca_uncond_{i}.png``.
 """
 import argparse
 import os
@@ -119,6 +121,8 @@ def build_parser():
                     "[1, clip_dim]: a .pt (torch.save of a tensor) or .npy file")
     ap.add_argument("--image_encoder", type=str, default=None, help="local directory of a transformers "
                     "CLIPVisionModelWithProjection, for --ip_adapter_image")
+    ap.add_argument("--score_pca", type=_bool, default=False, help="true: every --log_freq steps, save the PCA maps of the class "
+                    "direction and of the local unconditional score as pca_cls_dir_{i}.png / pca_uncond_{i}.png")
     return ap
 
 
@@ -255,6 +259,8 @@ def main(argv=None):
         if pads:
             extra["init_image"], extra["mask_image"] = sd.outpaint_canvas(extra["init_image"], *pads)
         extra.update(mask_blur=opt.mask_blur, mask_mode=opt.mask_mode, composite=opt.composite)
+    if opt.score_pca:
+        extra["score_pca"] = True
     sd.seed_everything(opt.seed)
     t0 = time.time()
     imgs, image_log = sd.generate_image(prompts=[opt.prompt] * opt.num_sampled, negative_prompts=opt.negative,

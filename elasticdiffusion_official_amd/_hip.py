@@ -14,7 +14,7 @@ import torch  # noqa: F401  (must be imported before the .so so libamdhip64 is a
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT_DIR = os.path.dirname(PKG_DIR)
 SOURCES = [os.path.join(PKG_DIR, "csrc", n) for n in ("elastic_kernels.hip", "unet_kernels.hip", "attention_kernels.hip", "gemm_kernels.hip", "vae_kernels.hip",
-                                                       "canny_kernels.hip", "resize_kernels.hip", "mask_kernels.hip", "lora_kernels.hip")]
+                                                       "canny_kernels.hip", "resize_kernels.hip", "mask_kernels.hip", "lora_kernels.hip", "pca_kernels.hip")]
 SRC = SOURCES[0]
 INCLUDE = os.path.join(ROOT_DIR, "include")
 SO_PATH = os.path.join(PKG_DIR, "libelastic_hip.so")
@@ -116,6 +116,9 @@ SIGNATURES = {
     "ed_phase_epilogue_ms": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                              _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f,
                              _f, _f, _f, _f, _i, _vp, _vp, _f, _f, _vp, _vp],
+    "ed_score_pca_workspace": [_i, _i64],
+    "ed_score_pca_fit": [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ed_score_pca_map": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
 }
 
 _LIB = None

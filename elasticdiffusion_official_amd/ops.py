@@ -1497,6 +1497,53 @@ def resize_u8(img, size, filter="bicubic", out="u8"):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Score PCA maps (csrc/pca_kernels.hip): the reference's per-step diagnostic pictures, no host sync
+# ---------------------------------------------------------------------------------------------------------------------
+def score_pca_workspace(B, n, device=None):
+    """The workspace of score_pca for B samples of n = H * W pixels: an f64 tensor, allocate once and reuse (launches on one
+    stream)."""
+    nbytes = _hip.lib().ed_score_pca_workspace(int(B), int(n))
+    if nbytes <= 0:
+        _reject(f"score_pca_workspace: B must be >= 1 and n in 4..2^28, got B = {B}, n = {n}")
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def score_pca(score, normalize=False, workspace=None, return_fit=False):
+    """score f32 [B, 4, H, W] -> uint8 [B, H, W, 3] on the device: every sample's pixels projected onto the first three principal
+    components of that sample and scaled to bytes by the projection's own range -- ``sklearn.decomposition.PCA(3).fit / transform``
+    + ``np.uint8((r - r.min()) / (r.max() - r.min()) * 255)`` of pca_diffusion_scores.py:165-179, within one byte step (DESIGN.md
+    section 26).  ``normalize``: the script's ``(s - min) / (max - min) * 2 - 1`` of the class direction over the whole tensor, in
+    fp32 as there, before the fit.  ``return_fit``: also (components f32 [B,3,4], mean f32 [B,4], explained_variance f32 [B,3]).
+    Four launches (five with ``normalize``), no sync.
+    workspace = score_pca_workspace(B, H * W); allocated here when absent."""
+    p_score = _dev(score, torch.float32, "score")
+    if score.dim() != 4 or score.shape[1] != 4:
+        _reject(f"score_pca: score must be [B, 4, H, W] (a 4-channel latent score), got {tuple(score.shape)}")
+    B, C, H, W = score.shape
+    need = _hip.lib().ed_score_pca_workspace(B, H * W)
+    if B < 1 or H * W < 4 or need <= 0:
+        _reject(f"score_pca: needs B >= 1 and 4 <= H * W <= 2^28 pixels to fit three components, got {tuple(score.shape)}")
+    dev = score.device
+    if workspace is None:
+        workspace = torch.empty(need // 8, dtype=torch.float64, device=dev)
+    elif not isinstance(workspace, torch.Tensor) or workspace.numel() * workspace.element_size() < need:
+        _reject(f"workspace must hold {need} bytes (score_pca_workspace({B}, {H * W}))")
+    comps, mean, var, norm = (torch.empty(B, k, dtype=torch.float32, device=dev) for k in (12, 4, 3, 2))
+    out = torch.empty(B, H, W, 3, dtype=torch.uint8, device=dev)
+    TIMER.note_work("ed_score_pca_fit", flops=28.0 * B * H * W, nbytes=(32.0 if normalize else 16.0) * B * H * W)
+    _call("ed_score_pca_fit", p_score, B, C, H, W, int(bool(normalize)), _dev(comps, torch.float32, "components"),
+          _dev(mean, torch.float32, "mean"), _dev(var, torch.float32, "explained_variance"), _dev(norm, torch.float32, "norm"),
+          _dev(workspace, None, "workspace"), _stream())
+    TIMER.note_work("ed_score_pca_map", flops=2 * 28.0 * B * H * W, nbytes=35.0 * B * H * W)
+    _call("ed_score_pca_map", _dev(score, torch.float32, "score"), B, C, H, W,
+          _dev(norm, torch.float32, "norm") if normalize else None, _dev(out, torch.uint8, "out"),
+          _dev(workspace, None, "workspace"), _stream())
+    if return_fit:
+        return out, (comps.view(B, 3, 4), mean, var)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # Image-to-image and masked inpainting (DESIGN.md section 18): once per image before the loop, the blend once per phase
 # ---------------------------------------------------------------------------------------------------------------------
 VAE_INPUT_MAX_DIM = 8192

@@ -144,6 +144,18 @@ def check_inpaint_unet_arguments(in_channels, init_image=None, mask_image=None, 
     return True
 
 
+SCORE_PCA_KEYS = ("pca_cls_dir", "pca_uncond")  # the reference script's file names (pca_diffusion_scores.py:181, 196)
+
+
+def check_score_pca_arguments(score_pca, channels):
+    """``score_pca`` projects 4-channel scores onto three components: a latent of another channel count
+    (``channels``: the model's OUTPUT channels, what the class direction and the unconditional score have) is refused."""
+    if score_pca and channels != 4:
+        raise ValueError(f"score_pca maps a 4-channel score onto its first three principal components; this model's scores have "
+                         f"{channels} channels")
+    return bool(score_pca)
+
+
 def check_ip_adapter_arguments(loaded, has_image_encoder, ip_adapter_image=None, ip_adapter_image_embeds=None):
     """The argument rules of ``ip_adapter_image`` / ``ip_adapter_image_embeds``, pure host code that runs
     before anything is launched -> does this run carry an image prompt?  ValueError: an adapter is loaded and no image is given
@@ -412,6 +424,7 @@ class ElasticDiffusion(nn.Module):
         self.last_init_pixels = None   # uint8 [height,width,3]: the (resized) 8-bit init picture of the last such image, on the device
         self.last_pixel_mask = None    # uint8 [height,width]: its (resized, blurred) 8-bit picture mask, on the device
         self.last_masked_image_latents = None  # zm of the last image on a 9-channel UNet (the blanked picture's scaled latent)
+        self.last_score_pca = None     # the PCA maps of the last ``generate_latents(score_pca=True)``, else None
 
     @staticmethod
     def _model_layout(module):
@@ -822,7 +835,7 @@ class ElasticDiffusion(nn.Module):
 
     # ---- one estimation phase (ED:1016-1035 or ED:1043-1056) ---------------------------------------
     def _phase_steps(self, P, x, ti, K, g, drop_p, emb, cond=None, direct=True, rrg_w=None, rrg_norm=0.0, frames=None,
-                     rescale=None, extras=None, multistep=None):
+                     rescale=None, extras=None, multistep=None, keep_scores=False):
         """Generator: pre-model glue -> ``yield _ModelCall`` (receives the model output rows) -> post-model glue;
         returns (prev, x0, info).  ``direct``: assemble straight into the hipGraph's static input (one image in flight,
         one rank); otherwise into a scratch batch the driver concatenates / the sharder slices.  ``rrg_w``: this is the
@@ -832,7 +845,8 @@ class ElasticDiffusion(nn.Module):
         with ``rrg_w`` the reduced-resolution pair gets its own ratio (info["ratio_low"]).  ``extras`` = (extra [B,E,Hl,Wl],
         pad_value [E]) on a 9-channel inpainting UNet: the model rows carry C + E channels, the extra ones registered to each row's
         latent (``ops.assemble_rows_x``); everything after the model call is unchanged.  ``multistep`` (``_multistep_args``): the
-        DPM-Solver++(2M) update of this timestep in the DDIM one's place, in the same launch; None launches what it always did."""
+        DPM-Solver++(2M) update of this timestep in the DDIM one's place, in the same launch; None launches what it always did.
+        ``keep_scores``: info["direction"] / info["local"] are kept as ``verbose`` keeps them (the inputs of the score PCA maps)."""
         ms_kw = {} if multistep is None else dict(multistep=multistep)
         B, C = x.shape[:2]
         CR = C if extras is None else C + extras[0].shape[1]  # channels of a model INPUT row
@@ -895,7 +909,7 @@ class ElasticDiffusion(nn.Module):
         pt = self.scheduler.config.prediction_type
         ratio_low = rescale.ratio_low if rescale is not None and rrg_w is not None else None
         if FUSED_GLUE:
-            keep = self.verbose  # the full-resolution direction / local score are only by-products for the image logs
+            keep = self.verbose or keep_scores  # the full-resolution direction / local score are only by-products for the image logs
             direction = torch.empty_like(x) if keep else None
             local = torch.empty_like(x) if keep else None
             x_next = torch.empty_like(x) if rrg_w is not None else None
@@ -1183,6 +1197,11 @@ class ElasticDiffusion(nn.Module):
         a, b = self.scheduler.add_noise_coefficients(self._timesteps[j])
         return ops.inpaint_blend(x, mask, z0, noise, a, b)
 
+    def _score_channels(self):
+        """channels of the latent, and so of the class direction and the local score (``_setup_run``'s S.C)"""
+        cfg = self.unet.config
+        return getattr(cfg, "out_channels", 4) if cfg.in_channels == INPAINT_IN_CHANNELS else cfg.in_channels
+
     def _check_inpaint9(self, height, width, init_image=None, mask_image=None, mask_mode="binary"):
         """``check_inpaint_unet_arguments`` for this pipeline's UNet and ControlNet at a run's size"""
         s = self.vae_scale_factor
@@ -1252,12 +1271,15 @@ class ElasticDiffusion(nn.Module):
 
     def _program(self, S, prompts, negative_prompts, condition_image=None, trace=None, progress=_identity_progress,
                  direct=True, frames=None, init_image=None, mask_image=None, mask_blur=0.0, mask_mode="binary",
-                 min_chunks=None, ip_adapter_image=None, ip_adapter_image_embeds=None):
+                 min_chunks=None, ip_adapter_image=None, ip_adapter_image_embeds=None, score_maps=None):
         """Generator: the denoising loop of ONE image (ED:981-1078), yielding ``_ModelCall``s; returns the final latent.
         All host RNG draws happen inside, in the reference's order.  ``init_image`` / ``mask_image``: image-to-image and
         inpainting -- the loop starts at timestep index ``S.t_start`` from the noised encoding of the
         image, and with a mask the kept region is put back at the next noise level after every step.  ``mask_blur`` /
-        ``mask_mode``: the mask feathered on the device and, in "graded" mode, read as a per-pixel release time (section 19)."""
+        ``mask_mode``: the mask feathered on the device and, in "graded" mode, read as a per-pixel release time (section 19).
+        ``score_maps`` (a dict; section 26): filled with {"pca_cls_dir": {i: bytes}, "pca_uncond": {i: bytes}}, the PCA maps
+        (uint8 [B, Hl, Wl, 3], on the device) of the class direction and the local score of the FIRST phase of every timestep
+        index i with i % log_freq == 0."""
         P = S.P
         if isinstance(prompts, str):
             prompts = [prompts]
@@ -1308,13 +1330,22 @@ class ElasticDiffusion(nn.Module):
         # DPM-Solver++(2M) history, per image: (x0 of the last full-resolution phase of the previous timestep index, its timestep).
         # The two buffers alternate by themselves: every phase writes a fresh x0, and the one before the last is released here.
         hist = None
+        pca_ws = None
+        if score_maps is not None:
+            score_maps.update({key: {} for key in SCORE_PCA_KEYS})
+            pca_ws = ops.score_pca_workspace(B, P.Hl * P.Wl, self.device)
         for i, t in enumerate(progress(self._timesteps[S.t_start:]), start=S.t_start):  # absolute index; t_start = 0 without strength
             ms = self._multistep_args(t, hist, i == S.T - 1)  # both phases of a timestep step from the same history
             w_i = S.rrg(i)
             rrg_w = w_i if w_i > 10 else None  # ED:1061-1062
             two_phase = S.repaint and i < S.T - 1
+            mapped = score_maps is not None and i % self.log_freq == 0
             prev, x0, info = yield from self._phase_steps(P, x, i, S.R + 1, S.guidance, S.drop_p, emb, cond, direct,
-                                                          None if two_phase else rrg_w, S.norm, frames, rescale, extras, ms)
+                                                          None if two_phase else rrg_w, S.norm, frames, rescale, extras, ms,
+                                                          keep_scores=mapped)
+            if mapped:  # PCA:165-196 on the R + 1-pass direction estimate and the per-view score, before the RePaint phase
+                score_maps["pca_cls_dir"][i] = ops.score_pca(info["direction"], normalize=True, workspace=pca_ws)
+                score_maps["pca_uncond"][i] = ops.score_pca(info["local"], workspace=pca_ws)
             if logs is not None and logs["init_low"] is None:
                 # ED:1023-1024: taken right after the FIRST direction estimate, i.e. before the RePaint phase replaces
                 # ``info`` with the one of the undone sample (ED:1043)
@@ -1366,7 +1397,8 @@ class ElasticDiffusion(nn.Module):
                          rrg_scherduler_cls=CosineScheduler, cosine_scale=3.0, repaint_sampling=True,
                          progress=_identity_progress, condition_image=None, controlnet_conditioning_scale=1.0,
                          trace=None, guidance_rescale=0.0, init_image=None, strength=1.0, mask_image=None, *, mask_blur=0.0,
-                         mask_mode="binary", min_chunks=None, ip_adapter_image=None, ip_adapter_image_embeds=None):
+                         mask_mode="binary", min_chunks=None, ip_adapter_image=None, ip_adapter_image_embeds=None,
+                         score_pca=False):
         """``guidance_rescale`` in [0, 1] (diffusers' keyword; 0 = off): the std rescale of the guided model output of
         arXiv 2305.08891 section 3.4, what zero-terminal-SNR / v-prediction checkpoints are meant to be sampled with
         (DESIGN.md section 17).
@@ -1399,9 +1431,16 @@ class ElasticDiffusion(nn.Module):
         ``ip_adapter_image`` / ``ip_adapter_image_embeds`` (keyword-only): the image prompt of a loaded
         IP-Adapter (``load_ip_adapter``), exactly one of the two -- an RGB PIL image / uint8 [H,W,3] array or tensor (uploaded
         once; CLIP's resize, crop and normalise run on the device, then the ``image_encoder``), or its CLIP image embeddings
-        [1 or B, clip_dim]."""
+        [1 or B, clip_dim].
+
+        ``score_pca`` (keyword-only): the reference's diagnostic pictures (pca_diffusion_scores.py) for this
+        loop.  At every timestep index i with i % log_freq == 0 the class direction (normalised as there) and the local
+        unconditional score of the timestep's first phase are projected onto their first three principal components and scaled to
+        bytes on the device (``ops.score_pca``; nothing syncs); ``last_score_pca`` = {"pca_cls_dir": {i: uint8 [B, Hl, Wl, 3]},
+        "pca_uncond": {...}} afterwards.  It only reads: latents and host RNG stream are those of the run without it."""
         self._check_ip_adapter(ip_adapter_image, ip_adapter_image_embeds)
         check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
+        score_pca = check_score_pca_arguments(score_pca, self._score_channels())
         mask_blur = check_soft_inpaint_arguments(init_image, mask_image, mask_blur, mask_mode,
                                                  latent_size=(height // self.vae_scale_factor, width // self.vae_scale_factor))
         self._check_inpaint9(height, width, init_image, mask_image, mask_mode)
@@ -1409,10 +1448,12 @@ class ElasticDiffusion(nn.Module):
                             rrg_init_weight, rrg_scherduler_cls, cosine_scale, repaint_sampling,
                             controlnet_conditioning_scale, guidance_rescale, strength)
         self._runner.new_image()
+        maps = {} if score_pca else None
         x = self._drive(self._program(S, prompts, negative_prompts, condition_image, trace, progress, direct=True,
                                       init_image=init_image, mask_image=mask_image, mask_blur=mask_blur, mask_mode=mask_mode,
                                       min_chunks=min_chunks, ip_adapter_image=ip_adapter_image,
-                                      ip_adapter_image_embeds=ip_adapter_image_embeds))
+                                      ip_adapter_image_embeds=ip_adapter_image_embeds, score_maps=maps))
+        self.last_score_pca = maps
         self.last_latents = x
         self.host_s["blocked_ahead_of_gpu"] = self._stager.waited
         self._mark("loop_done")
@@ -1428,7 +1469,8 @@ class ElasticDiffusion(nn.Module):
         """Several images of the SAME size / settings in flight at once (new; the reference has nothing like it).
 
         ``jobs`` = list of dicts {prompts, negative_prompts="", seed, condition_image=None, init_image=None,
-        mask_image=None, mask_blur=0.0, mask_mode="binary", ip_adapter_image=None, ip_adapter_image_embeds=None}; ``strength`` is a setting of the call like the other schedule parameters, and jobs with and without
+        mask_image=None, mask_blur=0.0, mask_mode="binary", ip_adapter_image=None, ip_adapter_image_embeds=None, score_pca=False}
+        (``score_pca``: that job's maps, as ``generate_latents`` makes them, in ``job_score_pca[index]``); ``strength`` is a setting of the call like the other schedule parameters, and jobs with and without
         an init image may mix (at ``strength`` 1: below it every job needs one; on a 9-channel inpainting UNet every job carries
         both ``init_image`` and ``mask_image``).  Each job is one
         ``_program`` with its own host RNG stream (``_HostRng``: exactly the stream ``seed_everything(seed)`` +
@@ -1456,6 +1498,7 @@ class ElasticDiffusion(nn.Module):
                 n_chunks = max(n_chunks or 1, n)
         for job in jobs:
             check_img2img_arguments(num_inference_steps, job.get("init_image"), strength, job.get("mask_image"))
+            check_score_pca_arguments(job.get("score_pca", False), self._score_channels())
             if job.get("composite"):
                 raise ValueError("composite is a keyword of generate_image: a job of generate_latents_interleaved returns latents")
             check_soft_inpaint_arguments(job.get("init_image"), job.get("mask_image"), job.get("mask_blur", 0.0),
@@ -1487,16 +1530,19 @@ class ElasticDiffusion(nn.Module):
             if started[0] and not self.cache_backgrounds:
                 frames = (self._strip_frames(S.P.gpad, self._timesteps, S.C), self._strip_frames(S.P.vpad, self._timesteps, S.C))
             started[0] += 1
+            if job.get("score_pca"):
+                self.job_score_pca[j] = {}
             prog = self._program(S, job["prompts"], job.get("negative_prompts", ""), job.get("condition_image"),
                                  direct=False, frames=frames, init_image=job.get("init_image"),
                                  mask_image=job.get("mask_image"), mask_blur=float(job.get("mask_blur", 0.0)),
                                  mask_mode=job.get("mask_mode", "binary"), min_chunks=n_chunks,
                                  ip_adapter_image=job.get("ip_adapter_image"),
-                                 ip_adapter_image_embeds=job.get("ip_adapter_image_embeds"))
+                                 ip_adapter_image_embeds=job.get("ip_adapter_image_embeds"), score_maps=self.job_score_pca.get(j))
             with rng:
                 call = next(prog)
             live.append([j, prog, rng, call])
 
+        self.job_score_pca = {}  # job index -> its PCA maps, for the jobs that carry ``score_pca``
         self.job_events = {}  # job -> [start event, end event] on this device's stream (``job_latencies``)
         self._live_jobs = live  # a change of LoRA state is refused while this list is non-empty (``_lora_change``)
         try:
@@ -1558,13 +1604,16 @@ class ElasticDiffusion(nn.Module):
 
     @_on_own_device
     @torch.no_grad()
-    def generate(self, latent, text_embeds, add_text_embeds, guidance_scale=7.5, guidance_rescale=0.0):
+    def generate(self, latent, text_embeds, add_text_embeds, guidance_scale=7.5, guidance_rescale=0.0, score_pca=False):
         """ED:761-796: plain CFG + DDIM generation of ``latent`` (B,C,h,w; the reference calls it on the initial
         reduced-resolution latent for its ``verbose`` image log) over the scheduler's current timesteps.
         ``text_embeds`` / ``add_text_embeds`` = cat([uncond, cond]) like the reference's.  A latent smaller than the
         model's native size is padded with the noised-background frames (ED:404-411).
         ``guidance_rescale`` > 0: the reference's rescale_noise_cfg (ED:800-811) on uncond + g * (cond - uncond) with
         noise_pred_text = cond, its std ratio computed on the device.
+        ``score_pca``: this loop is the script's own (PCA:151-204); every log_freq steps the PCA maps of
+        cond - uncond (normalised as there) and of uncond are added to the info dict, {"pca_cls_dir": {i: uint8 [B,h,w,3] on the
+        device}, "pca_uncond": {...}}.
         -> (PIL image of the first sample, {"inter_x0": [pred_original_sample every log_freq steps]})"""
         ops.rescale_coefficients(guidance_rescale)
         if self.unet.config.in_channels != 4:
@@ -1572,6 +1621,8 @@ class ElasticDiffusion(nn.Module):
         dev, mdt = self.device, self.model_dtype
         x = latent.to(dev, torch.float32).contiguous()
         B, C, h, w = x.shape
+        maps = {key: {} for key in SCORE_PCA_KEYS} if check_score_pca_arguments(score_pca, C) else {}
+        pca_ws = ops.score_pca_workspace(B, h * w, dev) if maps else None
         if self.scheduler.timesteps is None:
             raise RuntimeError("generate(): call scheduler.set_timesteps / generate_image first (ED:776 iterates them)")
         ts = list(self.scheduler.timesteps)
@@ -1603,6 +1654,9 @@ class ElasticDiffusion(nn.Module):
             uncond, cnd = out[:B].contiguous(), out[B:].contiguous()
             prev, x0 = torch.empty_like(x), torch.empty_like(x)
             direction = (cnd - uncond).contiguous()
+            if maps and i % self.log_freq == 0:
+                maps["pca_cls_dir"][i] = ops.score_pca(direction, normalize=True, workspace=pca_ws)
+                maps["pca_uncond"][i] = ops.score_pca(uncond, workspace=pca_ws)
             if rs_kw:
                 ops.guidance_moments(uncond, direction, np.float32(guidance_scale), rs_kw["ratio"], ws, text=cnd)
             ms = self._multistep_args(t, hist, i == len(ts) - 1)
@@ -1614,7 +1668,7 @@ class ElasticDiffusion(nn.Module):
             x = prev
             if i % self.log_freq == 0:
                 inter.append(x0.cpu())
-        return self._to_pil(self.decode_latents(x))[0], {"inter_x0": inter}
+        return self._to_pil(self.decode_latents(x))[0], {"inter_x0": inter, **maps}
 
     @staticmethod
     def _to_pil(imgs):
@@ -1685,13 +1739,15 @@ class ElasticDiffusion(nn.Module):
                        progress=_default_progress, tiled_decoder=False, grid=False, guidance_rescale=0.0, *,
                        condition_image=None, controlnet_conditioning_scale=1.0, output_type="pil", init_image=None,
                        strength=1.0, mask_image=None, mask_blur=0.0, mask_mode="binary", composite=False,
-                       ip_adapter_image=None, ip_adapter_image_embeds=None):
+                       ip_adapter_image=None, ip_adapter_image_embeds=None, score_pca=False):
         """ED:953-965 signature (ControlNet keywords of EDC:1120-1134 are keyword-only here), then ``guidance_rescale``
         (diffusers' keyword) and, keyword-only, ``init_image`` / ``strength`` / ``mask_image`` / ``mask_blur`` / ``mask_mode``
         (see ``generate_latents``) and ``composite``: paste every decoded picture over the 8-bit init picture through the
         (blurred) pixel mask, ``PIL.Image.composite``'s bytes, in the launch that converts the floats to 8 bit
         (``ops.composite_u8``) -- where the mask is 0 the result IS the init picture.
         ``ip_adapter_image`` / ``ip_adapter_image_embeds``: the image prompt of a loaded IP-Adapter (see ``generate_latents``).
+        ``score_pca``: the PCA maps of ``generate_latents``, the first sample's enlarged by the VAE factor with Pillow's BILINEAR bytes
+        on the device, in ``image_log`` as {"pca_cls_dir": {i: PIL}, "pca_uncond": {i: PIL}} (the script's pictures and names).
         Returns ``(images, image_log)``; images are PIL by default, a float tensor with ``output_type='pt'``."""
         self._check_ip_adapter(ip_adapter_image, ip_adapter_image_embeds)
         check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
@@ -1703,9 +1759,12 @@ class ElasticDiffusion(nn.Module):
                                   cosine_scale, repaint_sampling, progress, condition_image,
                                   controlnet_conditioning_scale, guidance_rescale=guidance_rescale, init_image=init_image,
                                   strength=strength, mask_image=mask_image, mask_blur=mask_blur, mask_mode=mask_mode,
-                                  ip_adapter_image=ip_adapter_image, ip_adapter_image_embeds=ip_adapter_image_embeds)
+                                  ip_adapter_image=ip_adapter_image, ip_adapter_image_embeds=ip_adapter_image_embeds,
+                                  score_pca=score_pca)
         dec = self.tiled_decode if tiled_decoder else self.decode_latents
         image_log = self._image_log(dec, guidance_scale, guidance_rescale) if self.verbose else {}  # ED:1092-1118 (before the final decode)
+        if score_pca:
+            image_log.update(self._score_pca_log(self.last_score_pca))
         imgs = torch.cat([dec(z[i:i + 1]) for i in range(len(z))])  # decode_bs = 1 (ED:1090, 1121)
         self._mark("decode_done")
         if grid:
@@ -1715,6 +1774,18 @@ class ElasticDiffusion(nn.Module):
         if composite:
             return self._composite_pil(imgs), image_log
         return self._to_pil(imgs), image_log
+
+    def _score_pca_log(self, maps):
+        """PCA:180: the first sample's maps enlarged by the VAE factor (``T.Resize`` on a PIL image = ``Image.resize(BILINEAR)``)"""
+        from PIL import Image
+        s = self.vae_scale_factor
+        log = {}
+        for key, by_step in maps.items():
+            log[key] = {}
+            for i, m in by_step.items():
+                big = ops.resize_u8(m[0], (m.shape[1] * s, m.shape[2] * s), filter="bilinear")
+                log[key][i] = Image.fromarray(big.cpu().numpy())
+        return log
 
     def _composite_pil(self, imgs):
         """decoded (B,3,H,W) floats in [0,1] -> PIL images: each pasted over ``last_init_pixels`` through ``last_pixel_mask``"""
@@ -1879,7 +1950,7 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
                        rrg_scherduler_cls=CosineScheduler, cosine_scale=3.0, repaint_sampling=True,
                        progress=_default_progress, tiled_decoder=False, grid=False, guidance_rescale=0.0, *,
                        output_type="pil", init_image=None, strength=1.0, mask_image=None, mask_blur=0.0, mask_mode="binary",
-                       composite=False, ip_adapter_image=None, ip_adapter_image_embeds=None):
+                       composite=False, ip_adapter_image=None, ip_adapter_image_embeds=None, score_pca=False):
         self._check_ip_adapter(ip_adapter_image, ip_adapter_image_embeds)
         check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
         check_soft_inpaint_arguments(init_image, mask_image, mask_blur, mask_mode, composite, output_type, grid,
@@ -1896,4 +1967,5 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
                                       condition_image=cond, controlnet_conditioning_scale=controlnet_conditioning_scale,
                                       output_type=output_type, init_image=init_image, strength=strength,
                                       mask_image=mask_image, mask_blur=mask_blur, mask_mode=mask_mode, composite=composite,
-                                      ip_adapter_image=ip_adapter_image, ip_adapter_image_embeds=ip_adapter_image_embeds)
+                                      ip_adapter_image=ip_adapter_image, ip_adapter_image_embeds=ip_adapter_image_embeds,
+                                      score_pca=score_pca)

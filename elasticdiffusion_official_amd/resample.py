@@ -44,7 +44,15 @@ def _lanczos(x):
     return 0.0
 
 
-FILTERS = {"bicubic": (_bicubic, 2.0), "lanczos": (_lanczos, 3.0)}
+def _bilinear(x):
+    if x < 0.0:
+        x = -x
+    if x < 1.0:
+        return 1.0 - x
+    return 0.0
+
+
+FILTERS = {"bicubic": (_bicubic, 2.0), "lanczos": (_lanczos, 3.0), "bilinear": (_bilinear, 1.0)}
 
 
 def ksize(in_size, out_size, filter):

@@ -783,6 +783,36 @@ enum { ED_LORA_TENSOR_WORDS = 8, ED_LORA_ADAPTER_WORDS = 4, ED_LORA_TILE_N = 64,
 int ed_lora_merge(const int64_t* table_host, const int64_t* table_dev, int n_tensors, int n_adapters, int64_t n_tiles,
                   void* stream);
 
+/*
+ * ---- score PCA maps (additions, still ABI v13): pca_diffusion_scores.py:165-179 on the device.  A score is
+ * f32 [B, C = 4, H, W], dense, n = H * W pixels per sample; sample b's pixels are the rows of X_b [n, 4].
+ *
+ * ed_score_pca_workspace -- no launch: bytes of the workspace both calls below take for B samples of n pixels (0 outside their
+ *   bounds).  8-byte aligned; ed_score_pca_map reads what ed_score_pca_fit left in it.
+ * ed_score_pca_fit -- per sample: mean and covariance (divided by n - 1) of X_b from fp64 sums shifted by the sample's first pixel,
+ *   merged in a fixed order (a fixed number of blocks per sample write partials into the workspace, one wave per sample merges them);
+ *   the covariance diagonalised by cyclic Jacobi in fp64; the three largest eigenpairs in descending order, every component turned
+ *   so that its entry of largest magnitude is positive (sklearn's svd_flip(u_based_decision=False)).
+ *     components f32 [B, 3, 4], mean f32 [B, 4], explained_variance f32 [B, 3], norm f32 [B, 2] = (min, max) of the WHOLE tensor.
+ *   normalize != 0: the fit is that of s' = (s - min) / (max - min) * 2 - 1, the reference's normalisation of the class direction,
+ *   formed per element with its four fp32 operations (one more launch finds min and max first).  A constant tensor (max == min,
+ *   where the reference divides by zero) is left un-normalised.
+ * ed_score_pca_map -- out uint8 [B, H, W, 3]: r_j = fp32(sum_c (x_c - mean_c) components[b][j][c]), the sum in fp64 (differences
+ *   first, then products and sums left to right) from the fit's fp64 mean and components, which it left in the workspace;
+ *   lo / hi = the minimum / maximum of r over the sample's pixels and three components, out = (uint8)((r - lo) / (hi - lo) * 255)
+ *   in fp32, truncated; 0 where hi == lo.  norm: the buffer ed_score_pca_fit wrote when it normalised (x is then s' as above),
+ *   NULL when it did not.
+ *
+ * C != 4, H * W < 4, H * W > 2^28, B < 1, a null or misaligned buffer (4 bytes; the workspace 8) or two buffers that overlap are
+ * hipErrorInvalidValue and nothing is launched.  Two launches each (three for a normalising fit); no host sync, no atomics: equal
+ * inputs give equal bits.
+ */
+int64_t ed_score_pca_workspace(int B, int64_t n);
+int ed_score_pca_fit(const float* score, int B, int C, int H, int W, int normalize, float* components, float* mean,
+                     float* explained_variance, float* norm, void* workspace, void* stream);
+int ed_score_pca_map(const float* score, int B, int C, int H, int W, const float* norm, uint8_t* out, void* workspace,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
