@@ -119,6 +119,9 @@ SIGNATURES = {
     "ed_score_pca_workspace": [_i, _i64],
     "ed_score_pca_fit": [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "ed_score_pca_map": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    "ed_groupnorm_nhwc_f32_weighted": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp],
+    "ed_groupnorm_f32_weighted": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp],
+    "ed_softmax_rows_bias": [_vp, _i64, _i64, _f, _vp, _vp],
 }
 
 _LIB = None

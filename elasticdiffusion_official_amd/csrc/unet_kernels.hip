@@ -932,19 +932,39 @@ k_bias_residual_add_cl(const uint16_t* __restrict__ h, const uint16_t* __restric
 #define GN32_THREADS 256
 #define GN32_CHUNK 65536  // elements per block
 
+// WEIGHTED: pixel (y, x) counts wy[y] * wx[x] times (either vector may be NULL = all ones; the narrowed constant-image encode,
+// DESIGN.md section 27).  Every pixel is summed ONCE by the unweighted code (all-ones weights give the unweighted bits) and the EXCESS
+// (w - 1) of the few heavy pixels in double, in double partials behind the fp32 ones (three times the workspace): a handful of heavy
+// terms can dominate a sum and their rounding would not average out.  The unweighted instantiation is the code it always was.
+template <bool WEIGHTED>
 __global__ void __launch_bounds__(GN32_THREADS)
-k_gn32_partial(const float* __restrict__ x, float* __restrict__ partial, int64_t group_len, int nchunks) {
+k_gn32_partial(const float* __restrict__ x, float* __restrict__ partial, int64_t group_len, int nchunks, const float* __restrict__ wx,
+               const float* __restrict__ wy, int HW, int W) {
   __shared__ double red[2 * (GN32_THREADS / 64)];
   const int64_t ng = blockIdx.y;
   const int chunk = blockIdx.x;
   const float* base = x + ng * group_len;
   const int64_t e0 = (int64_t)chunk * GN32_CHUNK, e1 = e0 + GN32_CHUNK < group_len ? e0 + GN32_CHUNK : group_len;
   float s = 0.f, q = 0.f;
+  double ws = 0.0, wq = 0.0;  // (WEIGHTED) the excess weight's share
   const float K = base[0];
-  auto add = [&](float4 v) {
+  auto weight = [&](int pix) {
+    const int py = pix / W;
+    return (double)(wy ? wy[py] : 1.0f) * (double)(wx ? wx[pix - py * W] : 1.0f) - 1.0;
+  };
+  auto add = [&](float4 v, int64_t e) {
     v.x -= K, v.y -= K, v.z -= K, v.w -= K;
     s += (v.x + v.y) + (v.z + v.w);
     q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+    if (WEIGHTED) {  // HW % 4 == 0: the four pixels share one channel, but (W % 4 != 0) not always one image row
+      const int pix = (int)(e % HW);
+      const double w0 = weight(pix), w1 = weight(pix + 1), w2 = weight(pix + 2), w3 = weight(pix + 3);
+      if (w0 != 0.0 || w1 != 0.0 || w2 != 0.0 || w3 != 0.0) {
+        const double a = v.x, b = v.y, c = v.z, d = v.w;
+        ws += (w0 * a + w1 * b) + (w2 * c + w3 * d);
+        wq += (w0 * (a * a) + w1 * (b * b)) + (w2 * (c * c) + w3 * (d * d));
+      }
+    }
   };
   int64_t i = e0 + 4 * (int64_t)threadIdx.x;
   const int64_t step = 4 * GN32_THREADS;
@@ -953,14 +973,32 @@ k_gn32_partial(const float* __restrict__ x, float* __restrict__ partial, int64_t
 #pragma unroll
     for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const float4*>(base + i + u * step);
 #pragma unroll
-    for (int u = 0; u < 4; ++u) add(v[u]);
+    for (int u = 0; u < 4; ++u) add(v[u], i + u * step);
   }
-  for (; i + 3 < e1; i += step) add(*reinterpret_cast<const float4*>(base + i));
+  for (; i + 3 < e1; i += step) add(*reinterpret_cast<const float4*>(base + i), i);
   double ds = (double)s, dq = (double)q;
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) {
     ds += __shfl_xor(ds, off, 64);
     dq += __shfl_xor(dq, off, 64);
+  }
+  if (WEIGHTED) {  // one more block reduction, of the excess sums
+    __shared__ double ered[2 * (GN32_THREADS / 64)];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      ws += __shfl_xor(ws, off, 64);
+      wq += __shfl_xor(wq, off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) ered[2 * (threadIdx.x >> 6)] = ws, ered[2 * (threadIdx.x >> 6) + 1] = wq;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double es = 0.0, eq = 0.0;
+#pragma unroll
+      for (int w = 0; w < GN32_THREADS / 64; ++w) es += ered[2 * w], eq += ered[2 * w + 1];
+      // [N G, nchunks, 2] doubles behind the [N G, nchunks, 2] floats
+      double* edst = reinterpret_cast<double*>(partial + (int64_t)gridDim.y * nchunks * 2) + (ng * nchunks + chunk) * 2;
+      edst[0] = es, edst[1] = eq;
+    }
   }
   if ((threadIdx.x & 63) == 0) red[2 * (threadIdx.x >> 6)] = ds, red[2 * (threadIdx.x >> 6) + 1] = dq;
   __syncthreads();
@@ -977,7 +1015,7 @@ template <bool ACT>
 __global__ void __launch_bounds__(GN32_THREADS)
 k_gn32_apply(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
              const float* __restrict__ partial, float* __restrict__ out, int64_t group_len, int HW, int cpg, int G,
-             int nchunks, float eps) {
+             int nchunks, float eps, const float* __restrict__ wx, const float* __restrict__ wy, int W) {
   __shared__ float st[2];
   const int64_t ng = blockIdx.y;
   const int chunk = blockIdx.x;
@@ -985,8 +1023,28 @@ k_gn32_apply(const float* __restrict__ x, const float* __restrict__ gamma, const
     double ts = 0.0, tq = 0.0;
     const float* p = partial + ng * nchunks * 2;
     for (int c = 0; c < nchunks; ++c) ts += (double)p[2 * c], tq += (double)p[2 * c + 1];
-    const double dmean = ts / (double)group_len;  // of x - K, K = the group's first element (k_gn32_partial)
-    double var = tq / (double)group_len - dmean * dmean;
+    if (wx || wy) {  // the excess weights' sums: double partials behind the fp32 ones (nothing to add when all weights are 1)
+      const double* e = reinterpret_cast<const double*>(partial + (int64_t)gridDim.y * nchunks * 2) + ng * nchunks * 2;
+      double es = 0.0, eq = 0.0;
+      for (int c = 0; c < nchunks; ++c) es += e[2 * c], eq += e[2 * c + 1];
+      if (es != 0.0) ts += es;
+      if (eq != 0.0) tq += eq;
+    }
+    double count = (double)group_len;
+    if (wx || wy) {  // weighted statistics: cpg * sum(wy) * sum(wx) elements (integers held in fp32: the sums are exact)
+      double sx = W, sy = HW / W;
+      if (wx) {
+        sx = 0.0;
+        for (int i = 0; i < W; ++i) sx += (double)wx[i];
+      }
+      if (wy) {
+        sy = 0.0;
+        for (int i = 0; i < HW / W; ++i) sy += (double)wy[i];
+      }
+      count = sx * sy * (double)cpg;
+    }
+    const double dmean = ts / count;  // of x - K, K = the group's first element (k_gn32_partial)
+    double var = tq / count - dmean * dmean;
     if (var < 0.0) var = 0.0;
     const double mean = (double)x[ng * group_len] + dmean;
     st[0] = (float)mean, st[1] = (float)(1.0 / sqrt(var + (double)eps));
@@ -1023,17 +1081,30 @@ k_gn32_apply(const float* __restrict__ x, const float* __restrict__ gamma, const
 // (fp32 GEMM), replacing F.scaled_dot_product_attention, whose ROCm backend is AOTriton's `attn_fwd` -- the last Triton
 // kernel on the path (profiles/r2_final_bench_*: 0.8 % of GPU time).  One 256-thread block per row; the row (<= 128 KiB)
 // is read twice -- online max / sum in one pass, then normalise -- and written once; the second read hits L2.
-template <int NT>
+// BIAS: softmax(scale * x[r, :] + bias) with one fp32 bias per column -- the log multiplicity of the keys of the narrowed
+// constant-image encode; a zero bias adds nothing, so it gives the bits of the plain instantiation.
+#define LOG2E 1.44269504088896340736f
+template <int NT, bool BIAS>
 __global__ void __launch_bounds__(NT)
-k_softmax_rows_f32(float* __restrict__ x, int64_t cols, float scale_log2e) {
+k_softmax_rows_f32(float* __restrict__ x, int64_t cols, float scale_log2e, const float* __restrict__ bias) {
   __shared__ float red_m[NT / 64], red_s[NT / 64];
   float* row = x + (int64_t)blockIdx.x * cols;
   const int tid = threadIdx.x;
   float m = -INFINITY, sum = 0.f;
   const int64_t nv = cols >> 2;
+  // the exponent-domain score of column j: x * scale * log2 e (+ bias[j] * log2 e)
+  auto sc4 = [&](float4 v, int64_t i) {
+    v.x *= scale_log2e, v.y *= scale_log2e, v.z *= scale_log2e, v.w *= scale_log2e;
+    if (BIAS) {
+      const float4 bv = *reinterpret_cast<const float4*>(bias + 4 * i);
+      v.x += bv.x * LOG2E, v.y += bv.y * LOG2E, v.z += bv.z * LOG2E, v.w += bv.w * LOG2E;
+    }
+    return v;
+  };
+  auto sc1 = [&](float v, int64_t j) { return BIAS ? v * scale_log2e + bias[j] * LOG2E : v * scale_log2e; };
   for (int64_t i = tid; i < nv; i += NT) {
-    const float4 v = *reinterpret_cast<const float4*>(row + 4 * i);
-    const float a = v.x * scale_log2e, b = v.y * scale_log2e, c = v.z * scale_log2e, d = v.w * scale_log2e;
+    const float4 v = sc4(*reinterpret_cast<const float4*>(row + 4 * i), i);
+    const float a = v.x, b = v.y, c = v.z, d = v.w;
     const float mx = fmaxf(fmaxf(a, b), fmaxf(c, d));
     if (mx > m) {
       sum *= __builtin_amdgcn_exp2f(m - mx);
@@ -1042,7 +1113,7 @@ k_softmax_rows_f32(float* __restrict__ x, int64_t cols, float scale_log2e) {
     sum += __builtin_amdgcn_exp2f(a - m) + __builtin_amdgcn_exp2f(b - m) + __builtin_amdgcn_exp2f(c - m) + __builtin_amdgcn_exp2f(d - m);
   }
   for (int64_t i = 4 * nv + tid; i < cols; i += NT) {
-    const float a = row[i] * scale_log2e;
+    const float a = sc1(row[i], i);
     if (a > m) {
       sum *= __builtin_amdgcn_exp2f(m - a);
       m = a;
@@ -1067,14 +1138,14 @@ k_softmax_rows_f32(float* __restrict__ x, int64_t cols, float scale_log2e) {
   for (int w = 0; w < NT / 64; ++w) gs += red_m[w] == -INFINITY ? 0.f : red_s[w] * __builtin_amdgcn_exp2f(red_m[w] - gm);
   const float inv = 1.0f / gs;
   for (int64_t i = tid; i < nv; i += NT) {
-    float4 v = *reinterpret_cast<const float4*>(row + 4 * i);
-    v.x = __builtin_amdgcn_exp2f(v.x * scale_log2e - gm) * inv;
-    v.y = __builtin_amdgcn_exp2f(v.y * scale_log2e - gm) * inv;
-    v.z = __builtin_amdgcn_exp2f(v.z * scale_log2e - gm) * inv;
-    v.w = __builtin_amdgcn_exp2f(v.w * scale_log2e - gm) * inv;
+    float4 v = sc4(*reinterpret_cast<const float4*>(row + 4 * i), i);
+    v.x = __builtin_amdgcn_exp2f(v.x - gm) * inv;
+    v.y = __builtin_amdgcn_exp2f(v.y - gm) * inv;
+    v.z = __builtin_amdgcn_exp2f(v.z - gm) * inv;
+    v.w = __builtin_amdgcn_exp2f(v.w - gm) * inv;
     *reinterpret_cast<float4*>(row + 4 * i) = v;
   }
-  for (int64_t i = 4 * nv + tid; i < cols; i += NT) row[i] = __builtin_amdgcn_exp2f(row[i] * scale_log2e - gm) * inv;
+  for (int64_t i = 4 * nv + tid; i < cols; i += NT) row[i] = __builtin_amdgcn_exp2f(sc1(row[i], i) - gm) * inv;
 }
 
 inline int done() { return (int)hipGetLastError(); }
@@ -1368,33 +1439,63 @@ int64_t ed_groupnorm_f32_workspace(int N, int C, int HW, int G) {
   return (int64_t)N * G * nchunks * 2 * (int64_t)sizeof(float);
 }
 
-int ed_groupnorm_f32(const void* x, const void* gamma, const void* beta, void* out, float* workspace, int N, int C, int HW,
-                     int G, float eps, int act_silu, void* stream) {
+// wx [W] / wy [HW / W]: the optional pixel multiplicities of the weighted entry point (NULL, NULL: W is not looked at)
+static int gn32_launch(const void* x, const void* gamma, const void* beta, void* out, float* workspace, int N, int C, int HW, int W,
+                       int G, float eps, int act_silu, const float* wx, const float* wy, void* stream) {
   if (N == 0) return 0;
   if (G <= 0 || C % G != 0 || HW % 4 != 0 || (((uintptr_t)x | (uintptr_t)out) & 15u) || (int64_t)N * G > 65535)
     return (int)hipErrorInvalidValue;  // (sample, group) is the grid's y dimension
+  if (W <= 0 || HW % W != 0 || (((uintptr_t)wx | (uintptr_t)wy) & 3u) || ((wx || wy) && ((uintptr_t)workspace & 7u)))
+    return (int)hipErrorInvalidValue;  // (weighted: double partials)
   const int cpg = C / G;
   const int64_t group_len = (int64_t)cpg * HW;
   const int64_t nchunks = (group_len + GN32_CHUNK - 1) / GN32_CHUNK;
   if (nchunks > 0x7fffffffll) return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)nchunks, (unsigned)((int64_t)N * G));
-  k_gn32_partial<<<grid, GN32_THREADS, 0, s>>>((const float*)x, workspace, group_len, (int)nchunks);
+  if (wx || wy)
+    k_gn32_partial<true><<<grid, GN32_THREADS, 0, s>>>((const float*)x, workspace, group_len, (int)nchunks, wx, wy, HW, W);
+  else
+    k_gn32_partial<false><<<grid, GN32_THREADS, 0, s>>>((const float*)x, workspace, group_len, (int)nchunks, nullptr, nullptr, HW, W);
   if (act_silu)
     k_gn32_apply<true><<<grid, GN32_THREADS, 0, s>>>((const float*)x, (const float*)gamma, (const float*)beta, workspace,
-                                                    (float*)out, group_len, HW, cpg, G, (int)nchunks, eps);
+                                                    (float*)out, group_len, HW, cpg, G, (int)nchunks, eps, wx, wy, W);
   else
     k_gn32_apply<false><<<grid, GN32_THREADS, 0, s>>>((const float*)x, (const float*)gamma, (const float*)beta, workspace,
-                                                     (float*)out, group_len, HW, cpg, G, (int)nchunks, eps);
+                                                     (float*)out, group_len, HW, cpg, G, (int)nchunks, eps, wx, wy, W);
+  return done();
+}
+
+int ed_groupnorm_f32(const void* x, const void* gamma, const void* beta, void* out, float* workspace, int N, int C, int HW,
+                     int G, float eps, int act_silu, void* stream) {
+  return gn32_launch(x, gamma, beta, out, workspace, N, C, HW, HW > 0 ? HW : 1, G, eps, act_silu, nullptr, nullptr, stream);
+}
+
+int ed_groupnorm_f32_weighted(const void* x, const void* gamma, const void* beta, void* out, float* workspace, int N, int C, int H,
+                              int W, int G, float eps, int act_silu, const float* wx, const float* wy, void* stream) {
+  if (H <= 0 || W <= 0 || (int64_t)H * W > 0x7fffffffll) return (int)hipErrorInvalidValue;
+  return gn32_launch(x, gamma, beta, out, workspace, N, C, H * W, W, G, eps, act_silu, wx, wy, stream);
+}
+
+static int softmax_rows_launch(void* x, int64_t rows, int64_t cols, float scale, const float* bias, void* stream) {
+  if (rows == 0 || cols == 0) return 0;
+  if (rows < 0 || cols < 0 || rows > 0x7fffffffll || ((uintptr_t)x & 15u) || (cols % 4 != 0 && rows > 1))
+    return (int)hipErrorInvalidValue;  // rows start 16-byte aligned when cols % 4 == 0
+  if (bias) {
+    if ((uintptr_t)bias & 15u) return (int)hipErrorInvalidValue;
+    k_softmax_rows_f32<256, true><<<(unsigned)rows, 256, 0, (hipStream_t)stream>>>((float*)x, cols, scale * LOG2E, bias);
+  } else {
+    k_softmax_rows_f32<256, false><<<(unsigned)rows, 256, 0, (hipStream_t)stream>>>((float*)x, cols, scale * LOG2E, nullptr);
+  }
   return done();
 }
 
 int ed_softmax_rows(void* x, int64_t rows, int64_t cols, float scale, void* stream) {
-  if (rows == 0 || cols == 0) return 0;
-  if (rows < 0 || cols < 0 || rows > 0x7fffffffll || ((uintptr_t)x & 15u) || (cols % 4 != 0 && rows > 1))
-    return (int)hipErrorInvalidValue;  // rows start 16-byte aligned when cols % 4 == 0
-  k_softmax_rows_f32<256><<<(unsigned)rows, 256, 0, (hipStream_t)stream>>>((float*)x, cols, scale * 1.44269504088896340736f);
-  return done();
+  return softmax_rows_launch(x, rows, cols, scale, nullptr, stream);
+}
+
+int ed_softmax_rows_bias(void* x, int64_t rows, int64_t cols, float scale, const float* bias, void* stream) {
+  return softmax_rows_launch(x, rows, cols, scale, bias, stream);
 }
 
 int64_t ed_groupnorm_nhwc_workspace(int N, int C, int HW, int G) {

@@ -42,9 +42,18 @@ __device__ __forceinline__ int split_exponent(float absmax) {
 // is the group's first element (pixel 0, channel g * cpg), read by every block of the sample and again by the apply pass: shifted by a
 // sample of the data the sums are a few standard deviations in size, so the fp32 partials and var = qq/n - (ss/n)^2 keep their digits
 // whatever the group's mean.  Fixed summation order: bit-reproducible.
+// WEIGHTED: pixel (y, x) counts wy[y] * wx[x] times (either vector may be NULL = all ones) -- the narrowed constant-image encode, where
+// one row / column stands for a run of identical ones.  Both sums carry the weight; the apply pass divides by the
+// weighted element count.  The weighted sums are kept in two parts: every pixel ONCE, by the unweighted code (same order, same fp32
+// partials: all-ones weights give the unweighted bits), and the EXCESS (w - 1) of the few heavy pixels in double, in double partials
+// [N, nchunks, G, 2] behind the fp32 ones (three times the workspace) -- a handful of heavy terms can dominate a sum, and their rounding
+// errors would not average out as they do over thousands of equal terms.  The unweighted instantiation is the code it always was.
+template <bool WEIGHTED>
 __global__ void __launch_bounds__(GV_THREADS)
-k_gn32_nhwc_partial(const float* __restrict__ x, float* __restrict__ partial, int C, int HW, int G, int rows_per_block) {
-  extern __shared__ float sh[];          // [row lanes][VC][2]
+k_gn32_nhwc_partial(const float* __restrict__ x, float* __restrict__ partial, int C, int HW, int G, int rows_per_block,
+                    const float* __restrict__ wx, const float* __restrict__ wy, int W) {
+  extern __shared__ double sh_raw[];
+  float* sh = reinterpret_cast<float*>(sh_raw);          // [row lanes][VC][2]
   const int n = blockIdx.y, chunk = blockIdx.x;
   const int VC = C >> 2, cpg = C / G;
   const int ncol = (VC + GV_THREADS - 1) / GV_THREADS;        // columns per thread (1 for C <= 1024)
@@ -59,11 +68,21 @@ k_gn32_nhwc_partial(const float* __restrict__ x, float* __restrict__ partial, in
       const int vc = my_c + j * GV_THREADS;
       if (vc >= VC) break;
       float s = 0.f, q = 0.f;
+      double es = 0.0, eq = 0.0;  // (WEIGHTED) the excess weight's share
       const float K = base[((vc << 2) / cpg) * cpg];
-      auto add = [&](float4 v) {
+      auto add = [&](float4 v, int pix) {
         v.x -= K, v.y -= K, v.z -= K, v.w -= K;
         s += (v.x + v.y) + (v.z + v.w);
         q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+        if (WEIGHTED) {
+          const int py = pix / W;
+          const double w = (double)(wy ? wy[py] : 1.0f) * (double)(wx ? wx[pix - py * W] : 1.0f) - 1.0;
+          if (w != 0.0) {
+            const double a = v.x, b = v.y, c = v.z, d = v.w;
+            es += w * ((a + b) + (c + d));
+            eq += w * ((a * a + b * b) + (c * c + d * d));
+          }
+        }
       };
       const float* col = base + (vc << 2);
       const int64_t step = (int64_t)R * C;
@@ -74,11 +93,15 @@ k_gn32_nhwc_partial(const float* __restrict__ x, float* __restrict__ partial, in
 #pragma unroll
         for (int u = 0; u < GV_UNROLL; ++u) v[u] = *reinterpret_cast<const float4*>(p0 + u * step);
 #pragma unroll
-        for (int u = 0; u < GV_UNROLL; ++u) add(v[u]);
+        for (int u = 0; u < GV_UNROLL; ++u) add(v[u], row + u * R);
       }
-      for (; row < r1; row += R) add(*reinterpret_cast<const float4*>(col + (int64_t)row * C));
+      for (; row < r1; row += R) add(*reinterpret_cast<const float4*>(col + (int64_t)row * C), row);
       float* slot = sh + ((int64_t)my_r * VC + vc) * 2;
       slot[0] = s, slot[1] = q;
+      if (WEIGHTED) {  // the double slots lie behind the R * VC float pairs
+        double* eslot = sh_raw + (int64_t)R * VC + ((int64_t)my_r * VC + vc) * 2;
+        eslot[0] = es, eslot[1] = eq;
+      }
     }
   }
   __syncthreads();
@@ -94,6 +117,19 @@ k_gn32_nhwc_partial(const float* __restrict__ x, float* __restrict__ partial, in
       }
     dst[2 * g] = (float)s;
     dst[2 * g + 1] = (float)q;
+    if (WEIGHTED) {
+      double es = 0.0, eq = 0.0;
+      for (int vc = g * cols_per_group; vc < (g + 1) * cols_per_group; ++vc)
+        for (int r = 0; r < R; ++r) {
+          const double* eslot = sh_raw + (int64_t)R * VC + ((int64_t)r * VC + vc) * 2;
+          es += eslot[0];
+          eq += eslot[1];
+        }
+      // [N, nchunks, G, 2] doubles behind the [gridDim.y, nchunks, G, 2] floats
+      double* edst = reinterpret_cast<double*>(partial + (int64_t)gridDim.y * gridDim.x * 2 * G) + ((int64_t)n * gridDim.x + chunk) * 2 * G;
+      edst[2 * g] = es;
+      edst[2 * g + 1] = eq;
+    }
   }
 }
 
@@ -104,7 +140,7 @@ template <bool ACT, bool SPLIT>
 __global__ void __launch_bounds__(GV_THREADS)
 k_gn32_nhwc_apply(const float* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
                   const float* __restrict__ partial, void* __restrict__ out, int C, int HW, int G, int rows_per_block, double count,
-                  float eps) {
+                  float eps, const float* __restrict__ wx, const float* __restrict__ wy, int W) {
   __shared__ double red[2 * GV_THREADS];
   __shared__ float stats[2 * GV_MAXG];
   // (walked back to front, like the 16-bit kernel's apply pass: what the statistics pass read last is what the last-level cache still holds)
@@ -127,6 +163,28 @@ k_gn32_nhwc_apply(const float* __restrict__ x, const float* __restrict__ gamma, 
       for (int k = 0; k < parts; ++k) {
         ss += red[2 * (k * G + threadIdx.x)];
         qq += red[2 * (k * G + threadIdx.x) + 1];
+      }
+      if (wx || wy) {  // weighted statistics: the excess weights' sums (double partials behind the fp32 ones; nothing to add when all
+                       // weights are 1), and the element count (C / G) sum(wy) sum(wx) (integers held in fp32: the sums are exact)
+        const double* e = reinterpret_cast<const double*>(partial + (int64_t)gridDim.y * nchunks * 2 * G) + (int64_t)n * nchunks * 2 * G +
+                          2 * threadIdx.x;
+        double es = 0.0, eq = 0.0;
+        for (int c = 0; c < nchunks; ++c) {
+          es += e[(int64_t)c * 2 * G];
+          eq += e[(int64_t)c * 2 * G + 1];
+        }
+        if (es != 0.0) ss += es;
+        if (eq != 0.0) qq += eq;
+        double sx = W, sy = HW / W;
+        if (wx) {
+          sx = 0.0;
+          for (int i = 0; i < W; ++i) sx += (double)wx[i];
+        }
+        if (wy) {
+          sy = 0.0;
+          for (int i = 0; i < HW / W; ++i) sy += (double)wy[i];
+        }
+        count = sx * sy * (double)(C / G);
       }
       const double dmean = ss / count;  // of x - K (k_gn32_nhwc_partial)
       double var = qq / count - dmean * dmean;
@@ -262,6 +320,34 @@ inline int gv_chunks(int C, int HW, int* rows_per_block) {
   return (HW + rpb - 1) / rpb;
 }
 
+// both GroupNorm entry points: wx [W] / wy [HW / W] are the optional pixel multiplicities (NULL, NULL: W is not looked at)
+int gn32_nhwc_launch(const void* x, const void* gamma, const void* beta, void* out, float* workspace, int N, int C, int HW, int W, int G,
+                     float eps, int act_silu, int split16, const float* wx, const float* wy, void* stream) {
+  if (N == 0) return 0;
+  if (N < 0 || HW <= 0 || W <= 0 || HW % W != 0 || (((uintptr_t)wx | (uintptr_t)wy) & 3u) || G <= 0 || G > GV_MAXG || C % G != 0 ||
+      (C / G) % 4 != 0 || C > 4 * GV_THREADS * 4 || N > 65535 ||
+      (((uintptr_t)x | (uintptr_t)out | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)workspace) & 15u))
+    return (int)hipErrorInvalidValue;
+  hipStream_t s = (hipStream_t)stream;
+  int rpb;
+  const int nchunks = gv_chunks(C, HW, &rpb);
+  dim3 grid(nchunks, N);
+  const int VC = C / 4;
+  const size_t lds = sizeof(float) * 2 * (size_t)VC * (VC <= GV_THREADS ? GV_THREADS / VC : 1);
+  if (wx || wy) k_gn32_nhwc_partial<true><<<grid, GV_THREADS, 3 * lds, s>>>((const float*)x, workspace, C, HW, G, rpb, wx, wy, W);
+  else k_gn32_nhwc_partial<false><<<grid, GV_THREADS, lds, s>>>((const float*)x, workspace, C, HW, G, rpb, nullptr, nullptr, W);
+  const double count = (double)HW * (C / G);
+#define GV_APPLY(ACT, SPLIT)                                                                                                      \
+  k_gn32_nhwc_apply<ACT, SPLIT><<<grid, GV_THREADS, 0, s>>>((const float*)x, (const float*)gamma, (const float*)beta, workspace, \
+                                                            out, C, HW, G, rpb, count, eps, wx, wy, W)
+  if (act_silu && split16) GV_APPLY(true, true);
+  else if (act_silu) GV_APPLY(true, false);
+  else if (split16) GV_APPLY(false, true);
+  else GV_APPLY(false, false);
+#undef GV_APPLY
+  return done();
+}
+
 }  // namespace
 
 extern "C" {
@@ -275,27 +361,13 @@ int64_t ed_groupnorm_nhwc_f32_workspace(int N, int C, int HW, int G) {
 
 int ed_groupnorm_nhwc_f32(const void* x, const void* gamma, const void* beta, void* out, float* workspace, int N, int C, int HW, int G,
                           float eps, int act_silu, int split16, void* stream) {
-  if (N == 0) return 0;
-  if (N < 0 || G <= 0 || G > GV_MAXG || C % G != 0 || (C / G) % 4 != 0 || C > 4 * GV_THREADS * 4 || N > 65535 ||
-      (((uintptr_t)x | (uintptr_t)out | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)workspace) & 15u))
-    return (int)hipErrorInvalidValue;
-  hipStream_t s = (hipStream_t)stream;
-  int rpb;
-  const int nchunks = gv_chunks(C, HW, &rpb);
-  dim3 grid(nchunks, N);
-  const int VC = C / 4;
-  const size_t lds = sizeof(float) * 2 * (size_t)VC * (VC <= GV_THREADS ? GV_THREADS / VC : 1);
-  k_gn32_nhwc_partial<<<grid, GV_THREADS, lds, s>>>((const float*)x, workspace, C, HW, G, rpb);
-  const double count = (double)HW * (C / G);
-#define GV_APPLY(ACT, SPLIT)                                                                                                      \
-  k_gn32_nhwc_apply<ACT, SPLIT><<<grid, GV_THREADS, 0, s>>>((const float*)x, (const float*)gamma, (const float*)beta, workspace, \
-                                                            out, C, HW, G, rpb, count, eps)
-  if (act_silu && split16) GV_APPLY(true, true);
-  else if (act_silu) GV_APPLY(true, false);
-  else if (split16) GV_APPLY(false, true);
-  else GV_APPLY(false, false);
-#undef GV_APPLY
-  return done();
+  return gn32_nhwc_launch(x, gamma, beta, out, workspace, N, C, HW, HW, G, eps, act_silu, split16, nullptr, nullptr, stream);
+}
+
+int ed_groupnorm_nhwc_f32_weighted(const void* x, const void* gamma, const void* beta, void* out, float* workspace, int N, int C, int H,
+                                   int W, int G, float eps, int act_silu, int split16, const float* wx, const float* wy, void* stream) {
+  if (H <= 0 || W <= 0 || (int64_t)H * W > 0x7fffffffll) return (int)hipErrorInvalidValue;
+  return gn32_nhwc_launch(x, gamma, beta, out, workspace, N, C, H * W, W, G, eps, act_silu, split16, wx, wy, stream);
 }
 
 int ed_absmax_f32(const void* x, int64_t n, float* out, void* stream) {

@@ -314,3 +314,65 @@ class TilePlan:
         rt, rs = one(self.rows, self.H)
         ct, cs = one(self.cols, self.W)
         return rt, rs, ct, cs
+
+
+# ---------------------------------------------------------------------------------------------------
+# the VAE encoder on a constant-colour image (DESIGN.md section 27)
+# ---------------------------------------------------------------------------------------------------
+def constant_border_trace(levels=4, layers=2):
+    """[(stage, level, lead, trail)]: how far, along one axis, the encoder's activations on a CONSTANT image differ from their interior
+    value AFTER each stage -- only zero padding makes them vary.  A 3 x 3 pad-1 convolution adds one row / column on each side (a
+    ResnetBlock has two); 1 x 1 convolutions, GroupNorm and the attention add none (they are pointwise or enter through global
+    sums); the pad-(0, 1, 0, 1) stride-2 downsampler maps lead -> ceil(lead / 2) (output j reads inputs 2j .. 2j + 2) and
+    trail -> floor(trail / 2) + 1 (its last output reads the pad).  In units of the stage's own level; level l has 2^(levels-1-l)
+    rows / columns per latent unit."""
+    lead = trail = 1
+    trace = [("conv_in", 0, lead, trail)]
+    for lv in range(levels):
+        for k in range(layers):
+            lead, trail = lead + 2, trail + 2
+            trace.append((f"down{lv}.resnet{k}", lv, lead, trail))
+        if lv < levels - 1:
+            lead, trail = -(-lead // 2), trail // 2 + 1
+            trace.append((f"down{lv}.downsample", lv + 1, lead, trail))
+    last = levels - 1
+    for name, grow in (("mid.resnet0", 2), ("mid.attention", 0), ("mid.resnet1", 2), ("conv_out", 1)):
+        lead, trail = lead + grow, trail + grow
+        trace.append((name, last, lead, trail))
+    return trace
+
+
+@dataclass
+class ConstantAxisPlan:
+    """One axis of ``L`` latent units narrowed to ``keep``: latent unit ``rep_lat`` stands for itself and the ``L - keep`` units
+    removed next to it.  ``weights[l]``: the multiplicity of every row / column of the narrowed level-l activation (all 1 except the
+    representative ``rep[l]``); ``expand``: for each of the L latent units the narrowed unit that holds its value."""
+    L: int
+    keep: int
+    rep_lat: int
+    rep: list
+    weights: list
+    expand: list
+
+
+def plan_constant_axis(L, levels=4, layers=2):
+    """ConstantAxisPlan for an axis of ``L`` latent units, or None when the axis is left alone (L < 2 keep).  keep = final lead +
+    trail + 4, rounded up to a multiple of 8 (32 for the SD / SDXL VAE: 13 + 14 + 4 = 31); the representative of level l (s = 2^(levels
+    -1-l) rows / columns per latent unit) is rep_lat * s + s / 2 with rep_lat = keep / 2 - 1 and weighs 1 + (R >> l), R = (L - keep)
+    2^(levels-1): the removed run, always a whole number of downsampler windows, so every level's weights sum to the full size."""
+    _, _, lead, trail = constant_border_trace(levels, layers)[-1]
+    keep = -(-(lead + trail + 4) // 8) * 8
+    if L < 2 * keep:
+        return None
+    S = 1 << (levels - 1)
+    rep_lat, R = keep // 2 - 1, (L - keep) * S
+    rep, weights = [], []
+    for lv in range(levels):
+        s = S >> lv
+        r = rep_lat * s + s // 2
+        w = [1] * (keep * s)
+        w[r] += R >> lv
+        rep.append(r)
+        weights.append(w)
+    expand = [i if i <= rep_lat else (rep_lat if i <= rep_lat + L - keep else i - (L - keep)) for i in range(L)]
+    return ConstantAxisPlan(L, keep, rep_lat, rep, weights, expand)

@@ -13,12 +13,14 @@ layout, GEGLU) is fused into hand-written HIP kernels (csrc/unet_kernels.hip) fo
 """
 import math
 import os
+import threading
 from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .geometry import plan_constant_axis
 from . import ops      # (imports without the shared library: it is loaded at the first launch)
 
 
@@ -83,6 +85,45 @@ def _f32_bias(mod):
     return None if b is None else _derived(mod, "bias32", (b,), lambda: b.detach().float())
 
 
+# The narrowed constant-image encode (AutoencoderKL.encode_constant): {(H, W) of an activation: (wx [W] | None, wy [H] | None, key_bias
+# [H * W] | None)} -- the multiplicity of every column / row of the encoder's activations at that size, and its logarithm per token for
+# the mid-block attention.  Set (per thread) only while such an encode runs: every GroupNorm and the attention are otherwise what
+# they always were.
+_CONSTANT_ENCODE = threading.local()
+
+
+def _narrowed_encode_active():
+    return getattr(_CONSTANT_ENCODE, "planes", None) is not None
+
+
+def _plane_weights(x):
+    planes = getattr(_CONSTANT_ENCODE, "planes", None)
+    return (None, None, None) if planes is None else planes.get((x.shape[2], x.shape[3]), (None, None, None))
+
+
+def _weighted_group_norm(norm, x, wx, wy, silu):
+    """GroupNorm [+ SiLU] whose statistics count pixel (y, x) wy[y] * wx[x] times: the HIP kernels for the fp32 layouts the product runs
+    (ed_groupnorm_nhwc_f32_weighted / ed_groupnorm_f32_weighted), plain torch for everything else (CPU, fp64, 16-bit)."""
+    N, C, H, W = x.shape
+    G = norm.num_groups
+    if FUSED_KERNELS and x.is_cuda and x.dtype == torch.float32 and norm.weight.dtype == torch.float32:
+        w32 = [None if w is None else w.float() for w in (wx, wy)]
+        if VAE_SPLIT_CONV and ops.is_nhwc(x) and ops.groupnorm_nhwc_f32_ok(C, G):
+            return ops.groupnorm_nhwc_f32(x, norm.weight, norm.bias, G, norm.eps, silu=silu, wx=w32[0], wy=w32[1])
+        if VAE_HIP_GROUPNORM and x.is_contiguous() and (H * W) % 4 == 0 and N * G <= 65535:
+            return ops.groupnorm_f32(x, norm.weight, norm.bias, G, norm.eps, silu=silu, wx=w32[0], wy=w32[1])
+    dt = torch.float32 if x.dtype in _HALF else x.dtype
+    xf = x.to(dt).reshape(N, G, C // G, H, W)
+    w = (torch.ones(H, dtype=dt, device=x.device) if wy is None else wy.to(dt))[:, None] \
+        * (torch.ones(W, dtype=dt, device=x.device) if wx is None else wx.to(dt))[None, :]
+    count = w.sum() * (C // G)
+    mean = (xf * w).sum((2, 3, 4), keepdim=True) / count
+    d = xf - mean
+    var = (d * d * w).sum((2, 3, 4), keepdim=True) / count
+    y = (d * torch.rsqrt(var + norm.eps)).reshape(N, C, H, W) * norm.weight.to(dt)[None, :, None, None] + norm.bias.to(dt)[None, :, None, None]
+    return (F.silu(y) if silu else y).to(x.dtype)
+
+
 def group_norm_act(norm, x, silu=False, tokens=False, chan_bias=None, conv_bias=None):
     """GroupNorm [+ SiLU] [-> (N, H*W, C) token layout] of ``x``, or of ``(x + conv_bias[c]) + chan_bias[n, c]``: the
     bias of the (bias-free) convolution that produced x and the time-embedding add of ResnetBlock2D, folded into the
@@ -90,6 +131,12 @@ def group_norm_act(norm, x, silu=False, tokens=False, chan_bias=None, conv_bias=
     N, C, H, W = x.shape
     G = norm.num_groups
     cpg = C // G
+    wx, wy, _ = _plane_weights(x)
+    if wx is not None or wy is not None:
+        if tokens or chan_bias is not None or conv_bias is not None:
+            # the narrowed encode runs its ResnetBlocks without folded biases (ResnetBlock2D.forward) and never asks for tokens
+            raise RuntimeError("group_norm_act: weighted statistics take no folded bias and no token layout")
+        return _weighted_group_norm(norm, x, wx, wy, silu)
     s32 = _stream32(x, norm.weight.dtype)
     nhwc = not s32 and _fusable_nhwc(x) and C % 8 == 0 and cpg >= 8
     if (chan_bias is not None or conv_bias is not None) and (
@@ -173,6 +220,10 @@ VAE_NCHW_RESIDUAL = True
 # boundary).  As accurate against fp64 as the library's fp32 convolution (tests/test_vae_split.py).
 VAE_SPLIT_CONV = True
 VAE_SPLIT_DOWNSAMPLE = True   # round 6: the encoder's stride-2 downsamplers on the split-operand path as well (ed_conv3x3_nhwc_f32out_s2)
+# AutoencoderKL.encode_constant (the pad strips: constant-colour images) runs the encoder on an image narrowed to the non-constant border
+# plus one weighted row / column per level (geometry.plan_constant_axis) -- 4x fewer pixels for a 256 x 1024 px strip.
+# False: the full image through ``encode``.
+VAE_NARROW_CONSTANT = True
 # A/B switch from the environment: ED_DISABLE=FLASH_ATTENTION,FUSED_QKV,... turns the named module switches off
 for _name in filter(None, os.environ.get("ED_DISABLE", "").split(",")):
     if _name not in globals() or not isinstance(globals()[_name], bool):
@@ -377,6 +428,11 @@ class ResnetBlock2D(nn.Module):
         tb = self.time_emb_proj(F.silu(temb)) if self.time_emb_proj is not None else None
         sc, c1, c2 = self.conv_shortcut, self.conv1, self.conv2
         cout = c1.out_channels
+        if _narrowed_encode_active():
+            # AutoencoderKL.encode_constant off the split path (CPU, fp64, a 16-bit VAE, VAE_SPLIT_CONV off): the plain block -- the
+            # weighted GroupNorm folds no bias in and returns NCHW, which the fused branches below do not take
+            h = c1(group_norm_act(self.norm1, x, silu=True))
+            return (x if sc is None else sc(x)) + c2(group_norm_act(self.norm2, h, silu=True))
         if _stream32(x, c1.weight.dtype):
             # fp32 residual stream (UNet2DConditionModel.residual_fp32): both branches in the model dtype -- the same GroupNorm -> convolution
             # kernels from norm1's output on -- and ONE fp32 add onto the stream
@@ -470,12 +526,14 @@ class ResnetBlock2D(nn.Module):
         n1, n2, sc = self.norm1, self.norm2, self.conv_shortcut
         _, cin, H, W = x.shape
 
+        wx, wy, _ = _plane_weights(x)    # the narrowed constant-image encode: weighted statistics (None, None otherwise)
+
         def block(xs):
             w1, s1 = _split_weight(self.conv1)
             w2, s2 = _split_weight(self.conv2)
-            a = ops.groupnorm_nhwc_f32(xs, n1.weight, n1.bias, n1.num_groups, n1.eps, silu=True, split=True)
+            a = ops.groupnorm_nhwc_f32(xs, n1.weight, n1.bias, n1.num_groups, n1.eps, silu=True, split=True, wx=wx, wy=wy)
             h = ops.conv3x3_f32out(a, w1, self.conv1.bias, None, s1)
-            a = ops.groupnorm_nhwc_f32(h, n2.weight, n2.bias, n2.num_groups, n2.eps, silu=True, split=True)
+            a = ops.groupnorm_nhwc_f32(h, n2.weight, n2.bias, n2.num_groups, n2.eps, silu=True, split=True, wx=wx, wy=wy)
             res = xs if sc is None else _shortcut_nhwc(sc, xs)    # 1x1 convolution = an fp32 GEMM over the NHWC view
             return ops.conv3x3_f32out(a, w2, self.conv2.bias, res, s2)
 
@@ -1178,11 +1236,18 @@ class _VaeAttention(nn.Module):
     def forward(self, x):
         B, C, H, W = x.shape
         h = group_norm_act(self.group_norm, x)
+        key_bias = _plane_weights(x)[2]   # the narrowed constant-image encode: log multiplicity of every key (None otherwise)
         cl = ops.is_nhwc(h)   # channels-last VAE (VAE_SPLIT_CONV)
         h = h.permute(0, 2, 3, 1).reshape(B, H * W, C) if cl else h.view(B, C, H * W).transpose(1, 2)
         if VAE_HIP_ATTENTION and h.is_cuda and h.dtype == torch.float32 and (H * W) % 4 == 0:
             # two fp32 library GEMMs around ed_softmax_rows: no AOTriton (Triton) kernel on the path
-            o = ops.vae_attention(self.to_q(h), self.to_k(h), self.to_v(h))
+            o = ops.vae_attention(self.to_q(h), self.to_k(h), self.to_v(h), None if key_bias is None else key_bias.float())
+        elif key_bias is not None:
+            # scores + log multiplicity, formed in fp32 for a 16-bit VAE (log 769 in fp16 would be 3e-3 off); a few thousand tokens
+            dt = torch.float32 if h.dtype in _HALF else h.dtype
+            q, k, v = (f(h).to(dt) for f in (self.to_q, self.to_k, self.to_v))
+            scores = torch.baddbmm(key_bias.to(dt).view(1, 1, -1), q, k.transpose(1, 2), alpha=C ** -0.5)
+            o = torch.bmm(scores.softmax(-1), v).to(h.dtype)
         else:
             q, k, v = (f(h).unsqueeze(1) for f in (self.to_q, self.to_k, self.to_v))
             o = F.scaled_dot_product_attention(q, k, v).squeeze(1)
@@ -1298,6 +1363,62 @@ class AutoencoderKL(nn.Module):
 
     def encode(self, x):
         return SimpleNamespace(latent_dist=DiagonalGaussian(self.quant_conv(self.encoder(x))))
+
+    def constant_plan(self, Hpx, Wpx):
+        """(rows, columns): geometry.plan_constant_axis of a constant ``Hpx`` x ``Wpx`` image for this encoder, None for an axis that
+        is left alone (too short, not a whole number of latent units, or VAE_NARROW_CONSTANT off)"""
+        levels = len(self.config.block_out_channels)
+        S = 1 << (levels - 1)
+        layers = len(self.encoder.down_blocks[0].resnets)
+        if not VAE_NARROW_CONSTANT or Hpx % S or Wpx % S:
+            return None, None
+        return plan_constant_axis(Hpx // S, levels, layers), plan_constant_axis(Wpx // S, levels, layers)
+
+    def _constant_tables(self, py, px, Hn, Wn, device):
+        """({(H, W) of the narrowed level-l activation: (wx, wy, key_bias)}, expand index of the latent rows, of the latent columns) on
+        ``device``, built once per plan.  fp32 (what the kernels read; the multiplicities are small integers), fp64 for an fp64 VAE;
+        key_bias[y * W + x] = log wy[y] + log wx[x], the log multiplicity of a token."""
+        key = (None if py is None else py.L, None if px is None else px.L, Hn, Wn, str(device), self.dtype)
+        cache = self.__dict__.setdefault("_constant_cache", {})
+        if key not in cache:
+            dt = torch.float64 if self.dtype == torch.float64 else torch.float32
+            planes = {}
+            for lv in range(len(self.config.block_out_channels)):
+                wy = torch.ones(Hn >> lv, dtype=dt) if py is None else torch.tensor(py.weights[lv], dtype=dt)
+                wx = torch.ones(Wn >> lv, dtype=dt) if px is None else torch.tensor(px.weights[lv], dtype=dt)
+                bias = (wy.double().log()[:, None] + wx.double().log()[None, :]).reshape(-1).to(dt)
+                planes[(Hn >> lv, Wn >> lv)] = (None if px is None else wx.to(device), None if py is None else wy.to(device), bias.to(device))
+            index = [None if p is None else torch.tensor(p.expand, dtype=torch.int64, device=device) for p in (py, px)]
+            cache[key] = (planes, index)
+        return cache[key]
+
+    @torch.no_grad()
+    def encode_constant(self, colour, Hpx, Wpx):
+        """``encode`` of the constant-colour images ``colour`` [n, 3] expanded to [n, 3, Hpx, Wpx], without encoding what is constant
+        (DESIGN.md section 27): the encoder's activations vary only in a border that zero padding makes (geometry.constant_border_trace),
+        so it runs on an image with every long axis narrowed to that border plus a clean margin, in which ONE row / column per level
+        stands for the removed run: GroupNorm's statistics and the attention's softmax count it with its multiplicity, everything else is
+        local.  The moments are then expanded by repeating the representative latent row / column.  Exact in exact arithmetic; in fp32
+        the sums are re-associated.  An image too small to narrow is ``encode`` of the expanded image, bit for bit."""
+        n = colour.shape[0]
+        py, px = self.constant_plan(Hpx, Wpx)
+        if py is None and px is None:
+            return self.encode(colour[:, :, None, None].expand(n, 3, Hpx, Wpx).contiguous())
+        S = 1 << (len(self.config.block_out_channels) - 1)
+        Hn, Wn = (Hpx if py is None else py.keep * S), (Wpx if px is None else px.keep * S)
+        planes, (iy, ix) = self._constant_tables(py, px, Hn, Wn, colour.device)
+        if _narrowed_encode_active():
+            raise RuntimeError("encode_constant: a narrowed encode is already running on this thread")
+        _CONSTANT_ENCODE.planes = planes
+        try:
+            moments = self.quant_conv(self.encoder(colour[:, :, None, None].expand(n, 3, Hn, Wn).contiguous()))
+        finally:
+            _CONSTANT_ENCODE.planes = None
+        if iy is not None:
+            moments = moments.index_select(2, iy)
+        if ix is not None:
+            moments = moments.index_select(3, ix)
+        return SimpleNamespace(latent_dist=DiagonalGaussian(moments))
 
     def decode(self, z):
         return SimpleNamespace(sample=self.decoder(self.post_quant_conv(z)))

@@ -998,18 +998,32 @@ def tokens_add_nchw(x, tokens):
     return out
 
 
-def groupnorm_f32(x, gamma, beta, groups, eps, silu=False):
-    """x fp32 [N,C,H,W] NCHW-contiguous -> GroupNorm(+SiLU), fp32 (the VAE's normalisation layers; ed_groupnorm_f32)."""
+def _pixel_weights(what, wx, wy, H, W):
+    """the optional fp32 multiplicity vectors wx [W] / wy [H] of a weighted GroupNorm, checked"""
+    for name, w, n in (("wx", wx, W), ("wy", wy, H)):
+        if w is not None and tuple(w.shape) != (n,):
+            _reject(f"{what}: {name} must have shape ({n},), got {tuple(w.shape)}")
+    return _opt(wx, torch.float32, "wx"), _opt(wy, torch.float32, "wy")
+
+
+def groupnorm_f32(x, gamma, beta, groups, eps, silu=False, wx=None, wy=None):
+    """x fp32 [N,C,H,W] NCHW-contiguous -> GroupNorm(+SiLU), fp32 (the VAE's normalisation layers; ed_groupnorm_f32).  ``wx`` [W] /
+    ``wy`` [H] (fp32, optional): pixel (y, x) counts wy[y] * wx[x] times in the statistics (ed_groupnorm_f32_weighted)."""
     N, C, H, W = x.shape
     if (H * W) % 4:
         _reject("groupnorm_f32: H*W must be a multiple of 4")
     out = torch.empty_like(x)
-    nbytes = _hip.lib().ed_groupnorm_f32_workspace(N, C, H * W, groups)
+    nbytes = _hip.lib().ed_groupnorm_f32_workspace(N, C, H * W, groups) * (1 if wx is None and wy is None else 3)   # (+ double partials)
     ws = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=x.device)
-    TIMER.note_work("ed_groupnorm_f32", nbytes=3.0 * x.numel() * 4)
-    _call("ed_groupnorm_f32", _dev(x, torch.float32, "x"), _dev(gamma, torch.float32, "gamma"), _dev(beta, torch.float32, "beta"),
-          _dev(out, torch.float32, "out"), _dev(ws, torch.float32, "workspace"), N, C, H * W, groups, float(eps), int(silu),
-          _stream())
+    head = (_dev(x, torch.float32, "x"), _dev(gamma, torch.float32, "gamma"), _dev(beta, torch.float32, "beta"),
+            _dev(out, torch.float32, "out"), _dev(ws, torch.float32, "workspace"))
+    if wx is None and wy is None:
+        TIMER.note_work("ed_groupnorm_f32", nbytes=3.0 * x.numel() * 4)
+        _call("ed_groupnorm_f32", *head, N, C, H * W, groups, float(eps), int(silu), _stream())
+    else:
+        px, py = _pixel_weights("groupnorm_f32", wx, wy, H, W)
+        TIMER.note_work("ed_groupnorm_f32_weighted", nbytes=3.0 * x.numel() * 4)
+        _call("ed_groupnorm_f32_weighted", *head, N, C, H, W, groups, float(eps), int(silu), px, py, _stream())
     return out
 
 
@@ -1018,10 +1032,11 @@ def groupnorm_nhwc_f32_ok(C, groups):
     return C % groups == 0 and (C // groups) % 4 == 0 and groups <= 256 and C <= 4096
 
 
-def groupnorm_nhwc_f32(x, gamma, beta, groups, eps, silu=False, split=False):
+def groupnorm_nhwc_f32(x, gamma, beta, groups, eps, silu=False, split=False, wx=None, wy=None):
     """x [N,C,H,W] fp32 in channels_last memory -> GroupNorm(+SiLU) in fp32, returned as fp32 channels_last [N,C,H,W] or, with
     ``split``, as the fp16 channels_last [N,3C,H,W] = [hi | lo | hi] operand of ``conv3x3_f32out`` (hi = fp16(y), lo = fp16(y - hi)).
-    See ed_groupnorm_nhwc_f32."""
+    See ed_groupnorm_nhwc_f32.  ``wx`` [W] / ``wy`` [H] (fp32, optional): pixel (y, x) counts wy[y] * wx[x] times in the statistics
+    (ed_groupnorm_nhwc_f32_weighted)."""
     if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.dtype == torch.float32):
         _reject("groupnorm_nhwc_f32: x must be an fp32 [N,C,H,W] tensor on the MI355X; no CPU fallback")
     N, C, H, W = x.shape
@@ -1032,11 +1047,18 @@ def groupnorm_nhwc_f32(x, gamma, beta, groups, eps, silu=False, split=False):
         _reject(f"groupnorm_nhwc_f32: unsupported C = {C}, groups = {groups}")
     out = (torch.empty((N, 3 * C, H, W), dtype=torch.float16, device=x.device, memory_format=cl) if split
            else torch.empty_like(x, memory_format=cl))
-    nbytes = _hip.lib().ed_groupnorm_nhwc_f32_workspace(N, C, H * W, groups)
+    nbytes = _hip.lib().ed_groupnorm_nhwc_f32_workspace(N, C, H * W, groups) * (1 if wx is None and wy is None else 3)   # (+ double partials)
     ws = torch.empty(max(4, nbytes // 4), dtype=torch.float32, device=x.device)
-    TIMER.note_work("ed_groupnorm_nhwc_f32", nbytes=x.numel() * (4.0 + 4.0 + (6.0 if split else 4.0)))
-    _call("ed_groupnorm_nhwc_f32", x.data_ptr(), _dev(gamma, torch.float32, "gamma"), _dev(beta, torch.float32, "beta"), out.data_ptr(),
-          _dev(ws, torch.float32, "workspace"), N, C, H * W, groups, float(eps), int(silu), int(split), _stream_of(x))
+    traffic = x.numel() * (4.0 + 4.0 + (6.0 if split else 4.0))
+    head = (x.data_ptr(), _dev(gamma, torch.float32, "gamma"), _dev(beta, torch.float32, "beta"), out.data_ptr(),
+            _dev(ws, torch.float32, "workspace"))
+    if wx is None and wy is None:
+        TIMER.note_work("ed_groupnorm_nhwc_f32", nbytes=traffic)
+        _call("ed_groupnorm_nhwc_f32", *head, N, C, H * W, groups, float(eps), int(silu), int(split), _stream_of(x))
+    else:
+        px, py = _pixel_weights("groupnorm_nhwc_f32", wx, wy, H, W)
+        TIMER.note_work("ed_groupnorm_nhwc_f32_weighted", nbytes=traffic)
+        _call("ed_groupnorm_nhwc_f32_weighted", *head, N, C, H, W, groups, float(eps), int(silu), int(split), px, py, _stream_of(x))
     return out
 
 
@@ -1148,34 +1170,43 @@ def conv3x3_f32out_s2(a, w, bias=None, out_scale=1.0, act_absmax=None):
     return out
 
 
-def softmax_rows_(x, scale=1.0):
-    """x fp32 [..., cols] contiguous -> softmax(scale * x) over the last dim, IN PLACE (ed_softmax_rows)."""
+def softmax_rows_(x, scale=1.0, bias=None):
+    """x fp32 [..., cols] contiguous -> softmax(scale * x [+ bias]) over the last dim, IN PLACE (ed_softmax_rows; with the optional
+    fp32 ``bias`` [cols], one value per column, ed_softmax_rows_bias)."""
     cols = x.shape[-1]
     if cols % 4 and x.numel() != cols:
         _reject("softmax_rows_: cols must be a multiple of 4")
-    TIMER.note_work("ed_softmax_rows", nbytes=3.0 * x.numel() * 4)
-    _call("ed_softmax_rows", _dev(x, torch.float32, "x"), x.numel() // cols, cols, float(scale), _stream())
+    if bias is None:
+        TIMER.note_work("ed_softmax_rows", nbytes=3.0 * x.numel() * 4)
+        _call("ed_softmax_rows", _dev(x, torch.float32, "x"), x.numel() // cols, cols, float(scale), _stream())
+        return x
+    if tuple(bias.shape) != (cols,):
+        _reject(f"softmax_rows_: bias must have shape ({cols},), got {tuple(bias.shape)}")
+    TIMER.note_work("ed_softmax_rows_bias", nbytes=3.0 * x.numel() * 4)
+    _call("ed_softmax_rows_bias", _dev(x, torch.float32, "x"), x.numel() // cols, cols, float(scale), _dev(bias, torch.float32, "bias"),
+          _stream())
     return x
 
 
 VAE_ATTENTION_CHUNK_BYTES = 1 << 30  # score-matrix bytes materialised at a time by vae_attention (a few thousand rows keep the GEMMs efficient)
 
 
-def vae_attention(q, k, v):
-    """softmax(q k^T / sqrt(C)) v for the VAE's single-head attention, fp32 [B, N, C]: two library fp32 GEMMs around
+def vae_attention(q, k, v, key_bias=None):
+    """softmax(q k^T / sqrt(C) [+ key_bias]) v for the VAE's single-head attention, fp32 [B, N, C]: two library fp32 GEMMs around
     ed_softmax_rows, over chunks of query rows so that the [rows, N] score block stays under VAE_ATTENTION_CHUNK_BYTES
-    (N = 32768 tokens for the 1024x2048 decode: 4.3 GB of scores per sample).  Replaces SDPA / AOTriton."""
+    (N = 32768 tokens for the 1024x2048 decode: 4.3 GB of scores per sample).  Replaces SDPA / AOTriton.  ``key_bias`` fp32 [N]:
+    the log multiplicity of every key (the narrowed constant-image encode), added to each chunk's scores by ed_softmax_rows_bias."""
     B, N, C = q.shape
     scale = C ** -0.5
     # rows per chunk: the [B, rows, N] fp32 score block stays under the cap for any B (at least 64 rows)
     rows = max(64, min(N, VAE_ATTENTION_CHUNK_BYTES // (4 * N * B) // 64 * 64)) if N > 256 else N
     kt = k.transpose(1, 2)
     if rows >= N:
-        return torch.bmm(softmax_rows_(torch.bmm(q, kt), scale), v)
+        return torch.bmm(softmax_rows_(torch.bmm(q, kt), scale, key_bias), v)
     out = torch.empty_like(q)
     for a in range(0, N, rows):
         s = torch.bmm(q[:, a:a + rows], kt)                      # [B, rows, N]
-        out[:, a:a + rows] = torch.bmm(softmax_rows_(s, scale), v)
+        out[:, a:a + rows] = torch.bmm(softmax_rows_(s, scale, key_bias), v)
     return out
 
 

@@ -703,6 +703,24 @@ class ElasticDiffusion(nn.Module):
         s = self.vae_scale_factor
         return max(1, min(T, STRIP_CHUNK, (16 << 20) // max(1, 3 * Hs * s * Ws * s * 4)))
 
+    def _strip_group(self, Hs, Ws, chunk, n_units):
+        """Units (of ``chunk`` timesteps) per VAE call when the strips are encoded narrowed (models.VAE_NARROW_CONSTANT), else 0.  A narrowed
+        call is several times smaller than the full one, and a single unit would leave the convolutions of the last level with a
+        fraction of a round of tiles; so a rank puts as many of its units into one call as fit _strip_chunk's pixel budget counted in
+        NARROWED pixels, spread evenly over its calls.  The figure depends on the pool and the rank count alone, so every call of a
+        rank count has one batch (the last call repeats a unit) and MIOpen sees one shape per rank count."""
+        plan = getattr(self.vae, "constant_plan", None)
+        if plan is None or not hasattr(self.vae, "encode_constant"):
+            return 0
+        s = self.vae_scale_factor
+        py, px = plan(Hs * s, Ws * s)
+        if py is None and px is None:
+            return 0
+        Hn, Wn = (Hs if py is None else py.keep), (Ws if px is None else px.keep)
+        fit = max(1, (16 << 20) // max(1, chunk * 3 * Hn * s * Wn * s * 4))
+        per_rank = -(-n_units // (self.sharder.world_size if self.sharder.exchange else 1))
+        return -(-per_rank // -(-per_rank // fit))
+
     def strip_pools(self, pad, T):
         """-> {(Hs, Ws, chunk): [strip indices]}: the strips of one PadPlan whose encodes share a call shape.  Each pool is
         ONE sharded unit list, i.e. one ``sharder.run`` (one exchange when sharded) per pool and image."""
@@ -758,9 +776,24 @@ class ElasticDiffusion(nn.Module):
             sel_all = torch.cat([t_idx + p * T for p in range(len(members))])          # [P * n_units, chunk] draw rows
             t_all = t_idx.repeat(len(members), 1)                                      # ... and their timestep indices
 
+            group = self._strip_group(Hs, Ws, chunk, sel_all.shape[0])
+
             def encode(sel_rows, _a, _b, _c, t_rows):
                 """Noised strips of the units ``sel_rows`` [n, chunk] (units are sharded over ranks like model rows)."""
                 outs = []
+                if group:
+                    # narrowed encodes, ``group`` units per VAE call (the last call is filled up with its final unit); the posterior and
+                    # the forward noise are applied to the expanded moments, per element as below
+                    n = sel_rows.shape[0]
+                    for a in range(0, n, group):
+                        pick = torch.arange(a, a + group, device=sel_rows.device).clamp_(max=n - 1)
+                        sel, tt = sel_rows[pick].reshape(-1), t_rows[pick].reshape(-1)
+                        dist = self.vae.encode_constant(colour[sel].to(vae_dtype), Hs * s, Ws * s).latent_dist
+                        enc = (dist.mean.float() + dist.std.float() * post[sel]) * sf
+                        cf = coef[tt]
+                        out = cf[:, 0].view(-1, 1, 1, 1) * enc + cf[:, 1].view(-1, 1, 1, 1) * fwd[sel]
+                        outs.append(out.view(group, chunk, *out.shape[1:])[:min(group, n - a)])
+                    return torch.cat(outs)
                 for sel, tt in zip(sel_rows, t_rows):
                     img = colour[sel][:, :, None, None].expand(chunk, 3, Hs * s, Ws * s).contiguous().to(vae_dtype)
                     dist = self.vae.encode(img).latent_dist

@@ -813,6 +813,28 @@ int ed_score_pca_fit(const float* score, int B, int C, int H, int W, int normali
 int ed_score_pca_map(const float* score, int B, int C, int H, int W, const float* norm, uint8_t* out, void* workspace,
                      void* stream);
 
+/*
+ * ---- weighted statistics for the narrowed constant-image VAE encode (additions, no signature change, so
+ * still ABI v13).  The encode of a constant-colour image varies only in a border; the encoder is run on an image with fewer rows /
+ * columns in which ONE row / column per level stands for a run of identical ones.  What is global in the encoder -- the GroupNorm
+ * statistics and the mid-block attention's softmax -- must count that row / column with its multiplicity:
+ *
+ * ed_groupnorm_nhwc_f32_weighted / ed_groupnorm_f32_weighted -- ed_groupnorm_nhwc_f32 / ed_groupnorm_f32 on an [N, C, H, W] activation
+ *   (HW = H * W) whose pixel (y, x) counts wy[y] * wx[x] times in the mean and the variance: both shifted sums carry the weight and
+ *   the element count is (C / G) sum(wy) sum(wx).  wx f32 [W] or NULL, wy f32 [H] or NULL (NULL = all ones), 4-byte aligned.  The
+ *   apply pass and every other argument are the unweighted entry point's; the workspace is THREE TIMES its ed_*_workspace bytes,
+ *   16-byte aligned: every pixel is summed once by the unweighted code and the excess (w - 1) of the heavy pixels in double, in
+ *   double partials behind the fp32 ones (a few heavy terms can dominate a sum; their rounding would not average out).  All-ones
+ *   weights give the unweighted entry point's bits, and wx = wy = NULL is that entry point.
+ * ed_softmax_rows_bias -- x[r, :] = softmax(scale * x[r, :] + bias) in place: ed_softmax_rows with one fp32 bias per column
+ *   (16-byte aligned), the log multiplicity of the key.  bias = NULL is ed_softmax_rows; a zero bias gives the same bits.
+ */
+int ed_groupnorm_nhwc_f32_weighted(const void* x, const void* gamma, const void* beta, void* out, float* workspace, int N, int C, int H,
+                                   int W, int G, float eps, int act_silu, int split16, const float* wx, const float* wy, void* stream);
+int ed_groupnorm_f32_weighted(const void* x, const void* gamma, const void* beta, void* out, float* workspace, int N, int C, int H,
+                              int W, int G, float eps, int act_silu, const float* wx, const float* wy, void* stream);
+int ed_softmax_rows_bias(void* x, int64_t rows, int64_t cols, float scale, const float* bias, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
