@@ -32,6 +32,9 @@ and a mask, and conditions on the mask and the blanked picture instead of pastin
 ``--ip_adapter_embeds FILE`` (``.pt`` / ``.npy``).
 ``--score_pca true`` saves the reference's diagnostic pictures (pca_diffusion_scores.py) every ``--log_freq``
 steps under the script's own names, ``pca_cls_dir_{i}.png`` / ``pca_uncond_{i}.png``.
+``--region_prompt TEXT`` with ``--region_mask FILE|x0,y0,x1,y1[:WEIGHT]`` (both repeatable, paired in order) are regional prompts
+(DESIGN.md section 28): ``--prompt`` stays the base prompt that fills what the regions leave uncovered, a mask is a picture at
+H x W (white = the region) or a box in pixels, WEIGHT > 0 (default 1) decides overlaps, and ``--region_blur R`` feathers the masks.
 """
 import argparse
 import os
@@ -123,7 +126,50 @@ def build_parser():
                     "CLIPVisionModelWithProjection, for --ip_adapter_image")
     ap.add_argument("--score_pca", type=_bool, default=False, help="true: every --log_freq steps, save the PCA maps of the class "
                     "direction and of the local unconditional score as pca_cls_dir_{i}.png / pca_uncond_{i}.png")
+    ap.add_argument("--region_prompt", action="append", default=[], metavar="TEXT", help="prompt of one region (repeatable, up to 7); "
+                    "pairs with the --region_mask at the same position, --prompt stays the base prompt")
+    ap.add_argument("--region_mask", action="append", default=[], metavar="FILE|x0,y0,x1,y1[:WEIGHT]", help="where a region "
+                    "applies: a mask picture at H x W (white = the region) or a box in pixels; WEIGHT > 0 (default 1) scales the "
+                    "region where regions overlap")
+    ap.add_argument("--region_blur", type=float, default=0.0, help="feather the region masks: Gaussian radius in pixels at H x W; "
+                    "0 = off")
     return ap
+
+
+def _region_mask_arg(text):
+    """``FILE|x0,y0,x1,y1[:WEIGHT]`` -> (a path or a 4-tuple of ints, weight)"""
+    spec, weight = _lora_arg(text)
+    parts = spec.split(",")
+    if len(parts) == 4:
+        try:
+            return tuple(int(v) for v in parts), weight
+        except ValueError:
+            pass
+    return spec, weight
+
+
+def parse_regions(opt, open_image=None):
+    """The ``regions`` list of ``generate_image`` from --region_prompt / --region_mask, or None without them; SystemExit on unequal
+    counts or a mask file that does not exist.  ``open_image(path)`` -> the mask picture (default: Pillow, converted to "L")."""
+    if len(opt.region_prompt) != len(opt.region_mask):
+        raise SystemExit(f"--region_prompt and --region_mask pair in order: got {len(opt.region_prompt)} prompts and "
+                         f"{len(opt.region_mask)} masks")
+    if not opt.region_prompt:
+        if opt.region_blur:
+            raise SystemExit("--region_blur needs --region_prompt / --region_mask")
+        return None
+    if open_image is None:
+        from PIL import Image
+        open_image = lambda path: Image.open(path).convert("L")  # noqa: E731
+    regions = []
+    for prompt, text in zip(opt.region_prompt, opt.region_mask):
+        mask, weight = _region_mask_arg(text)
+        if isinstance(mask, str):
+            if not os.path.isfile(mask):
+                raise SystemExit(f"--region_mask: no such file {mask!r} (a box is x0,y0,x1,y1)")
+            mask = open_image(mask)
+        regions.append((prompt, mask, weight))
+    return regions
 
 
 def _load_embeds(path):
@@ -164,7 +210,12 @@ def main(argv=None):
         raise SystemExit(f"--guidance_rescale must be in [0, 1], got {opt.guidance_rescale}")
     if opt.max_prompt_chunks < 1:
         raise SystemExit(f"--max_prompt_chunks must be >= 1, got {opt.max_prompt_chunks}")
-    from .pipeline import check_img2img_arguments
+    from .pipeline import check_img2img_arguments, check_region_arguments
+    regions = parse_regions(opt)
+    try:
+        check_region_arguments(regions, opt.H, opt.W, 8, opt.region_blur, 9 if opt.sd_version.endswith("-inpaint") else 4)
+    except ValueError as e:
+        raise SystemExit(f"--region_prompt / --region_mask / --region_blur: {e}")
     loras = [_lora_arg(v) for v in opt.lora]
     for path, _ in loras:
         if not os.path.isfile(path):
@@ -261,6 +312,8 @@ def main(argv=None):
         extra.update(mask_blur=opt.mask_blur, mask_mode=opt.mask_mode, composite=opt.composite)
     if opt.score_pca:
         extra["score_pca"] = True
+    if regions:
+        extra.update(regions=regions, region_blur=opt.region_blur)
     sd.seed_everything(opt.seed)
     t0 = time.time()
     imgs, image_log = sd.generate_image(prompts=[opt.prompt] * opt.num_sampled, negative_prompts=opt.negative,

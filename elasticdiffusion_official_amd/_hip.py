@@ -116,6 +116,15 @@ SIGNATURES = {
     "ed_phase_epilogue_ms": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                              _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f,
                              _f, _f, _f, _f, _i, _vp, _vp, _f, _f, _vp, _vp],
+    "ed_region_weights": [_vp, _vp, _i, _i64, _vp, _vp],
+    "ed_assemble_rows_n": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
+                           _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp],
+    "ed_region_blend": [_vp, _vp, _vp, _i, _i, _i64, _vp],
+    "ed_phase_epilogue_rg": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                             _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f,
+                             _f, _f, _f, _f, _i, _vp, _vp, _f, _f, _vp, _i, _vp, _i, _vp],
+    "ed_phase_moments_rg": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i,
+                            _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp],
     "ed_score_pca_workspace": [_i, _i64],
     "ed_score_pca_fit": [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "ed_score_pca_map": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp],

@@ -230,7 +230,8 @@ __device__ __forceinline__ void pick_assemble_body(int64_t t, const float* __res
                 const int32_t* __restrict__ src_row, const int32_t* __restrict__ src_col,
                 const float* __restrict__ frame, void* __restrict__ out, float* __restrict__ low,
                 int K, int B, int C, int H, int W, int h, int w, int PH, int PW, int off_y, int off_x,
-                const float* __restrict__ extra = nullptr, int E = 0, const float* __restrict__ pad_value = nullptr) {
+                const float* __restrict__ extra = nullptr, int E = 0, const float* __restrict__ pad_value = nullptr,
+                const int copies = 2) {  // rows written per step and sample: uncond + cond, or uncond + P cond (ed_assemble_rows_n)
   const int CT = X ? C + E : C;  // X: see gather_windows_body; `low` keeps the C latent channels
   int64_t n = (int64_t)K * B * CT * PH * PW;
   if (t >= n) return;
@@ -262,10 +263,7 @@ __device__ __forceinline__ void pick_assemble_body(int64_t t, const float* __res
   }
   int64_t plane = (int64_t)PH * PW;
   int64_t e = ((int64_t)c * PH + y) * PW + x;
-  int64_t row_u = ((int64_t)k * 2 + 0) * B + b;
-  int64_t row_c = ((int64_t)k * 2 + 1) * B + b;
-  st<Tag>(out, row_u * CT * plane + e, val);
-  st<Tag>(out, row_c * CT * plane + e, val);
+  for (int q = 0; q < copies; ++q) st<Tag>(out, (((int64_t)k * copies + q) * B + b) * CT * plane + e, val);
 }
 
 template <typename Tag>
@@ -283,7 +281,8 @@ __device__ __forceinline__ void pick_assemble_x4_body(int64_t t, const float* __
                    const int32_t* __restrict__ src_row, const int32_t* __restrict__ src_col,
                    const float* __restrict__ frame, void* __restrict__ out, float* __restrict__ low,
                    int K, int B, int C, int H, int W, int h, int w, int PH, int PW, int off_y, int off_x,
-                   const float* __restrict__ extra = nullptr, int E = 0, const float* __restrict__ pad_value = nullptr) {
+                   const float* __restrict__ extra = nullptr, int E = 0, const float* __restrict__ pad_value = nullptr,
+                   const int copies = 2) {
   const int CT = X ? C + E : C;
   int PW4 = PW >> 2;
   int64_t n = (int64_t)K * B * CT * PH * PW4;
@@ -323,10 +322,8 @@ __device__ __forceinline__ void pick_assemble_x4_body(int64_t t, const float* __
   }
   int64_t plane_sz = (int64_t)PH * PW;
   int64_t e0 = ((int64_t)c * PH + y) * PW + x;
-  int64_t row_u = ((int64_t)k * 2 + 0) * B + b;
-  int64_t row_c = ((int64_t)k * 2 + 1) * B + b;
-  st4<Tag>(out, row_u * CT * plane_sz + e0, val[0], val[1], val[2], val[3]);
-  st4<Tag>(out, row_c * CT * plane_sz + e0, val[0], val[1], val[2], val[3]);
+  for (int q = 0; q < copies; ++q)
+    st4<Tag>(out, (((int64_t)k * copies + q) * B + b) * CT * plane_sz + e0, val[0], val[1], val[2], val[3]);
 }
 
 template <typename Tag>
@@ -612,6 +609,34 @@ k_assemble_rows_x(const AssembleArgsX a) {
   }
 }
 
+// ---- ed_assemble_rows_n: ed_assemble_rows_x with `copies` rows per resampling step and sample (regional prompts, section 28) -----
+// The picked vector is gathered once and stored `copies` times; E = 0 (extra NULL) is the 4-channel case.
+struct AssembleArgsN : AssembleArgsX {
+  int copies;
+};
+
+template <typename Tag, bool PX4, bool GX4>
+__global__ void __launch_bounds__(ED_BLOCK)
+k_assemble_rows_n(const AssembleArgsN a) {
+  if ((int)blockIdx.x < a.pick_blocks) {
+    int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
+    if (PX4)
+      pick_assemble_x4_body<Tag, true>(t, a.latent, a.idx, a.src_row, a.src_col, a.gframe, a.g_out, a.low, a.K, a.B, a.C, a.H,
+                                       a.W, a.h, a.w, a.gPH, a.gPW, a.g_off_y, a.g_off_x, a.extra, a.E, a.pad_value, a.copies);
+    else
+      pick_assemble_body<Tag, true>(t, a.latent, a.idx, a.src_row, a.src_col, a.gframe, a.g_out, a.low, a.K, a.B, a.C, a.H, a.W,
+                                    a.h, a.w, a.gPH, a.gPW, a.g_off_y, a.g_off_x, a.extra, a.E, a.pad_value, a.copies);
+  } else {
+    int64_t t = (int64_t)((int)blockIdx.x - a.pick_blocks) * ED_BLOCK + threadIdx.x;
+    if (GX4)
+      gather_windows_x4_body<Tag, true>(t, a.latent, a.v_out, a.B, a.C, a.H, a.W, a.win_y0, a.win_x0, a.V, a.Sh, a.Sw, a.vPH,
+                                        a.vPW, a.v_off_y, a.v_off_x, a.vframe, 1.0f, 0, a.extra, a.E, a.pad_value);
+    else
+      gather_windows_body<Tag, true>(t, a.latent, a.v_out, a.B, a.C, a.H, a.W, a.win_y0, a.win_x0, a.V, a.Sh, a.Sw, a.vPH, a.vPW,
+                                     a.v_off_y, a.v_off_x, a.vframe, 1.0f, 0, a.extra, a.E, a.pad_value);
+  }
+}
+
 // ---- ed_phase_epilogue: unpad + fill + scatter + CFG/DDIM (+ RRG) in ONE launch ---------------------
 // Everything downstream of the model call is a per-output-pixel gather: which resampling step covers the pixel (stamp
 // table) -> cond - uncond of that step's rows; the first non-zero covering view centre; the DDIM update; optionally the
@@ -880,6 +905,228 @@ k_moments_finalise(const double* __restrict__ partials, int B, int nblk_full, in
 inline int moments_blocks(int64_t n) {
   int64_t g = (n + (int64_t)ED_BLOCK * ED_MOM_PER_THREAD - 1) / ((int64_t)ED_BLOCK * ED_MOM_PER_THREAD);
   return (int)(g < 1 ? 1 : (g > ED_MOM_MAX_BLOCKS ? ED_MOM_MAX_BLOCKS : g));
+}
+
+// ---- regional prompts ------------------------------------------------------------------
+// A step of the model batch holds 1 + P rows per sample, uncond first and then the P cond rows (base prompt, regions); the class
+// direction of a pixel is the weighted sum of the P directions cond_p - uncond with the per-pixel weights region_w [P,H,W] of
+// k_region_weights.  A term whose weight is 0 is skipped -- its row is not read -- and the first term that is not starts the sum, so
+// one-hot weights give the bits of that region's own direction.  Everything downstream is k_phase_epilogue's.  The argument block
+// is a type of its own (as EpilogueArgsMS): the blocks of the non-regional instantiations keep their sizes.
+#define ED_MAX_REGION_ROWS 8
+
+struct EpilogueArgsRG : EpilogueArgsMS {
+  const float* region_w;  // [P,H,W]
+  int P;
+};
+
+template <typename Tag>
+__device__ __forceinline__ float direction_rg_at(const EpilogueArgsRG& a, int b, int c, int Y, int X) {
+  int k = last_covering_step(a.stamp, a.inv_row, a.inv_col, a.K, a.w, Y, X);
+  int64_t plane = (int64_t)a.gPH * a.gPW, wplane = (int64_t)a.H * a.W;
+  int64_t e = ((int64_t)c * a.gPH + (a.up_row[Y] + a.g_off_y)) * a.gPW + (a.up_col[X] + a.g_off_x);
+  const int64_t row0 = (int64_t)k * (1 + a.P);
+  const float* wp = a.region_w + (int64_t)Y * a.W + X;
+  float u = 0.0f, d = 0.0f;
+  bool any = false;
+  for (int p = 0; p < a.P; ++p) {
+    float wv = wp[p * wplane];
+    if (wv == 0.0f) continue;
+    if (!any) u = ld<Tag>(a.g_out, ((row0 + 0) * a.B + b) * a.C * plane + e);
+    float cd = ld<Tag>(a.g_out, ((row0 + 1 + p) * a.B + b) * a.C * plane + e);
+    float term = __fmul_rn(wv, __fsub_rn(cd, u));
+    d = any ? __fadd_rn(d, term) : term;
+    any = true;
+  }
+  return d;
+}
+
+template <typename Tag>
+__device__ __forceinline__ float uncond_last_rg_at(const EpilogueArgsRG& a, int b, int c, int i, int j) {
+  int64_t plane = (int64_t)a.gPH * a.gPW;
+  int64_t e = ((int64_t)c * a.gPH + (i + a.g_off_y)) * a.gPW + (j + a.g_off_x);
+  return ld<Tag>(a.g_out, (((int64_t)(a.K - 1) * (1 + a.P) + 0) * a.B + b) * a.C * plane + e);
+}
+
+// k_phase_epilogue with the regional direction: same thread mapping, same operation order after `d`
+template <typename Tag, bool VP, bool GR, int ST>
+__global__ void __launch_bounds__(ED_BLOCK)
+k_phase_epilogue_rg(const EpilogueArgsRG a) {
+  const int64_t nfull = (int64_t)a.B * a.C * a.H * a.W;
+  const int64_t nlow = (int64_t)a.B * a.C * a.h * a.w;
+  int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
+  if (t >= nfull + nlow) return;
+  if (t >= nfull) {
+    int64_t u = t - nfull;
+    int j = (int)(u % a.w);
+    int64_t r = u / a.w;
+    int i = (int)(r % a.h);
+    r /= a.h;
+    int c = (int)(r % a.C);
+    int b = (int)(r / a.C);
+    if (a.low_dir) a.low_dir[u] = direction_rg_at<Tag>(a, b, c, a.down_row[i], a.down_col[j]);
+    if (a.uncond_last) a.uncond_last[u] = uncond_last_rg_at<Tag>(a, b, c, i, j);
+    return;
+  }
+  int X = (int)(t % a.W);
+  int64_t r = t / a.W;
+  int Y = (int)(r % a.H);
+  r /= a.H;
+  int c = (int)(r % a.C);
+  int b = (int)(r / a.C);
+  float loc = local_at<Tag>(a, b, c, Y, X);
+  float d = direction_rg_at<Tag>(a, b, c, Y, X);
+  float pv, z0, x0h = 0.0f;
+  if constexpr (ST == ST_MS2) x0h = a.x0_hist[t];
+  ddim_one<VP, GR, ST>(loc, d, a.x[t], a.g, a.sb, a.sa, a.sp, a.sd, pv, z0, GR ? a.ratio[b] : 0.0f, a.gr, a.omgr, x0h, a.hb, a.r_inv);
+  a.prev[t] = pv;
+  a.x0[t] = z0;
+  if (a.direction) a.direction[t] = d;
+  if (a.local) a.local[t] = loc;
+  if (a.x_next) {
+    int i = a.up_row[Y], j = a.up_col[X];
+    float lu = uncond_last_rg_at<Tag>(a, b, c, i, j);
+    float ldir = direction_rg_at<Tag>(a, b, c, a.down_row[i], a.down_col[j]);
+    float m = rescaled<GR>(__fadd_rn(lu, __fmul_rn(a.g, ldir)), GR ? a.ratio_low[b] : 0.0f, a.gr, a.omgr);
+    float up = pred_x0<VP>(m, a.low_latent[(((int64_t)b * a.C + c) * a.h + i) * a.w + j], a.sb, a.sa);
+    float grad = __fmul_rn(__fmul_rn(a.rrg_norm, __fsub_rn(z0, up)), a.rrg_weight);
+    a.x_next[t] = __fadd_rn(pv, -grad);
+  }
+}
+
+// k_phase_moments over the regional direction
+template <typename Tag>
+__global__ void __launch_bounds__(ED_BLOCK)
+k_phase_moments_rg(const EpilogueArgsRG a, int nblk_full, int nblk_low, double* __restrict__ partials) {
+  PairAcc acc;
+  const int full_blocks = a.B * nblk_full;
+  if ((int)blockIdx.x < full_blocks) {
+    const int b = blockIdx.x / nblk_full, k = blockIdx.x % nblk_full;
+    const int64_t n = (int64_t)a.C * a.H * a.W;
+    for (int64_t i = (int64_t)k * ED_BLOCK + threadIdx.x; i < n; i += (int64_t)nblk_full * ED_BLOCK) {
+      int X = (int)(i % a.W);
+      int64_t r = i / a.W;
+      int Y = (int)(r % a.H), c = (int)(r / a.H);
+      acc.add(local_at<Tag>(a, b, c, Y, X), direction_rg_at<Tag>(a, b, c, Y, X), a.g);
+    }
+  } else {
+    const int q = (int)blockIdx.x - full_blocks;
+    const int b = q / nblk_low, k = q % nblk_low;
+    const int64_t n = (int64_t)a.C * a.h * a.w;
+    for (int64_t i = (int64_t)k * ED_BLOCK + threadIdx.x; i < n; i += (int64_t)nblk_low * ED_BLOCK) {
+      int j = (int)(i % a.w);
+      int64_t r = i / a.w;
+      int ii = (int)(r % a.h), c = (int)(r / a.h);
+      acc.add(uncond_last_rg_at<Tag>(a, b, c, ii, j), direction_rg_at<Tag>(a, b, c, a.down_row[ii], a.down_col[j]), a.g);
+    }
+  }
+  moments_block_store(acc, partials + (int64_t)blockIdx.x * 6);
+}
+
+// ed_region_weights: n masks u8 [n,HW] and their weights -> w f32 [n + 1,HW], plane 0 the base prompt's.  r_p = weight_p * (m_p / 255),
+// s = r_1 + .. + r_n in order, r_0 = max(0, 1 - s), tot = r_0 + s (>= 1 up to rounding, never 0), w_p = r_p / tot.
+struct RegionWeightArgs {
+  float weight[ED_MAX_REGION_ROWS - 1];
+};
+
+__device__ __forceinline__ void region_weights_one(const uint32_t* m, const RegionWeightArgs& rw, int n, float* out) {
+  float r[ED_MAX_REGION_ROWS - 1];
+  float s = 0.0f;
+#pragma unroll
+  for (int p = 0; p < ED_MAX_REGION_ROWS - 1; ++p) {
+    if (p < n) {
+      r[p] = __fmul_rn(rw.weight[p], __fdiv_rn((float)m[p], 255.0f));
+      s = p ? __fadd_rn(s, r[p]) : r[p];
+    }
+  }
+  float r0 = fmaxf(0.0f, __fsub_rn(1.0f, s));
+  float tot = __fadd_rn(r0, s);
+  out[0] = __fdiv_rn(r0, tot);
+#pragma unroll
+  for (int p = 0; p < ED_MAX_REGION_ROWS - 1; ++p)
+    if (p < n) out[1 + p] = __fdiv_rn(r[p], tot);
+}
+
+__global__ void __launch_bounds__(ED_BLOCK)
+k_region_weights(const uint8_t* __restrict__ masks, const RegionWeightArgs rw, int n, int64_t HW, float* __restrict__ w) {
+  int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
+  if (t >= HW) return;
+  uint32_t m[ED_MAX_REGION_ROWS - 1];
+  float out[ED_MAX_REGION_ROWS];
+#pragma unroll
+  for (int p = 0; p < ED_MAX_REGION_ROWS - 1; ++p) m[p] = p < n ? masks[p * HW + t] : 0u;
+  region_weights_one(m, rw, n, out);
+#pragma unroll
+  for (int p = 0; p < ED_MAX_REGION_ROWS; ++p)
+    if (p <= n) w[p * HW + t] = out[p];
+}
+
+// 4 consecutive pixels per thread: one 4-byte load per mask, one 16-byte store per plane; requires HW % 4 == 0
+__global__ void __launch_bounds__(ED_BLOCK)
+k_region_weights_x4(const uint32_t* __restrict__ masks, const RegionWeightArgs rw, int n, int64_t HW4, float4* __restrict__ w) {
+  int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
+  if (t >= HW4) return;
+  uint32_t pk[ED_MAX_REGION_ROWS - 1];
+#pragma unroll
+  for (int p = 0; p < ED_MAX_REGION_ROWS - 1; ++p) pk[p] = p < n ? masks[p * HW4 + t] : 0u;
+  float out[4][ED_MAX_REGION_ROWS];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    uint32_t m[ED_MAX_REGION_ROWS - 1];
+#pragma unroll
+    for (int p = 0; p < ED_MAX_REGION_ROWS - 1; ++p) m[p] = (pk[p] >> (8 * e)) & 0xffu;
+    region_weights_one(m, rw, n, out[e]);
+  }
+#pragma unroll
+  for (int p = 0; p < ED_MAX_REGION_ROWS; ++p)
+    if (p <= n) w[p * HW4 + t] = make_float4(out[0][p], out[1][p], out[2][p], out[3][p]);
+}
+
+// ed_region_blend (the un-fused path): out[bc, i] = sum_p w[p, i] * dirs[p, bc, i] with direction_rg_at's skip rule and order
+__device__ __forceinline__ float region_blend_one(const float* __restrict__ dirs, const float* __restrict__ w, int P, int64_t dstride,
+                                                   int64_t wstride, int64_t di, int64_t wi) {
+  float d = 0.0f;
+  bool any = false;
+  for (int p = 0; p < P; ++p) {
+    float wv = w[p * wstride + wi];
+    if (wv == 0.0f) continue;
+    float term = __fmul_rn(wv, dirs[p * dstride + di]);
+    d = any ? __fadd_rn(d, term) : term;
+    any = true;
+  }
+  return d;
+}
+
+__global__ void __launch_bounds__(ED_BLOCK)
+k_region_blend(const float* __restrict__ dirs, const float* __restrict__ w, float* __restrict__ out, int P, int64_t n, int64_t HW) {
+  int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
+  if (t >= n) return;
+  out[t] = region_blend_one(dirs, w, P, n, HW, t, t % HW);
+}
+
+// 4 consecutive elements per thread; requires HW % 4 == 0 (a group lies in one plane) and 16-byte aligned buffers
+__global__ void __launch_bounds__(ED_BLOCK)
+k_region_blend_v4(const float4* __restrict__ dirs, const float4* __restrict__ w, float4* __restrict__ out, int P, int64_t n4,
+                  int64_t HW4) {
+  int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
+  if (t >= n4) return;
+  int64_t wi = t % HW4;
+  float d[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  bool any[4] = {false, false, false, false};
+  for (int p = 0; p < P; ++p) {
+    float4 wv4 = w[p * HW4 + wi];
+    if (wv4.x == 0.0f && wv4.y == 0.0f && wv4.z == 0.0f && wv4.w == 0.0f) continue;
+    float4 dv4 = dirs[p * n4 + t];
+    float wv[4] = {wv4.x, wv4.y, wv4.z, wv4.w}, dv[4] = {dv4.x, dv4.y, dv4.z, dv4.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (wv[e] == 0.0f) continue;
+      float term = __fmul_rn(wv[e], dv[e]);
+      d[e] = any[e] ? __fadd_rn(d[e], term) : term;
+      any[e] = true;
+    }
+  }
+  out[t] = make_float4(d[0], d[1], d[2], d[3]);
 }
 
 // ---- ed_undo_step ----------------------------------------------------------------------------------
@@ -1363,6 +1610,47 @@ int ed_assemble_rows_x(const float* latent, int B, int C, int H, int W, const ui
     default: return (int)hipErrorInvalidValue;
   }
 #undef ED_ASM_X
+  return done();
+}
+
+int ed_assemble_rows_n(const float* latent, int B, int C, int H, int W, const uint8_t* idx, const int32_t* src_row,
+                       const int32_t* src_col, const float* gframe, void* g_rows, float* low, int K, int h, int w, int gPH,
+                       int gPW, int g_off_y, int g_off_x, const int32_t* win_y0, const int32_t* win_x0,
+                       const float* vframe, void* v_rows, int V, int Sh, int Sw, int vPH, int vPW, int v_off_y, int v_off_x,
+                       int dtype, const float* extra, int E, const float* pad_value, int copies, void* stream) {
+  if (copies < 2 || copies > 1 + ED_MAX_REGION_ROWS || E < 0 || (E > 0 && (!extra || !pad_value)) || (E == 0 && extra) || !latent ||
+      C < 1 || B < 0 || K < 0 || V < 0 || H < 1 || W < 1 || h < 0 || w < 0 || Sh < 0 || Sw < 0 || g_off_y < 0 || g_off_x < 0 ||
+      g_off_y + h > gPH || g_off_x + w > gPW || v_off_y < 0 || v_off_x < 0 || v_off_y + Sh > vPH || v_off_x + Sw > vPW)
+    return (int)hipErrorInvalidValue;
+  int64_t n_g = (int64_t)K * B * (C + E) * gPH * gPW, n_v = (int64_t)V * B * (C + E) * vPH * vPW;
+  if (n_g + n_v == 0) return 0;
+  if ((n_g && (!g_rows || !idx || !src_row || !src_col)) || (n_v && (!v_rows || !win_y0 || !win_x0))) return (int)hipErrorInvalidValue;
+  bool px4 = (gPW & 3) == 0 && (w & 3) == 0 && (g_off_x & 3) == 0 && aligned16(g_rows) && aligned16(idx) &&
+             (!gframe || aligned16(gframe)) && (!low || aligned16(low));
+  bool gx4 = (vPW & 3) == 0 && (Sw & 3) == 0 && (v_off_x & 3) == 0 && aligned16(v_rows) && (!vframe || aligned16(vframe));
+  AssembleArgsN a;
+  a.latent = latent, a.B = B, a.C = C, a.H = H, a.W = W;
+  a.idx = idx, a.src_row = src_row, a.src_col = src_col, a.gframe = gframe, a.g_out = g_rows, a.low = low;
+  a.K = K, a.h = h, a.w = w, a.gPH = gPH, a.gPW = gPW, a.g_off_y = g_off_y, a.g_off_x = g_off_x;
+  a.win_y0 = win_y0, a.win_x0 = win_x0, a.vframe = vframe, a.v_out = v_rows;
+  a.V = V, a.Sh = Sh, a.Sw = Sw, a.vPH = vPH, a.vPW = vPW, a.v_off_y = v_off_y, a.v_off_x = v_off_x;
+  a.extra = extra, a.pad_value = pad_value, a.E = E, a.copies = copies;
+  a.pick_blocks = n_g ? grid_for(px4 ? n_g >> 2 : n_g) : 0;
+  int view_blocks = n_v ? grid_for(gx4 ? n_v >> 2 : n_v) : 0;
+  dim3 grid(a.pick_blocks + view_blocks), block(ED_BLOCK);
+  hipStream_t st_ = (hipStream_t)stream;
+#define ED_ASM_N(T)                                                              \
+  if (px4 && gx4) k_assemble_rows_n<T, true, true><<<grid, block, 0, st_>>>(a);  \
+  else if (px4) k_assemble_rows_n<T, true, false><<<grid, block, 0, st_>>>(a);   \
+  else if (gx4) k_assemble_rows_n<T, false, true><<<grid, block, 0, st_>>>(a);   \
+  else k_assemble_rows_n<T, false, false><<<grid, block, 0, st_>>>(a);
+  switch (dtype) {
+    case ED_F32: ED_ASM_N(F32) break;
+    case ED_F16: ED_ASM_N(F16) break;
+    case ED_BF16: ED_ASM_N(BF16) break;
+    default: return (int)hipErrorInvalidValue;
+  }
+#undef ED_ASM_N
   return done();
 }
 
@@ -1859,6 +2147,154 @@ int ed_inpaint_blend(const float* x, const uint8_t* mask, const float* z0, const
     if (clean) ED_LAUNCH(k_inpaint_blend_s<true>, n, x, mask, z0, noise, a, b, out, n, HW);
     else ED_LAUNCH(k_inpaint_blend_s<false>, n, x, mask, z0, noise, a, b, out, n, HW);
   }
+  return done();
+}
+
+// ---- regional prompts -------------------------------------------------------------------
+static inline bool ranges_overlap(const void* a, int64_t abytes, const void* b, int64_t bbytes) {
+  if (!a || !b || abytes <= 0 || bbytes <= 0) return false;
+  uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + (uintptr_t)bbytes && y < x + (uintptr_t)abytes;
+}
+
+static inline bool bad_region_rows(int P) { return P < 1 || P > ED_MAX_REGION_ROWS; }
+
+int ed_region_weights(const uint8_t* masks, const float* weights, int n, int64_t HW, float* region_w, void* stream) {
+  if (bad_region_rows(n + 1) || n < 1 || !masks || !weights || !region_w || HW < 0) return (int)hipErrorInvalidValue;
+  for (int p = 0; p < n; ++p)
+    if (!(weights[p] > 0.0f) || !(weights[p] <= 3.0e38f)) return (int)hipErrorInvalidValue;
+  if (ranges_overlap(masks, (int64_t)n * HW, region_w, (int64_t)(n + 1) * HW * 4)) return (int)hipErrorInvalidValue;
+  if (HW == 0) return 0;
+  RegionWeightArgs rw = {};
+  for (int p = 0; p < n; ++p) rw.weight[p] = weights[p];
+  if ((HW & 3) == 0 && (((uintptr_t)masks) & 3u) == 0 && aligned16(region_w))
+    ED_LAUNCH(k_region_weights_x4, HW >> 2, (const uint32_t*)masks, rw, n, HW >> 2, (float4*)region_w);
+  else
+    ED_LAUNCH(k_region_weights, HW, masks, rw, n, HW, region_w);
+  return done();
+}
+
+int ed_region_blend(const float* dirs, const float* region_w, float* out, int P, int planes, int64_t HW, void* stream) {
+  if (bad_region_rows(P) || !dirs || !region_w || !out || planes < 0 || HW < 0) return (int)hipErrorInvalidValue;
+  int64_t n = (int64_t)planes * HW;
+  if (ranges_overlap(region_w, (int64_t)P * HW * 4, out, n * 4) || ranges_overlap(dirs, (int64_t)P * n * 4, out, n * 4))
+    return (int)hipErrorInvalidValue;
+  if (n == 0) return 0;
+  if ((HW & 3) == 0 && aligned16(dirs) && aligned16(region_w) && aligned16(out))
+    ED_LAUNCH(k_region_blend_v4, n >> 2, (const float4*)dirs, (const float4*)region_w, (float4*)out, P, n >> 2, HW >> 2);
+  else
+    ED_LAUNCH(k_region_blend, n, dirs, region_w, out, P, n, HW);
+  return done();
+}
+
+// region_w must not share memory with anything the launch writes
+static bool region_w_overlaps_outputs(const float* region_w, int P, int B, int C, int H, int W, int h, int w, const float* const* full,
+                                      int n_full, const float* const* low, int n_low) {
+  int64_t wb = (int64_t)P * H * W * 4, fb = (int64_t)B * C * H * W * 4, lb = (int64_t)B * C * h * w * 4;
+  for (int i = 0; i < n_full; ++i)
+    if (ranges_overlap(region_w, wb, full[i], fb)) return true;
+  for (int i = 0; i < n_low; ++i)
+    if (ranges_overlap(region_w, wb, low[i], lb)) return true;
+  return false;
+}
+
+int ed_phase_epilogue_rg(const void* g_out, const void* v_out, int dtype, const float* x, const int8_t* stamp,
+                         const int32_t* inv_row, const int32_t* inv_col, const int32_t* up_row, const int32_t* up_col,
+                         const int32_t* down_row, const int32_t* down_col, const int32_t* row_blk, const int32_t* row_src,
+                         const int32_t* col_blk, const int32_t* col_src, const float* low_latent, float* prev, float* x0,
+                         float* x_next, float* low_dir, float* uncond_last, float* direction, float* local, int K, int B,
+                         int C, int H, int W, int h, int w, int gPH, int gPW, int g_off_y, int g_off_x, int vPH, int vPW,
+                         int n_col_blocks, float g, float sqrt_beta_t, float sqrt_alpha_t, float c_x, float b, float half_b,
+                         float r_inv, float rrg_norm, float rrg_weight, int prediction_type, const float* ratio,
+                         const float* ratio_low, float gr, float omgr, const float* x0_hist, int multistep,
+                         const float* region_w, int P, void* stream) {
+  if (bad_prediction_type(prediction_type) || bad_region_rows(P) || (!region_w && P > 1) || (multistep != 0 && multistep != 1) ||
+      (!multistep && x0_hist))
+    return (int)hipErrorInvalidValue;
+  const bool vp = prediction_type == ED_PRED_V;
+  Multistep ms = {x0_hist, half_b, r_inv};
+  if (!region_w)  // P == 1: the launch of ed_phase_epilogue_ms (multistep) / ed_phase_epilogue_gr
+    return phase_epilogue_launch(vp, g_out, v_out, dtype, x, stamp, inv_row, inv_col, up_row, up_col, down_row, down_col, row_blk,
+                                 row_src, col_blk, col_src, low_latent, prev, x0, x_next, low_dir, uncond_last, direction, local, K,
+                                 B, C, H, W, h, w, gPH, gPW, g_off_y, g_off_x, vPH, vPW, n_col_blocks, g, sqrt_beta_t, sqrt_alpha_t,
+                                 c_x, b, rrg_norm, rrg_weight, stream, ratio, ratio_low, gr, omgr, multistep ? &ms : nullptr);
+  const float* full[] = {prev, x0, x_next, direction, local};
+  const float* low[] = {low_dir, uncond_last};
+  if (B < 0 || C < 0 || H < 0 || W < 0 || h < 0 || w < 0 || K <= 0 ||
+      region_w_overlaps_outputs(region_w, P, B, C, H, W, h, w, full, 5, low, 2))
+    return (int)hipErrorInvalidValue;
+  int64_t n = (int64_t)B * C * H * W + (int64_t)B * C * h * w;
+  if ((int64_t)B * C * H * W == 0) return 0;
+  if (!g_out || !v_out || !x || !prev || !x0) return (int)hipErrorInvalidValue;
+  if (x_next && !low_latent) return (int)hipErrorInvalidValue;
+  if (ratio && x_next && !ratio_low) return (int)hipErrorInvalidValue;
+  if (hist_overlaps(x0_hist, prev, x0, (int64_t)B * C * H * W)) return (int)hipErrorInvalidValue;
+  EpilogueArgsRG a;
+  a.region_w = region_w, a.P = P;
+  a.ratio = ratio, a.ratio_low = ratio_low, a.gr = gr, a.omgr = omgr;
+  a.x0_hist = x0_hist, a.hb = half_b, a.r_inv = r_inv;
+  a.g_out = g_out, a.v_out = v_out, a.x = x, a.stamp = stamp;
+  a.inv_row = inv_row, a.inv_col = inv_col, a.up_row = up_row, a.up_col = up_col, a.down_row = down_row, a.down_col = down_col;
+  a.row_blk = row_blk, a.row_src = row_src, a.col_blk = col_blk, a.col_src = col_src;
+  a.low_latent = low_latent, a.prev = prev, a.x0 = x0, a.x_next = x_next, a.low_dir = low_dir, a.uncond_last = uncond_last;
+  a.direction = direction, a.local = local;
+  a.K = K, a.B = B, a.C = C, a.H = H, a.W = W, a.h = h, a.w = w, a.gPH = gPH, a.gPW = gPW, a.g_off_y = g_off_y;
+  a.g_off_x = g_off_x, a.vPH = vPH, a.vPW = vPW, a.ncb = n_col_blocks;
+  a.g = g, a.sb = sqrt_beta_t, a.sa = sqrt_alpha_t, a.sp = c_x, a.sd = b;
+  a.rrg_norm = rrg_norm, a.rrg_weight = rrg_weight;
+#define ED_EPI_RG(T, ST)                                                                                          \
+  if (ratio && vp) k_phase_epilogue_rg<T, true, true, ST><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(a);   \
+  else if (ratio) k_phase_epilogue_rg<T, false, true, ST><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(a);   \
+  else if (vp) k_phase_epilogue_rg<T, true, false, ST><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(a);      \
+  else k_phase_epilogue_rg<T, false, false, ST><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(a);
+#define ED_EPI_RG_T(ST)                        \
+  switch (dtype) {                             \
+    case ED_F32: ED_EPI_RG(F32, ST) break;     \
+    case ED_F16: ED_EPI_RG(F16, ST) break;     \
+    case ED_BF16: ED_EPI_RG(BF16, ST) break;   \
+    default: return (int)hipErrorInvalidValue; \
+  }
+  if (!multistep) { ED_EPI_RG_T(ST_DDIM) } else if (x0_hist) { ED_EPI_RG_T(ST_MS2) } else { ED_EPI_RG_T(ST_MS1) }
+#undef ED_EPI_RG_T
+#undef ED_EPI_RG
+  return done();
+}
+
+int ed_phase_moments_rg(const void* g_out, const void* v_out, int dtype, const int8_t* stamp, const int32_t* inv_row,
+                        const int32_t* inv_col, const int32_t* up_row, const int32_t* up_col, const int32_t* down_row,
+                        const int32_t* down_col, const int32_t* row_blk, const int32_t* row_src, const int32_t* col_blk,
+                        const int32_t* col_src, float* ratio, float* ratio_low, void* workspace, int K, int B, int C, int H,
+                        int W, int h, int w, int gPH, int gPW, int g_off_y, int g_off_x, int vPH, int vPW, int n_col_blocks,
+                        float g, const float* region_w, int P, void* stream) {
+  if (bad_region_rows(P) || (!region_w && P > 1)) return (int)hipErrorInvalidValue;
+  if (!region_w)
+    return ed_phase_moments(g_out, v_out, dtype, stamp, inv_row, inv_col, up_row, up_col, down_row, down_col, row_blk, row_src,
+                            col_blk, col_src, ratio, ratio_low, workspace, K, B, C, H, W, h, w, gPH, gPW, g_off_y, g_off_x, vPH,
+                            vPW, n_col_blocks, g, stream);
+  int64_t n_full = (int64_t)C * H * W, n_low = (int64_t)C * h * w;
+  if (B <= 0 || n_full <= 0) return B < 0 || n_full < 0 ? (int)hipErrorInvalidValue : 0;
+  if (bad_workspace(workspace) || !ratio || K <= 0 || (ratio_low && n_low <= 0)) return (int)hipErrorInvalidValue;
+  int nblk_full = moments_blocks(n_full), nblk_low = ratio_low ? moments_blocks(n_low) : 0;
+  int64_t wb = (int64_t)P * H * W * 4;
+  if (ranges_overlap(region_w, wb, ratio, (int64_t)B * 4) || ranges_overlap(region_w, wb, ratio_low, (int64_t)B * 4) ||
+      ranges_overlap(region_w, wb, workspace, (int64_t)B * (nblk_full + nblk_low) * 6 * 8))
+    return (int)hipErrorInvalidValue;
+  EpilogueArgsRG a = {};
+  a.region_w = region_w, a.P = P;
+  a.g_out = g_out, a.v_out = v_out, a.stamp = stamp;
+  a.inv_row = inv_row, a.inv_col = inv_col, a.up_row = up_row, a.up_col = up_col, a.down_row = down_row, a.down_col = down_col;
+  a.row_blk = row_blk, a.row_src = row_src, a.col_blk = col_blk, a.col_src = col_src;
+  a.K = K, a.B = B, a.C = C, a.H = H, a.W = W, a.h = h, a.w = w, a.gPH = gPH, a.gPW = gPW, a.g_off_y = g_off_y;
+  a.g_off_x = g_off_x, a.vPH = vPH, a.vPW = vPW, a.ncb = n_col_blocks, a.g = g;
+  dim3 grid(B * (nblk_full + nblk_low)), block(ED_BLOCK);
+  hipStream_t st_ = (hipStream_t)stream;
+  switch (dtype) {
+    case ED_F32: k_phase_moments_rg<F32><<<grid, block, 0, st_>>>(a, nblk_full, nblk_low, (double*)workspace); break;
+    case ED_F16: k_phase_moments_rg<F16><<<grid, block, 0, st_>>>(a, nblk_full, nblk_low, (double*)workspace); break;
+    case ED_BF16: k_phase_moments_rg<BF16><<<grid, block, 0, st_>>>(a, nblk_full, nblk_low, (double*)workspace); break;
+    default: return (int)hipErrorInvalidValue;
+  }
+  k_moments_finalise<<<ratio_low ? 2 * B : B, 64, 0, st_>>>((const double*)workspace, B, nblk_full, nblk_low, ratio, ratio_low);
   return done();
 }
 

@@ -232,6 +232,114 @@ def assemble_rows_x(latent, idx, src_row, src_col, g_rows, h, w, g_off_y, g_off_
                                                        + K * h * w + (0 if low is None else 4 * low.numel())))
 
 
+MAX_REGION_ROWS = 8  # ED_MAX_REGION_ROWS: the conditional rows of a step, base prompt + at most 7 regions
+
+
+def assemble_rows_n(latent, idx, src_row, src_col, g_rows, h, w, g_off_y, g_off_x, gframe, low, v_rows, win_y0, win_x0, Sh,
+                    Sw, v_off_y, v_off_x, vframe, copies, extra=None, pad_value=None):
+    """``assemble_rows`` / ``assemble_rows_x`` with ``copies`` (2..9) rows per resampling step and sample in the place of 2 (see
+    ed_assemble_rows_n): g_rows [(K*copies*B),C+E,gPH,gPW]; ``extra`` / ``pad_value`` as in ``assemble_rows_x`` or both None (E = 0)."""
+    if not isinstance(latent, torch.Tensor) or latent.dim() != 4:
+        _reject(f"assemble_rows_n: latent must be an f32 [B,C,H,W] tensor on the MI355X; no CPU fallback (got "
+                f"{tuple(getattr(latent, 'shape', ()))})")
+    B, C, H, W = latent.shape
+    if not isinstance(copies, int) or not 2 <= copies <= 1 + MAX_REGION_ROWS:
+        _reject(f"assemble_rows_n: copies must be an int in [2, {1 + MAX_REGION_ROWS}], got {copies!r}")
+    E = 0
+    if (extra is None) != (pad_value is None):
+        _reject("assemble_rows_n: extra and pad_value come together")
+    if extra is not None:
+        if not isinstance(extra, torch.Tensor) or extra.dim() != 4 or extra.shape[1] < 1 or \
+                (extra.shape[0], extra.shape[2], extra.shape[3]) != (B, H, W):
+            _reject(f"assemble_rows_n: extra must be f32 [{B},E,{H},{W}] with E >= 1, got {tuple(getattr(extra, 'shape', ()))}")
+        E = int(extra.shape[1])
+        if not isinstance(pad_value, torch.Tensor) or tuple(pad_value.shape) != (E,):
+            _reject(f"assemble_rows_n: pad_value must be an f32 [{E}] device tensor, got {tuple(getattr(pad_value, 'shape', ()))}")
+    K, V = idx.shape[0], win_y0.numel()
+    gr, C2, gPH, gPW = g_rows.shape
+    vr, C3, vPH, vPW = v_rows.shape
+    if not (gr == K * copies * B and vr == V * B and C2 == C + E == C3 and g_rows.dtype == v_rows.dtype):
+        _reject(f"assemble_rows_n: rows must be [{K * copies * B},{C + E},..] and [{V * B},{C + E},..] of one dtype, got "
+                f"{tuple(g_rows.shape)} {g_rows.dtype} / {tuple(v_rows.shape)} {v_rows.dtype}")
+    assert idx.shape[1] == h * w and src_row.numel() == 2 * h and src_col.numel() == 2 * w and win_x0.numel() == V
+    assert g_off_y + h <= gPH and g_off_x + w <= gPW and v_off_y + Sh <= vPH and v_off_x + Sw <= vPW
+    if gframe is not None:
+        assert tuple(gframe.shape) == (C, gPH, gPW)
+    if vframe is not None:
+        assert tuple(vframe.shape) == (C, vPH, vPW)
+    if low is not None:
+        assert tuple(low.shape) == (K, B, C, h, w)
+    _call("ed_assemble_rows_n", _dev(latent, torch.float32, "latent"), B, C, H, W, _dev(idx, torch.uint8, "idx"),
+          _dev(src_row, torch.int32), _dev(src_col, torch.int32), _opt(gframe, torch.float32, "gframe"),
+          _dev(g_rows, None, "g_rows"), _opt(low, torch.float32, "low"), K, h, w, gPH, gPW, g_off_y, g_off_x,
+          _dev(win_y0, torch.int32), _dev(win_x0, torch.int32), _opt(vframe, torch.float32, "vframe"),
+          _dev(v_rows, None, "v_rows"), V, Sh, Sw, vPH, vPW, v_off_y, v_off_x, _code(g_rows, "g_rows"),
+          _opt(extra, torch.float32, "extra"), E, _opt(pad_value, torch.float32, "pad_value"), copies, _stream())
+    # algorithmic bytes: every row element written once, one fp32 read per picked vector and view element, the picks and `low`
+    n_g, n_v = gr * gPH * gPW * (C + E), vr * vPH * vPW * (C + E)
+    TIMER.note_work("ed_assemble_rows_n", nbytes=float((n_g + n_v) * g_rows.element_size() + 4 * (n_g // copies + n_v)
+                                                       + K * h * w + (0 if low is None else 4 * low.numel())))
+
+
+def _region_w(region_w, H, W, what, outputs=()):
+    """``region_w`` f32 [P,H,W] on the device, 1 <= P <= 8, sharing no memory with the launch's outputs -> (pointer, P)"""
+    if not isinstance(region_w, torch.Tensor) or region_w.dim() != 3 or tuple(region_w.shape[1:]) != (H, W) or \
+            not 1 <= region_w.shape[0] <= MAX_REGION_ROWS:
+        _reject(f"{what}: region_w must be an f32 [P,{H},{W}] tensor with 1 <= P <= {MAX_REGION_ROWS}, got "
+                f"{tuple(getattr(region_w, 'shape', ()))}")
+    lo, hi = region_w.data_ptr(), region_w.data_ptr() + 4 * region_w.numel()
+    for t_ in outputs:
+        if isinstance(t_, torch.Tensor) and t_.data_ptr() < hi and lo < t_.data_ptr() + t_.element_size() * t_.numel():
+            _reject(f"{what}: region_w overlaps an output of the launch")
+    return _dev(region_w, torch.float32, "region_w"), int(region_w.shape[0])
+
+
+def region_weights(masks, weights, out=None):
+    """masks u8 [n,Hl,Wl] (255 = inside the region), ``weights`` n floats > 0 -> f32 [n + 1,Hl,Wl]: the per-pixel weights of the
+    base prompt (plane 0) and the n regions, summing to 1 (see ed_region_weights).  1 <= n <= 7.  One launch."""
+    import ctypes
+    if not isinstance(masks, torch.Tensor) or masks.dim() != 3 or not 1 <= masks.shape[0] <= MAX_REGION_ROWS - 1:
+        _reject(f"region_weights: masks must be a u8 [n,Hl,Wl] tensor on the MI355X with 1 <= n <= {MAX_REGION_ROWS - 1}; no CPU "
+                f"fallback (got {tuple(getattr(masks, 'shape', ()))})")
+    n, Hl, Wl = masks.shape
+    try:
+        wts = [float(v) for v in weights]
+    except (TypeError, ValueError):
+        _reject(f"region_weights: weights must be {n} floats, got {weights!r}")
+    if len(wts) != n or not all(0.0 < v < float("inf") for v in wts):
+        _reject(f"region_weights: weights must be {n} finite floats > 0, got {weights!r}")
+    if out is None:
+        out = torch.empty(n + 1, Hl, Wl, dtype=torch.float32, device=masks.device)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (n + 1, Hl, Wl):
+        _reject(f"region_weights: out must be f32 [{n + 1},{Hl},{Wl}], got {tuple(getattr(out, 'shape', ()))}")
+    _call("ed_region_weights", _dev(masks, torch.uint8, "masks"), (ctypes.c_float * n)(*wts), n, Hl * Wl,
+          _dev(out, torch.float32, "out"), _stream())
+    TIMER.note_work("ed_region_weights", nbytes=float(n * Hl * Wl + 4 * (n + 1) * Hl * Wl))
+    return out
+
+
+def region_blend(dirs, region_w, out=None):
+    """dirs f32 [P,B,C,H,W] (the P per-region class directions), region_w f32 [P,H,W] -> f32 [B,C,H,W], the weighted sum over p with
+    the skip rule and order of the fused regional epilogue (see ed_region_blend): the un-fused path's last step."""
+    if not isinstance(dirs, torch.Tensor) or dirs.dim() != 5:
+        _reject(f"region_blend: dirs must be an f32 [P,B,C,H,W] tensor on the MI355X; no CPU fallback (got "
+                f"{tuple(getattr(dirs, 'shape', ()))})")
+    P, B, C, H, W = dirs.shape
+    if out is None:
+        out = torch.empty(B, C, H, W, dtype=torch.float32, device=dirs.device)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (B, C, H, W):
+        _reject(f"region_blend: out must be f32 [{B},{C},{H},{W}], got {tuple(getattr(out, 'shape', ()))}")
+    lo, hi = out.data_ptr(), out.data_ptr() + 4 * out.numel()
+    if dirs.data_ptr() < hi and lo < dirs.data_ptr() + 4 * dirs.numel():
+        _reject("region_blend: dirs overlaps out")
+    wp, P2 = _region_w(region_w, H, W, "region_blend", (out,))
+    if P2 != P:
+        _reject(f"region_blend: dirs holds {P} directions, region_w {P2} planes")
+    _call("ed_region_blend", _dev(dirs, torch.float32, "dirs"), wp, _dev(out, torch.float32, "out"), P, B * C, H * W, _stream())
+    TIMER.note_work("ed_region_blend", nbytes=4.0 * (dirs.numel() + region_w.numel() + out.numel()))
+    return out
+
+
 PREDICTION_TYPES = {"epsilon": 0, "v_prediction": 1}  # ED_PRED_EPSILON / ED_PRED_V
 
 
@@ -309,15 +417,17 @@ def guidance_moments(local, direction, g, ratio, workspace, text=None):
 
 
 def phase_moments(g_out, v_out, shape, stamp, pick_tables, view_tables, n_col_blocks, g_off, K, h, w, g, ratio, workspace,
-                  ratio_low=None):
+                  ratio_low=None, region_w=None):
     """The ratios guidance_moments would give on the ``direction`` / ``local`` (and, with ``ratio_low``, the
     ``uncond_last`` / ``low_dir``) by-products of phase_epilogue, reduced straight from the model output rows (see
     ed_phase_moments): same arguments as phase_epilogue, ``shape`` = (B, C, H, W) of the latent.
-    workspace = guidance_moments_workspace(B, C*H*W, C*h*w if ratio_low is given else 0)."""
+    workspace = guidance_moments_workspace(B, C*H*W, C*h*w if ratio_low is given else 0).  ``region_w`` (f32 [P,H,W], regional
+    prompts): g_out holds 1 + P rows per step and sample and the direction is their weighted sum (ed_phase_moments_rg)."""
     B, C, H, W = shape
     gr, C2, gPH, gPW = g_out.shape
     vr, C3, vPH, vPW = v_out.shape
-    assert gr == K * 2 * B and C2 == C == C3 and vr % B == 0 and g_out.dtype == v_out.dtype
+    copies = 2 if region_w is None else 1 + int(getattr(region_w, "shape", (1,))[0])
+    assert gr == K * copies * B and C2 == C == C3 and vr % B == 0 and g_out.dtype == v_out.dtype
     assert tuple(stamp.shape) == (h * w, 4)
     inv_row, inv_col, up_row, up_col, down_row, down_col = pick_tables
     assert inv_row.numel() == 2 * H and inv_col.numel() == 2 * W and up_row.numel() == H and up_col.numel() == W
@@ -328,6 +438,15 @@ def phase_moments(g_out, v_out, shape, stamp, pick_tables, view_tables, n_col_bl
         if t_ is not None and tuple(t_.shape) != (B,):
             _reject(f"phase_moments: {name} must be f32 [{B}], got {tuple(t_.shape)}")
     n_low = C * h * w if ratio_low is not None else 0
+    if region_w is not None:
+        wp, P = _region_w(region_w, H, W, "phase_moments", (ratio, ratio_low, workspace))
+        _call("ed_phase_moments_rg", _dev(g_out, None, "g_out"), _dev(v_out, None, "v_out"), _code(g_out, "g_out"),
+              _dev(stamp, torch.int8, "stamp"), *(_dev(t_, torch.int32) for t_ in pick_tables),
+              *(_dev(t_, torch.int32) for t_ in view_tables), _dev(ratio, torch.float32, "ratio"),
+              _opt(ratio_low, torch.float32, "ratio_low"), _workspace(workspace, B, C * H * W, n_low),
+              K, B, C, H, W, h, w, gPH, gPW, g_off[0], g_off[1], vPH, vPW, n_col_blocks, float(g), wp, P, _stream())
+        TIMER.note_work("ed_phase_moments_rg", nbytes=(2.0 + P) * g_out.element_size() * B * (C * H * W + n_low))
+        return ratio, ratio_low
     _call("ed_phase_moments", _dev(g_out, None, "g_out"), _dev(v_out, None, "v_out"), _code(g_out, "g_out"),
           _dev(stamp, torch.int8, "stamp"), *(_dev(t_, torch.int32) for t_ in pick_tables),
           *(_dev(t_, torch.int32) for t_ in view_tables), _dev(ratio, torch.float32, "ratio"),
@@ -341,19 +460,23 @@ def phase_moments(g_out, v_out, shape, stamp, pick_tables, view_tables, n_col_bl
 def phase_epilogue(g_out, v_out, x, stamp, pick_tables, view_tables, n_col_blocks, g_off, K, h, w, g, coef, prev, x0,
                    low_dir=None, uncond_last=None, direction=None, local=None, x_next=None, low_latent=None,
                    rrg_norm=0.0, rrg_weight=0.0, prediction_type="epsilon", ratio=None, ratio_low=None,
-                   guidance_rescale=0.0, multistep=None):
+                   guidance_rescale=0.0, multistep=None, region_w=None):
     """unpad_direction + fill_directions + scatter_centres + cfg_ddim_step (+ rrg_update when ``x_next`` is given) in
     one launch (see ed_phase_epilogue / ed_phase_epilogue_pt).  pick_tables = (inv_row, inv_col, up_row, up_col,
     down_row, down_col); view_tables = (row_blk, row_src, col_blk, col_src); coef = DDIMSchedule.step_coefficients(t);
     prediction_type = the scheduler's ("epsilon" or "v_prediction").  ``ratio`` (f32 [B] from phase_moments, with
     ``ratio_low`` when ``x_next`` is given) applies the guidance rescale ``guidance_rescale`` (ed_phase_epilogue_gr);
     None is the plain launch.  ``multistep`` = (c_x, b, half_b, r_inv, x0_hist or None): the DPM-Solver++(2M) update in the
-    DDIM one's place (ed_phase_epilogue_ms; only coef[:2] are then used); None launches what it always launched."""
+    DDIM one's place (ed_phase_epilogue_ms; only coef[:2] are then used); None launches what it always launched.
+    ``region_w`` (f32 [P,H,W] from ``region_weights``; regional prompts): g_out holds 1 + P rows per step and
+    sample, [(K*(1+P)*B),C,gPH,gPW], and the class direction of a pixel is the weighted sum of the P directions cond_p - uncond
+    (ed_phase_epilogue_rg, one launch with every other keyword as above); None launches what it always launched."""
     pt = _pred_code(prediction_type)
     B, C, H, W = x.shape
     gr, C2, gPH, gPW = g_out.shape
     vr, C3, vPH, vPW = v_out.shape
-    assert gr == K * 2 * B and C2 == C == C3 and vr % B == 0 and g_out.dtype == v_out.dtype
+    copies = 2 if region_w is None else 1 + int(getattr(region_w, "shape", (1,))[0])
+    assert gr == K * copies * B and C2 == C == C3 and vr % B == 0 and g_out.dtype == v_out.dtype
     assert tuple(stamp.shape) == (h * w, 4) and tuple(prev.shape) == tuple(x.shape) == tuple(x0.shape)
     inv_row, inv_col, up_row, up_col, down_row, down_col = pick_tables
     assert inv_row.numel() == 2 * H and inv_col.numel() == 2 * W and up_row.numel() == H and up_col.numel() == W
@@ -368,6 +491,31 @@ def phase_epilogue(g_out, v_out, x, stamp, pick_tables, view_tables, n_col_block
     f32 = torch.float32
     if ratio is None and (ratio_low is not None or float(guidance_rescale) != 0.0):
         _reject("phase_epilogue: guidance_rescale / ratio_low need ratio (phase_moments)")
+    if region_w is not None:
+        ms, x0_hist = (tuple(float(c) for c in coef[2:4]) + (0.0, 0.0), None)
+        if multistep is not None:
+            ms, x0_hist = _multistep(multistep, prev, x0, "phase_epilogue")
+            if x0_hist is not None and tuple(x0_hist.shape) != tuple(x0.shape):
+                _reject(f"phase_epilogue: x0_hist must have x0's shape {tuple(x0.shape)}, got {tuple(x0_hist.shape)}")
+        gr_f, omgr_f = 0.0, 0.0
+        if ratio is not None:
+            if x_next is not None and ratio_low is None:
+                _reject("phase_epilogue: the fused RRG term with a rescale needs ratio_low")
+            if ratio_low is not None and tuple(ratio_low.shape) != (B,):
+                _reject(f"ratio_low must be f32 [{B}], got {tuple(ratio_low.shape)}")
+            gr_f, omgr_f = rescale_coefficients(guidance_rescale)
+        wp, P = _region_w(region_w, H, W, "phase_epilogue", (prev, x0, x_next, low_dir, uncond_last, direction, local))
+        _call("ed_phase_epilogue_rg", _dev(g_out, None, "g_out"), _dev(v_out, None, "v_out"), _code(g_out, "g_out"),
+              _dev(x, f32, "x"), _dev(stamp, torch.int8, "stamp"), *(_dev(t_, torch.int32) for t_ in pick_tables),
+              *(_dev(t_, torch.int32) for t_ in view_tables), _opt(low_latent, f32, "low_latent"), _dev(prev, f32, "prev"),
+              _dev(x0, f32, "x0"), _opt(x_next, f32, "x_next"), _opt(low_dir, f32, "low_dir"),
+              _opt(uncond_last, f32, "uncond_last"), _opt(direction, f32, "direction"), _opt(local, f32, "local"),
+              K, B, C, H, W, h, w, gPH, gPW, g_off[0], g_off[1], vPH, vPW, n_col_blocks, float(g), float(coef[0]), float(coef[1]),
+              *ms, float(rrg_norm), float(rrg_weight), pt, None if ratio is None else _ratio_ptr(ratio, B, "ratio"),
+              _opt(ratio_low, f32, "ratio_low"), gr_f, omgr_f, _opt(x0_hist, f32, "x0_hist"), int(multistep is not None), wp, P,
+              _stream())
+        TIMER.note_work("ed_phase_epilogue_rg", nbytes=float(g_out.element_size() * (2 + P) * x.numel() + 4 * 3 * x.numel()))
+        return prev, x0
     if multistep is not None:
         ms, x0_hist = _multistep(multistep, prev, x0, "phase_epilogue")
         if x0_hist is not None and tuple(x0_hist.shape) != tuple(x0.shape):

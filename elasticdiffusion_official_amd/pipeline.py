@@ -245,6 +245,73 @@ def check_soft_inpaint_arguments(init_image=None, mask_image=None, mask_blur=0.0
     return blur
 
 
+MAX_REGIONS = 7  # + the base prompt = ops.MAX_REGION_ROWS conditional rows per resampling step
+
+
+def check_region_arguments(regions, height, width, scale=8, region_blur=0.0, in_channels=4):
+    """The argument rules of ``regions`` / ``region_blur`` (regional prompts), pure host code that runs before
+    anything is launched -> (None, 0.0) without regions, else ([(prompt, mask, weight), ...], region_blur as a float) with every
+    weight a float and every mask one of: ("box", (x0, y0, x1, y1)) in pixels, ("pixel", picture) an 8-bit picture (L PIL image,
+    uint8 [H,W] / [H,W,1]) of height x width, ("latent", uint8 array / tensor) of (height // scale, width // scale).
+    ValueError: not 1..7 regions; an entry that is not (prompt, mask) or (prompt, mask, weight); a prompt that is not a string; a
+    weight that is not a finite float > 0; a mask of any other size or kind; a box that is empty or leaves the picture; a blur
+    radius that is not in [0, ops.MASK_BLUR_MAX]; ``region_blur`` without regions; a 9-channel inpainting UNet."""
+    try:
+        blur = float(region_blur)
+    except (TypeError, ValueError):
+        raise ValueError(f"region_blur must be a number in [0, {ops.MASK_BLUR_MAX:g}], got {region_blur!r}") from None
+    if not 0.0 <= blur <= ops.MASK_BLUR_MAX:  # also refuses NaN
+        raise ValueError(f"region_blur must be finite and in [0, {ops.MASK_BLUR_MAX:g}], got {region_blur!r}")
+    if regions is None:
+        if blur > 0:
+            raise ValueError("region_blur needs regions")
+        return None, 0.0
+    if in_channels != 4:
+        raise ValueError("regions are not supported with a 9-channel inpainting UNet (its mask and masked-image rows are out of "
+                         "scope for regional prompts)")
+    regions = list(regions)
+    if not 1 <= len(regions) <= MAX_REGIONS:
+        raise ValueError(f"regions must hold 1 to {MAX_REGIONS} (prompt, mask[, weight]) entries, got {len(regions)}")
+    Hl, Wl = height // scale, width // scale
+    out = []
+    for k, entry in enumerate(regions):
+        if not isinstance(entry, (tuple, list)) or len(entry) not in (2, 3):
+            raise ValueError(f"regions[{k}] must be (prompt, mask) or (prompt, mask, weight), got {entry!r}")
+        prompt, mask = entry[0], entry[1]
+        if not isinstance(prompt, str):
+            raise ValueError(f"regions[{k}]: the prompt must be a string (it applies to every sample), got {type(prompt).__name__}")
+        try:
+            weight = float(entry[2]) if len(entry) == 3 else 1.0
+        except (TypeError, ValueError):
+            raise ValueError(f"regions[{k}]: weight must be a float > 0, got {entry[2]!r}") from None
+        if not 0.0 < weight < float("inf"):
+            raise ValueError(f"regions[{k}]: weight must be a finite float > 0, got {entry[2]!r}")
+        if isinstance(mask, (tuple, list)):
+            if len(mask) != 4 or not all(isinstance(v, (int, np.integer)) for v in mask):
+                raise ValueError(f"regions[{k}]: a box must be four ints (x0, y0, x1, y1) in pixels, got {mask!r}")
+            x0, y0, x1, y1 = (int(v) for v in mask)
+            if not (0 <= x0 < x1 <= width and 0 <= y0 < y1 <= height):
+                raise ValueError(f"regions[{k}]: box {tuple(mask)} must satisfy 0 <= x0 < x1 <= {width} and 0 <= y0 < y1 <= {height}")
+            out.append((prompt, ("box", (x0, y0, x1, y1)), weight))
+            continue
+        if hasattr(mask, "convert"):
+            size = (mask.size[1], mask.size[0])
+        elif isinstance(mask, (np.ndarray, torch.Tensor)) and mask.dtype in (np.uint8, torch.uint8) and \
+                (mask.ndim == 2 or (mask.ndim == 3 and mask.shape[2] == 1)):
+            size = tuple(int(v) for v in mask.shape[:2])
+        else:
+            raise ValueError(f"regions[{k}]: the mask must be an L PIL image, a uint8 [H,W] array / tensor or a box (x0, y0, x1, y1), "
+                             f"got {type(mask).__name__} {getattr(mask, 'dtype', '')}")
+        if size == (height, width):
+            out.append((prompt, ("pixel", mask), weight))
+        elif size == (Hl, Wl) and not hasattr(mask, "convert"):
+            out.append((prompt, ("latent", mask), weight))
+        else:
+            raise ValueError(f"regions[{k}]: the mask is {size}; it must be the picture's {(height, width)} or, as a uint8 array / "
+                             f"tensor, the latent's {(Hl, Wl)}")
+    return out, blur
+
+
 class _Plan:
     """Per-call geometry: host plans (geometry.py) + their int32 device tables + the pick sampler."""
 
@@ -425,6 +492,7 @@ class ElasticDiffusion(nn.Module):
         self.last_pixel_mask = None    # uint8 [height,width]: its (resized, blurred) 8-bit picture mask, on the device
         self.last_masked_image_latents = None  # zm of the last image on a 9-channel UNet (the blanked picture's scaled latent)
         self.last_score_pca = None     # the PCA maps of the last ``generate_latents(score_pca=True)``, else None
+        self.last_region_weights = None  # f32 [n + 1,Hl,Wl] of the last run with ``regions`` (plane 0 the base prompt's), else None
 
     @staticmethod
     def _model_layout(module):
@@ -812,10 +880,12 @@ class ElasticDiffusion(nn.Module):
         return frames
 
     def _embed_rows(self, K, V, un, co, pun, pco):
-        """Text rows for one fused model batch: K x [uncond(B), cond(B)] then V x uncond(B)  (ED:436-438, 846-847)."""
+        """Text rows for one fused model batch: K x [uncond(B), cond(B)] then V x uncond(B)  (ED:436-438, 846-847).  With regional
+        prompts ``co`` / ``pco`` are lists of the P conditional embeddings (base prompt first): K x [uncond, cond_0 .. cond_{P-1}]."""
         dt = self.model_dtype
-        text = torch.cat([un, co] * K + [un] * V).to(dt).contiguous()
-        pooled = torch.cat([pun, pco] * K + [pun] * V).to(dt).contiguous()
+        cos, pcos = (list(co), list(pco)) if isinstance(co, (list, tuple)) else ([co], [pco])
+        text = torch.cat([un, *cos] * K + [un] * V).to(dt).contiguous()
+        pooled = torch.cat([pun, *pcos] * K + [pun] * V).to(dt).contiguous()
         return text, pooled
 
     # ---- model boundary ----------------------------------------------------------------------------
@@ -868,7 +938,7 @@ class ElasticDiffusion(nn.Module):
 
     # ---- one estimation phase (ED:1016-1035 or ED:1043-1056) ---------------------------------------
     def _phase_steps(self, P, x, ti, K, g, drop_p, emb, cond=None, direct=True, rrg_w=None, rrg_norm=0.0, frames=None,
-                     rescale=None, extras=None, multistep=None, keep_scores=False):
+                     rescale=None, extras=None, multistep=None, keep_scores=False, region_w=None):
         """Generator: pre-model glue -> ``yield _ModelCall`` (receives the model output rows) -> post-model glue;
         returns (prev, x0, info).  ``direct``: assemble straight into the hipGraph's static input (one image in flight,
         one rank); otherwise into a scratch batch the driver concatenates / the sharder slices.  ``rrg_w``: this is the
@@ -879,12 +949,17 @@ class ElasticDiffusion(nn.Module):
         pad_value [E]) on a 9-channel inpainting UNet: the model rows carry C + E channels, the extra ones registered to each row's
         latent (``ops.assemble_rows_x``); everything after the model call is unchanged.  ``multistep`` (``_multistep_args``): the
         DPM-Solver++(2M) update of this timestep in the DDIM one's place, in the same launch; None launches what it always did.
-        ``keep_scores``: info["direction"] / info["local"] are kept as ``verbose`` keeps them (the inputs of the score PCA maps)."""
+        ``keep_scores``: info["direction"] / info["local"] are kept as ``verbose`` keeps them (the inputs of the score PCA maps).
+        ``region_w`` (f32 [P,Hl,Wl]; regional prompts): a step holds 1 + P rows per sample and the class direction
+        is the per-pixel weighted sum of the P directions -- ``ops.assemble_rows_n`` and the regional epilogue in the places of the
+        plain launches; None launches what it always did."""
         ms_kw = {} if multistep is None else dict(multistep=multistep)
         B, C = x.shape[:2]
         CR = C if extras is None else C + extras[0].shape[1]  # channels of a model INPUT row
         dev, mdt = self.device, self.model_dtype
-        n_g, n_v = 2 * K * B, P.views.V * B
+        copies = 2 if region_w is None else 1 + region_w.shape[0]  # rows per resampling step and sample
+        assert region_w is None or extras is None
+        n_g, n_v = copies * K * B, P.views.V * B
         # host draws first (they never wait for the GPU)
         h0 = time.perf_counter()
         idx_host = self._stager.host((K, P.pick.N), torch.uint8)
@@ -910,7 +985,16 @@ class ElasticDiffusion(nn.Module):
         else:
             g_rows = torch.empty(n_g, CR, P.gpad.PH, P.gpad.PW, device=dev, dtype=mdt)
             v_rows = torch.empty(n_v, CR, P.vpad.PH, P.vpad.PW, device=dev, dtype=mdt)
-        if extras is not None:
+        if region_w is not None:
+            if FUSED_GLUE:
+                ops.assemble_rows_n(x, idx, P.src_row, P.src_col, g_rows, P.h, P.w, P.gpad.top, P.gpad.left, gframe, low,
+                                    v_rows, P.win_y0, P.win_x0, P.views.Sh, P.views.Sw, P.vpad.top, P.vpad.left, vframe, copies)
+            else:  # the pair rows as always, then every cond row a copy of the pair's
+                pair = torch.empty(2 * K * B, C, P.gpad.PH, P.gpad.PW, device=dev, dtype=mdt)
+                ops.pick_assemble(x, idx, P.src_row, P.src_col, pair, P.h, P.w, P.gpad.top, P.gpad.left, gframe, low)
+                ops.gather_views(x, v_rows, P.win_y0, P.win_x0, P.views.Sh, P.views.Sw, P.vpad.top, P.vpad.left, vframe)
+                g_rows.view(K, copies, B, C, P.gpad.PH, P.gpad.PW)[:] = pair.view(K, 2, B, C, P.gpad.PH, P.gpad.PW)[:, :1]
+        elif extras is not None:
             if FUSED_GLUE:
                 ops.assemble_rows_x(x, idx, P.src_row, P.src_col, g_rows, P.h, P.w, P.gpad.top, P.gpad.left, gframe, low,
                                     v_rows, P.win_y0, P.win_x0, P.views.Sh, P.views.Sw, P.vpad.top, P.vpad.left, vframe, *extras)
@@ -949,22 +1033,38 @@ class ElasticDiffusion(nn.Module):
             pick_t = (P.inv_row, P.inv_col, P.up_row, P.up_col, P.down_row, P.down_col)
             view_t = (P.row_blk, P.row_src, P.col_blk, P.col_src)
             rs_kw = {}
+            rg_kw = {} if region_w is None else dict(region_w=region_w)
             if rescale is not None:
                 ops.phase_moments(g_out, v_out, x.shape, stamp, pick_t, view_t, P.views.n_col_blocks,
                                   (P.gpad.top, P.gpad.left), K, P.h, P.w, np.float32(g), rescale.ratio, rescale.ws,
-                                  ratio_low=ratio_low)
+                                  ratio_low=ratio_low, **rg_kw)
                 rs_kw = dict(ratio=rescale.ratio, ratio_low=ratio_low, guidance_rescale=rescale.gr)
             ops.phase_epilogue(g_out, v_out, x, stamp, pick_t, view_t, P.views.n_col_blocks,
                                (P.gpad.top, P.gpad.left), K, P.h, P.w, np.float32(g), self._step_coef[ti], prev, x0,
                                low_dir=low_dir, uncond_last=uncond_last, direction=direction, local=local, x_next=x_next,
                                low_latent=low[K - 1] if rrg_w is not None else None, rrg_norm=rrg_norm,
-                               rrg_weight=0.0 if rrg_w is None else np.float32(rrg_w), prediction_type=pt, **rs_kw, **ms_kw)
+                               rrg_weight=0.0 if rrg_w is None else np.float32(rrg_w), prediction_type=pt, **rs_kw, **ms_kw,
+                               **rg_kw)
         else:
             dirs = torch.empty(K, B, C, P.h, P.w, device=dev, dtype=torch.float32)
-            ops.unpad_direction(g_out, dirs, uncond_last, P.gpad.top, P.gpad.left)
             direction = torch.empty_like(x)
-            ops.fill_directions(dirs, stamp, P.inv_row, P.inv_col, P.up_row, P.up_col, P.down_row, P.down_col, direction,
-                                low_dir)
+            if region_w is None:
+                ops.unpad_direction(g_out, dirs, uncond_last, P.gpad.top, P.gpad.left)
+                ops.fill_directions(dirs, stamp, P.inv_row, P.inv_col, P.up_row, P.up_col, P.down_row, P.down_col, direction,
+                                    low_dir)
+            else:  # the separate kernels once per region on its (uncond, cond_p) pair rows, then the weighted sums
+                n_p = copies - 1
+                g6 = g_out.view(K, copies, B, C, P.gpad.PH, P.gpad.PW)
+                full = torch.empty(n_p, *x.shape, device=dev, dtype=torch.float32)
+                lows = torch.empty(n_p, B, C, P.h, P.w, device=dev, dtype=torch.float32)
+                for p in range(n_p):
+                    pair = g6[:, [0, 1 + p]].reshape(2 * K * B, C, P.gpad.PH, P.gpad.PW).contiguous()
+                    ops.unpad_direction(pair, dirs, uncond_last, P.gpad.top, P.gpad.left)
+                    ops.fill_directions(dirs, stamp, P.inv_row, P.inv_col, P.up_row, P.up_col, P.down_row, P.down_col, full[p],
+                                        lows[p])
+                ops.region_blend(full, region_w, direction)
+                w_low = region_w[:, P.down_row.long()][:, :, P.down_col.long()].contiguous()  # low_dir samples (down_row, down_col)
+                ops.region_blend(lows, w_low, low_dir)
             local = torch.empty_like(x)
             ops.scatter_centres(v_out, local, P.views.n_col_blocks, P.row_blk, P.row_src, P.col_blk, P.col_src)
             rs_kw = {}
@@ -1012,7 +1112,7 @@ class ElasticDiffusion(nn.Module):
         return out
 
     # ---- ControlNet condition rows (EDC:457-461, 932-949) -- constant over the whole image ------------
-    def _condition_rows(self, P, cond_img, B, Ks):
+    def _condition_rows(self, P, cond_img, B, Ks, copies=2):
         s = self.vae_scale_factor
         cond_img = cond_img.to(self.device, torch.float32).contiguous()
         assert cond_img.shape[0] == 1 and tuple(cond_img.shape[-2:]) == (P.h * s, P.w * s), \
@@ -1044,7 +1144,7 @@ class ElasticDiffusion(nn.Module):
         ops.gather2d(cond_img, v_img, self._dev_i32([0] * V), self._dev_i32(rows_v), self._dev_i32(cols_v))
         out = {}
         for K in Ks:
-            g_part = g_img.expand(2 * K * B, -1, -1, -1)
+            g_part = g_img.expand(copies * K * B, -1, -1, -1)
             v_part = v_img.repeat_interleave(B, dim=0)
             out[K] = torch.cat([g_part, v_part]).contiguous() if P.one_batch else (g_part.contiguous(), v_part.contiguous())
         return out
@@ -1294,6 +1394,32 @@ class ElasticDiffusion(nn.Module):
         S.norm = np.float32(2.0 / (C * P.Hl * P.Wl))
         return S
 
+    def _region_weights(self, S, regions, region_blur):
+        """The per-pixel weights of a run's regions (``check_region_arguments``' list) -> f32 [n + 1,Hl,Wl] on the device.  A box is
+        drawn as a 255 rectangle at pixel size; a pixel-size mask is feathered by ``ops.gaussian_blur_u8`` when ``region_blur`` > 0
+        and reduced to the latent grid by ``ops.resize_u8`` (Pillow's BILINEAR bytes); a latent-size mask is used as is.  Then one
+        ``ops.region_weights`` launch.  Nothing syncs and nothing is drawn."""
+        P, s, dev = S.P, self.vae_scale_factor, self.device
+        H, W = P.Hl * s, P.Wl * s
+        masks = torch.empty(len(regions), P.Hl, P.Wl, dtype=torch.uint8, device=dev)
+        for k, (_, (kind, m), _) in enumerate(regions):
+            if kind == "latent":
+                t = torch.from_numpy(np.ascontiguousarray(m)) if isinstance(m, np.ndarray) else m
+                masks[k] = t.to(dev).reshape(P.Hl, P.Wl)
+                continue
+            if kind == "box":
+                u8 = torch.zeros(H, W, dtype=torch.uint8, device=dev)
+                u8[m[1]:m[3], m[0]:m[2]] = 255
+            else:
+                u8 = self._u8_image(m, 1, "region mask")
+                if isinstance(u8, np.ndarray):
+                    u8 = torch.from_numpy(np.ascontiguousarray(u8))
+                u8 = u8.to(dev).contiguous().view(H, W)
+            if region_blur > 0:
+                u8 = ops.gaussian_blur_u8(u8, region_blur)
+            masks[k] = ops.resize_u8(u8, (P.Hl, P.Wl), "bilinear")
+        return ops.region_weights(masks, [w for _, _, w in regions])
+
     def _prompt_chunks(self, prompts, negative_prompts):
         """Chunk count the encoder needs for these prompts and negative prompts together, or None for an encoder that does not
         chunk (an injected callable without ``chunks``, the synthetic embeddings)."""
@@ -1304,7 +1430,8 @@ class ElasticDiffusion(nn.Module):
 
     def _program(self, S, prompts, negative_prompts, condition_image=None, trace=None, progress=_identity_progress,
                  direct=True, frames=None, init_image=None, mask_image=None, mask_blur=0.0, mask_mode="binary",
-                 min_chunks=None, ip_adapter_image=None, ip_adapter_image_embeds=None, score_maps=None):
+                 min_chunks=None, ip_adapter_image=None, ip_adapter_image_embeds=None, score_maps=None, regions=None,
+                 region_blur=0.0):
         """Generator: the denoising loop of ONE image (ED:981-1078), yielding ``_ModelCall``s; returns the final latent.
         All host RNG draws happen inside, in the reference's order.  ``init_image`` / ``mask_image``: image-to-image and
         inpainting -- the loop starts at timestep index ``S.t_start`` from the noised encoding of the
@@ -1312,7 +1439,9 @@ class ElasticDiffusion(nn.Module):
         ``mask_mode``: the mask feathered on the device and, in "graded" mode, read as a per-pixel release time (section 19).
         ``score_maps`` (a dict; section 26): filled with {"pca_cls_dir": {i: bytes}, "pca_uncond": {i: bytes}}, the PCA maps
         (uint8 [B, Hl, Wl, 3], on the device) of the class direction and the local score of the FIRST phase of every timestep
-        index i with i % log_freq == 0."""
+        index i with i % log_freq == 0.  ``regions`` / ``region_blur`` (``check_region_arguments``' list; section 28): regional
+        prompts -- ``prompts`` is the base prompt, every region adds one conditional row per resampling step and sample, and the
+        class direction is their per-pixel weighted sum.  No draw depends on them."""
         P = S.P
         if isinstance(prompts, str):
             prompts = [prompts]
@@ -1321,6 +1450,8 @@ class ElasticDiffusion(nn.Module):
         # prompt and negative prompt share one token count: the larger chunk count of the two (and of ``min_chunks``)
         n = self._prompt_chunks(prompts, negative_prompts)
         if n is not None:
+            if regions:  # ... and of the region prompts: all are rows of one model batch
+                n = max(n, self.text_encoder.chunks([q for q, _, _ in regions]))
             n = max(n, int(min_chunks or 1))
         un, pun = self.get_text_embeds(negative_prompts, n)
         co, pco = self.get_text_embeds(prompts, n)
@@ -1328,12 +1459,20 @@ class ElasticDiffusion(nn.Module):
             raise ValueError(f"text_encoder returned {co.shape[1]} tokens for the prompts and {un.shape[1]} for the negative "
                              "prompts: the two are rows of one model batch and must have the same token count")
         B = len(prompts)
+        cos, pcos = [co], [pco]
+        for q, _, _ in regions or ():  # a region's prompt applies to every sample
+            cq, pq = self.get_text_embeds([q] * B, n)
+            if cq.shape[1] != co.shape[1]:
+                raise ValueError(f"text_encoder returned {cq.shape[1]} tokens for a region prompt and {co.shape[1]} for the prompts")
+            cos.append(cq)
+            pcos.append(pq)
         if ip_adapter_image is not None or ip_adapter_image_embeds is not None:
             # image prompt: the context of every row is [text tokens | image tokens] -- conditional rows carry the picture's tokens,
             # unconditional rows (the V view rows among them, through _embed_rows) the projection of a zero embedding
             iun, ico = self._ip_tokens(B, ip_adapter_image, ip_adapter_image_embeds)
             un = torch.cat([un, iun.to(un.dtype)], dim=1)
-            co = torch.cat([co, ico.to(co.dtype)], dim=1)
+            cos = [torch.cat([c, ico.to(c.dtype)], dim=1) for c in cos]  # the image tokens ride on every conditional row
+            co = cos[0]
         # initial latent from the host generator (ED:998-1000)
         z0 = noise0 = mask = None
         graded = mask_mode == "graded"
@@ -1349,12 +1488,19 @@ class ElasticDiffusion(nn.Module):
         if S.inpaint9:  # the model conditions on the mask and the blanked picture: nothing is pasted back (diffusers' num_channels_unet == 9)
             extras = self._inpaint9_extras(S, B, mask)
             mask = None
-        emb = {K: self._embed_rows(K, P.views.V, un, co, pun, pco) for K in S.Ks}
+        region_w = None
+        if regions:
+            region_w = self._region_weights(S, regions, region_blur)
+            emb = {K: self._embed_rows(K, P.views.V, un, cos, pun, pcos) for K in S.Ks}
+        else:
+            emb = {K: self._embed_rows(K, P.views.V, un, co, pun, pco) for K in S.Ks}
+        self.last_region_weights = region_w
+        rg_kw = {} if region_w is None else dict(region_w=region_w)
         cond = None
         if condition_image is not None:
             if self.controlnet is None:
                 raise ValueError("condition_image given but no controlnet was supplied")
-            cond = self._condition_rows(P, condition_image, B, S.Ks)
+            cond = self._condition_rows(P, condition_image, B, S.Ks, **({} if region_w is None else dict(copies=1 + len(cos))))
         logs = {"x0": [], "rrg_x0": [], "init_low": None, "embeds": (un, co, pun, pco)} if self.verbose else None
         self._logs = logs
         rescale = None
@@ -1375,7 +1521,7 @@ class ElasticDiffusion(nn.Module):
             mapped = score_maps is not None and i % self.log_freq == 0
             prev, x0, info = yield from self._phase_steps(P, x, i, S.R + 1, S.guidance, S.drop_p, emb, cond, direct,
                                                           None if two_phase else rrg_w, S.norm, frames, rescale, extras, ms,
-                                                          keep_scores=mapped)
+                                                          keep_scores=mapped, **rg_kw)
             if mapped:  # PCA:165-196 on the R + 1-pass direction estimate and the per-view score, before the RePaint phase
                 score_maps["pca_cls_dir"][i] = ops.score_pca(info["direction"], normalize=True, workspace=pca_ws)
                 score_maps["pca_uncond"][i] = ops.score_pca(info["local"], workspace=pca_ws)
@@ -1390,7 +1536,7 @@ class ElasticDiffusion(nn.Module):
                 x = self._undo(prev, i + 1)
                 cfg = S.guidance / 3
                 prev, x0, info = yield from self._phase_steps(P, x, i, 1, cfg, S.drop_p, emb, cond, direct, rrg_w, S.norm,
-                                                              frames, rescale, extras, ms)
+                                                              frames, rescale, extras, ms, **rg_kw)
             hist = (x0, t)
             if logs is not None:  # verbose image logs (ED:1058-1059, 1073-1076)
                 if i % self.log_freq == 0:
@@ -1431,7 +1577,7 @@ class ElasticDiffusion(nn.Module):
                          progress=_identity_progress, condition_image=None, controlnet_conditioning_scale=1.0,
                          trace=None, guidance_rescale=0.0, init_image=None, strength=1.0, mask_image=None, *, mask_blur=0.0,
                          mask_mode="binary", min_chunks=None, ip_adapter_image=None, ip_adapter_image_embeds=None,
-                         score_pca=False):
+                         score_pca=False, regions=None, region_blur=0.0):
         """``guidance_rescale`` in [0, 1] (diffusers' keyword; 0 = off): the std rescale of the guided model output of
         arXiv 2305.08891 section 3.4, what zero-terminal-SNR / v-prediction checkpoints are meant to be sampled with
         (DESIGN.md section 17).
@@ -1470,7 +1616,18 @@ class ElasticDiffusion(nn.Module):
         loop.  At every timestep index i with i % log_freq == 0 the class direction (normalised as there) and the local
         unconditional score of the timestep's first phase are projected onto their first three principal components and scaled to
         bytes on the device (``ops.score_pca``; nothing syncs); ``last_score_pca`` = {"pca_cls_dir": {i: uint8 [B, Hl, Wl, 3]},
-        "pca_uncond": {...}} afterwards.  It only reads: latents and host RNG stream are those of the run without it."""
+        "pca_uncond": {...}} afterwards.  It only reads: latents and host RNG stream are those of the run without it.
+
+        ``regions`` / ``region_blur`` (keyword-only): regional prompts.  ``regions`` = 1 to 7 entries
+        ``(prompt, mask)`` or ``(prompt, mask, weight)``; a mask is an L PIL image / uint8 [H,W] at the picture's size (reduced to the
+        latent grid on the device with Pillow's BILINEAR bytes, after a Gaussian blur of radius ``region_blur`` when that is > 0), a
+        uint8 array / tensor already at the latent's size (used as is), or a box ``(x0, y0, x1, y1)`` in pixels; ``weight`` > 0
+        (default 1) scales the region where regions overlap.  ``prompts`` is the base prompt: it fills what the regions leave
+        uncovered.  One negative prompt is shared by all rows.  Every region adds one conditional model row per resampling step and
+        sample; the host RNG stream is that of the run without regions.  ``last_region_weights`` holds the [n + 1,Hl,Wl] weights
+        (plane 0 the base prompt's) of the last run, or None."""
+        regions, region_blur = check_region_arguments(regions, height, width, self.vae_scale_factor, region_blur,
+                                                      self.unet.config.in_channels)
         self._check_ip_adapter(ip_adapter_image, ip_adapter_image_embeds)
         check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
         score_pca = check_score_pca_arguments(score_pca, self._score_channels())
@@ -1485,7 +1642,8 @@ class ElasticDiffusion(nn.Module):
         x = self._drive(self._program(S, prompts, negative_prompts, condition_image, trace, progress, direct=True,
                                       init_image=init_image, mask_image=mask_image, mask_blur=mask_blur, mask_mode=mask_mode,
                                       min_chunks=min_chunks, ip_adapter_image=ip_adapter_image,
-                                      ip_adapter_image_embeds=ip_adapter_image_embeds, score_maps=maps))
+                                      ip_adapter_image_embeds=ip_adapter_image_embeds, score_maps=maps, regions=regions,
+                                      region_blur=region_blur))
         self.last_score_pca = maps
         self.last_latents = x
         self.host_s["blocked_ahead_of_gpu"] = self._stager.waited
@@ -1502,7 +1660,8 @@ class ElasticDiffusion(nn.Module):
         """Several images of the SAME size / settings in flight at once (new; the reference has nothing like it).
 
         ``jobs`` = list of dicts {prompts, negative_prompts="", seed, condition_image=None, init_image=None,
-        mask_image=None, mask_blur=0.0, mask_mode="binary", ip_adapter_image=None, ip_adapter_image_embeds=None, score_pca=False}
+        mask_image=None, mask_blur=0.0, mask_mode="binary", ip_adapter_image=None, ip_adapter_image_embeds=None, score_pca=False,
+        regions=None, region_blur=0.0}
         (``score_pca``: that job's maps, as ``generate_latents`` makes them, in ``job_score_pca[index]``); ``strength`` is a setting of the call like the other schedule parameters, and jobs with and without
         an init image may mix (at ``strength`` 1: below it every job needs one; on a 9-channel inpainting UNet every job carries
         both ``init_image`` and ``mask_image``).  Each job is one
@@ -1525,10 +1684,12 @@ class ElasticDiffusion(nn.Module):
         for job in jobs:
             self._check_ip_adapter(job.get("ip_adapter_image"), job.get("ip_adapter_image_embeds"))
         n_chunks = None
-        for job in jobs:
+        job_regions = [check_region_arguments(job.get("regions"), height, width, self.vae_scale_factor, job.get("region_blur", 0.0),
+                                              self.unet.config.in_channels) for job in jobs]
+        for job, (rg, _) in zip(jobs, job_regions):
             n = self._prompt_chunks(job["prompts"], job.get("negative_prompts", ""))
             if n is not None:
-                n_chunks = max(n_chunks or 1, n)
+                n_chunks = max(n_chunks or 1, n, *([self.text_encoder.chunks([q for q, _, _ in rg])] if rg else []))
         for job in jobs:
             check_img2img_arguments(num_inference_steps, job.get("init_image"), strength, job.get("mask_image"))
             check_score_pca_arguments(job.get("score_pca", False), self._score_channels())
@@ -1570,7 +1731,8 @@ class ElasticDiffusion(nn.Module):
                                  mask_image=job.get("mask_image"), mask_blur=float(job.get("mask_blur", 0.0)),
                                  mask_mode=job.get("mask_mode", "binary"), min_chunks=n_chunks,
                                  ip_adapter_image=job.get("ip_adapter_image"),
-                                 ip_adapter_image_embeds=job.get("ip_adapter_image_embeds"), score_maps=self.job_score_pca.get(j))
+                                 ip_adapter_image_embeds=job.get("ip_adapter_image_embeds"), score_maps=self.job_score_pca.get(j),
+                                 regions=job_regions[j][0], region_blur=job_regions[j][1])
             with rng:
                 call = next(prog)
             live.append([j, prog, rng, call])
@@ -1637,7 +1799,8 @@ class ElasticDiffusion(nn.Module):
 
     @_on_own_device
     @torch.no_grad()
-    def generate(self, latent, text_embeds, add_text_embeds, guidance_scale=7.5, guidance_rescale=0.0, score_pca=False):
+    def generate(self, latent, text_embeds, add_text_embeds, guidance_scale=7.5, guidance_rescale=0.0, score_pca=False, *,
+                 regions=None):
         """ED:761-796: plain CFG + DDIM generation of ``latent`` (B,C,h,w; the reference calls it on the initial
         reduced-resolution latent for its ``verbose`` image log) over the scheduler's current timesteps.
         ``text_embeds`` / ``add_text_embeds`` = cat([uncond, cond]) like the reference's.  A latent smaller than the
@@ -1648,6 +1811,9 @@ class ElasticDiffusion(nn.Module):
         cond - uncond (normalised as there) and of uncond are added to the info dict, {"pca_cls_dir": {i: uint8 [B,h,w,3] on the
         device}, "pca_uncond": {...}}.
         -> (PIL image of the first sample, {"inter_x0": [pred_original_sample every log_freq steps]})"""
+        if regions is not None:
+            raise ValueError("regions are not supported by generate(), the base-resolution loop: it has no resampling rows to carry "
+                             "them; use generate_image / generate_latents")
         ops.rescale_coefficients(guidance_rescale)
         if self.unet.config.in_channels != 4:
             raise ValueError("generate() drives a 4-channel UNet: a bare latent has no mask or masked-image rows")
@@ -1772,7 +1938,7 @@ class ElasticDiffusion(nn.Module):
                        progress=_default_progress, tiled_decoder=False, grid=False, guidance_rescale=0.0, *,
                        condition_image=None, controlnet_conditioning_scale=1.0, output_type="pil", init_image=None,
                        strength=1.0, mask_image=None, mask_blur=0.0, mask_mode="binary", composite=False,
-                       ip_adapter_image=None, ip_adapter_image_embeds=None, score_pca=False):
+                       ip_adapter_image=None, ip_adapter_image_embeds=None, score_pca=False, regions=None, region_blur=0.0):
         """ED:953-965 signature (ControlNet keywords of EDC:1120-1134 are keyword-only here), then ``guidance_rescale``
         (diffusers' keyword) and, keyword-only, ``init_image`` / ``strength`` / ``mask_image`` / ``mask_blur`` / ``mask_mode``
         (see ``generate_latents``) and ``composite``: paste every decoded picture over the 8-bit init picture through the
@@ -1781,7 +1947,9 @@ class ElasticDiffusion(nn.Module):
         ``ip_adapter_image`` / ``ip_adapter_image_embeds``: the image prompt of a loaded IP-Adapter (see ``generate_latents``).
         ``score_pca``: the PCA maps of ``generate_latents``, the first sample's enlarged by the VAE factor with Pillow's BILINEAR bytes
         on the device, in ``image_log`` as {"pca_cls_dir": {i: PIL}, "pca_uncond": {i: PIL}} (the script's pictures and names).
+        ``regions`` / ``region_blur``: regional prompts (see ``generate_latents``).
         Returns ``(images, image_log)``; images are PIL by default, a float tensor with ``output_type='pt'``."""
+        check_region_arguments(regions, height, width, self.vae_scale_factor, region_blur, self.unet.config.in_channels)
         self._check_ip_adapter(ip_adapter_image, ip_adapter_image_embeds)
         check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
         check_soft_inpaint_arguments(init_image, mask_image, mask_blur, mask_mode, composite, output_type, grid,
@@ -1793,7 +1961,7 @@ class ElasticDiffusion(nn.Module):
                                   controlnet_conditioning_scale, guidance_rescale=guidance_rescale, init_image=init_image,
                                   strength=strength, mask_image=mask_image, mask_blur=mask_blur, mask_mode=mask_mode,
                                   ip_adapter_image=ip_adapter_image, ip_adapter_image_embeds=ip_adapter_image_embeds,
-                                  score_pca=score_pca)
+                                  score_pca=score_pca, regions=regions, region_blur=region_blur)
         dec = self.tiled_decode if tiled_decoder else self.decode_latents
         image_log = self._image_log(dec, guidance_scale, guidance_rescale) if self.verbose else {}  # ED:1092-1118 (before the final decode)
         if score_pca:
@@ -1983,7 +2151,9 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
                        rrg_scherduler_cls=CosineScheduler, cosine_scale=3.0, repaint_sampling=True,
                        progress=_default_progress, tiled_decoder=False, grid=False, guidance_rescale=0.0, *,
                        output_type="pil", init_image=None, strength=1.0, mask_image=None, mask_blur=0.0, mask_mode="binary",
-                       composite=False, ip_adapter_image=None, ip_adapter_image_embeds=None, score_pca=False):
+                       composite=False, ip_adapter_image=None, ip_adapter_image_embeds=None, score_pca=False, regions=None,
+                       region_blur=0.0):
+        check_region_arguments(regions, height, width, self.vae_scale_factor, region_blur, self.unet.config.in_channels)
         self._check_ip_adapter(ip_adapter_image, ip_adapter_image_embeds)
         check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
         check_soft_inpaint_arguments(init_image, mask_image, mask_blur, mask_mode, composite, output_type, grid,
@@ -2001,4 +2171,4 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
                                       output_type=output_type, init_image=init_image, strength=strength,
                                       mask_image=mask_image, mask_blur=mask_blur, mask_mode=mask_mode, composite=composite,
                                       ip_adapter_image=ip_adapter_image, ip_adapter_image_embeds=ip_adapter_image_embeds,
-                                      score_pca=score_pca)
+                                      score_pca=score_pca, regions=regions, region_blur=region_blur)

@@ -469,6 +469,60 @@ int ed_phase_epilogue_ms(const void* g_out, const void* v_out, int dtype, const 
                          const float* ratio_low, float gr, float omgr, const float* x0_hist, void* stream);
 
 /*
+ * Regional prompts: P = n + 1 conditional rows per resampling step and sample -- the base prompt and n
+ * regions, 1 <= P <= 8 -- whose class directions cond_p - uncond are summed per pixel with the weights region_w f32 [P,H,W].
+ * Model rows are step-major: [(K*(1+P)*B),C,gPH,gPW], within a step uncond first, then cond 0..P-1, each x B.  Additions, no
+ * signature change: still ABI v13.  Every entry point below returns hipErrorInvalidValue before any launch for P (n + 1; copies - 1)
+ * outside 1..8, for a NULL region_w with P > 1 and for a region_w that shares memory with an output.
+ *
+ * ed_region_weights -- masks u8 [n,HW] (255 = the region) and weights (a HOST array of n floats, each > 0) -> region_w f32 [n+1,HW],
+ * plane 0 the base prompt's.  Per pixel, in fp32, each operation rounded on its own:
+ *     r_p = weight_p * (m_p / 255),  s = r_1 + .. + r_n (in order),  r_0 = max(0, 1 - s),  tot = r_0 + s,  w_p = r_p / tot.
+ * One launch; 4 pixels per thread when HW % 4 == 0 and the buffers allow, the same bits as the scalar form.
+ *
+ * ed_assemble_rows_n -- ed_assemble_rows_x with `copies` (2..9) rows written per resampling step and sample in the place of the fixed
+ * 2: g_rows [(K*copies*B),C+E,gPH,gPW].  extra / pad_value may be NULL with E = 0.  The picked vector is gathered once and stored
+ * `copies` times; copies = 2 gives the bits of ed_assemble_rows (E = 0) / ed_assemble_rows_x.
+ *
+ * ed_region_blend -- the un-fused path: out f32 [planes,HW] = sum_p region_w[p,HW] * dirs[p,planes,HW] (dirs f32, the P directions
+ * of ed_unpad_direction + ed_fill_directions on the (uncond, cond_p) pair rows), with the rule of the fused kernels: a term whose
+ * weight is 0 is skipped (its direction is not read), the first term that is not starts the sum, the rest are added in order of p;
+ * 0 where every weight is 0.
+ *
+ * ed_phase_epilogue_rg -- ed_phase_epilogue_ms' argument list, then `multistep` (1: the DPM-Solver++ update as there; 0: the DDIM
+ * update of ed_phase_epilogue_gr, with sqrt_alpha_prev / sqrt_1m_alpha_prev in the places of c_x / b and half_b, r_inv, x0_hist
+ * unused -- x0_hist must be NULL), then region_w and P.  The direction of a pixel is the weighted sum above over the P cond rows of
+ * its covering step (zero-weight rows are not read); everything else -- low_dir at (down_row, down_col), the rescale, the update,
+ * the fused RRG term, the by-products -- is ed_phase_epilogue_ms' with that direction.  One launch.  A NULL region_w with P = 1
+ * launches exactly what ed_phase_epilogue_ms / ed_phase_epilogue_gr launch.
+ *
+ * ed_phase_moments_rg -- ed_phase_moments over the same regional direction; a NULL region_w with P = 1 is ed_phase_moments.
+ */
+int ed_region_weights(const uint8_t* masks, const float* weights, int n, int64_t HW, float* region_w, void* stream);
+int ed_assemble_rows_n(const float* latent, int B, int C, int H, int W, const uint8_t* idx, const int32_t* src_row,
+                       const int32_t* src_col, const float* gframe, void* g_rows, float* low, int K, int h, int w, int gPH,
+                       int gPW, int g_off_y, int g_off_x, const int32_t* win_y0, const int32_t* win_x0,
+                       const float* vframe, void* v_rows, int V, int Sh, int Sw, int vPH, int vPW, int v_off_y, int v_off_x,
+                       int dtype, const float* extra, int E, const float* pad_value, int copies, void* stream);
+int ed_region_blend(const float* dirs, const float* region_w, float* out, int P, int planes, int64_t HW, void* stream);
+int ed_phase_epilogue_rg(const void* g_out, const void* v_out, int dtype, const float* x, const int8_t* stamp,
+                         const int32_t* inv_row, const int32_t* inv_col, const int32_t* up_row, const int32_t* up_col,
+                         const int32_t* down_row, const int32_t* down_col, const int32_t* row_blk, const int32_t* row_src,
+                         const int32_t* col_blk, const int32_t* col_src, const float* low_latent, float* prev, float* x0,
+                         float* x_next, float* low_dir, float* uncond_last, float* direction, float* local, int K, int B,
+                         int C, int H, int W, int h, int w, int gPH, int gPW, int g_off_y, int g_off_x, int vPH, int vPW,
+                         int n_col_blocks, float g, float sqrt_beta_t, float sqrt_alpha_t, float c_x, float b, float half_b,
+                         float r_inv, float rrg_norm, float rrg_weight, int prediction_type, const float* ratio,
+                         const float* ratio_low, float gr, float omgr, const float* x0_hist, int multistep,
+                         const float* region_w, int P, void* stream);
+int ed_phase_moments_rg(const void* g_out, const void* v_out, int dtype, const int8_t* stamp, const int32_t* inv_row,
+                        const int32_t* inv_col, const int32_t* up_row, const int32_t* up_col, const int32_t* down_row,
+                        const int32_t* down_col, const int32_t* row_blk, const int32_t* row_src, const int32_t* col_blk,
+                        const int32_t* col_src, float* ratio, float* ratio_low, void* workspace, int K, int B, int C, int H,
+                        int W, int h, int w, int gPH, int gPW, int g_off_y, int g_off_x, int vPH, int vPW, int n_col_blocks,
+                        float g, const float* region_w, int P, void* stream);
+
+/*
  * ed_flash_attention -- fused attention forward of the UNet's transformer blocks (what diffusers' AttnProcessor2_0
  * does with F.scaled_dot_product_attention inside `self.unet(...)`, ED:422-426): out = softmax(scale * Q K^T) V per
  * (batch, head), never materialising the Nq x Nk score matrix.  MFMA 32x32x16 (bf16 / f16), online softmax in fp32.
