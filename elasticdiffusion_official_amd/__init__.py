@@ -68,7 +68,7 @@ if "MIOPEN_USER_DB_PATH" not in _os.environ or "MIOPEN_CUSTOM_CACHE_DIR" not in 
     _os.environ.setdefault("MIOPEN_USER_DB_PATH", _MIOPEN_DIR)
     _os.environ.setdefault("MIOPEN_CUSTOM_CACHE_DIR", _MIOPEN_DIR)
 
-from .schedule import ConstScheduler, CosineScheduler, DDIMSchedule, DPMSolverSchedule, LinearScheduler  # noqa: F401
+from .schedule import ConstScheduler, CosineScheduler, DDIMSchedule, DPMSolverSchedule, LCMSchedule, LinearScheduler  # noqa: F401
 
 
 def __getattr__(name):  # lazy: importing the package must not require a GPU (build check, CPU host-logic tests)

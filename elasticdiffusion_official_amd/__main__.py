@@ -14,7 +14,8 @@ extracted condition as ``condition.png``.  ``--prediction_type``, ``--timestep_s
 ``--rescale_betas_zero_snr`` override what the snapshot's ``scheduler/scheduler_config.json`` says (or the SD defaults
 without ``--weights``); the reference takes these from the hub config only.  ``--guidance_rescale`` is diffusers' keyword of
 that name (0 = off), what such checkpoints are meant to be sampled with.  ``--sampler dpmsolver++`` (``--solver_order`` 1 / 2) samples with
-DPM-Solver++(2M) instead of DDIM on the same timestep grid.  ``--init_image FILE`` with ``--strength`` (and
+DPM-Solver++(2M) instead of DDIM on the same timestep grid; ``--eta`` (DDIM), ``--sampler euler_a`` /
+``dpmsolver++sde`` / ``lcm`` are the stochastic samplers of section 29 (one host noise draw per phase).  ``--init_image FILE`` with ``--strength`` (and
 ``--mask_image FILE``: white = repaint, black = keep) is image-to-image / inpainting with diffusers' semantics; the picture is
 resized to H x W with Pillow's Lanczos filter, a mask of the picture's size with NEAREST.  ``--mask_blur R`` feathers the mask with
 Pillow's ``GaussianBlur(R)`` on the device, ``--mask_mode graded`` reads the grey levels as release times, ``--composite`` pastes
@@ -94,10 +95,13 @@ def build_parser():
     ap.add_argument("--guidance_rescale", type=float, default=0.0,
                     help="std rescale of the guided prediction in [0, 1] (arXiv 2305.08891 section 3.4; diffusers' "
                     "guidance_rescale), for zero-terminal-SNR / v-prediction checkpoints; 0 = off")
-    ap.add_argument("--sampler", type=str, default="ddim", choices=["ddim", "dpmsolver++"],
+    ap.add_argument("--sampler", type=str, default="ddim", choices=["ddim", "euler_a", "dpmsolver++", "dpmsolver++sde", "lcm"],
                     help="ddim: the reference's first-order sampler; dpmsolver++: DPM-Solver++(2M), the multistep solver meant "
-                    "for 20-25 step images (no extra model call per step)")
-    ap.add_argument("--solver_order", type=int, default=2, choices=[1, 2], help="order of --sampler dpmsolver++")
+                    "for 20-25 step images (no extra model call per step); euler_a: the ancestral step (DDIM at eta = 1) on "
+                    "the same timestep grid; dpmsolver++sde: SDE-DPM-Solver++(2M); lcm: the scheduler of an LCM-LoRA (4-8 steps)")
+    ap.add_argument("--solver_order", type=int, default=2, choices=[1, 2], help="order of --sampler dpmsolver++ / dpmsolver++sde")
+    ap.add_argument("--eta", type=float, default=0.0, help="eta of --sampler ddim in [0, 1]: 0 = deterministic (default), 1 = the "
+                    "ancestral step; every stochastic step draws one latent-sized noise sample on the host")
     ap.add_argument("--init_image", type=str, default=None, help="start from this picture instead of pure noise "
                     "(image-to-image; resized to H x W)")
     ap.add_argument("--strength", type=float, default=1.0, help="fraction of the schedule an --init_image run executes, in "
@@ -271,13 +275,12 @@ def main(argv=None):
     sched = dict(prediction_type=opt.prediction_type, timestep_spacing=opt.timestep_spacing,
                  rescale_betas_zero_snr=opt.rescale_betas_zero_snr)
     if any(v is not None for v in sched.values()):  # a given flag overrides the snapshot's value / the default
+        from .pipeline import check_sampler_arguments, make_scheduler
         from .schedule import DDIMSchedule
-        kw["scheduler"] = DDIMSchedule.from_config_dir(opt.weights, **sched)
-        if opt.sampler == "dpmsolver++":
-            from .schedule import DPMSolverSchedule
-            kw["scheduler"] = DPMSolverSchedule(**vars(kw["scheduler"].config), solver_order=opt.solver_order)
-    elif opt.sampler != "ddim":
-        kw.update(sampler=opt.sampler, solver_order=opt.solver_order)
+        check_sampler_arguments(opt.sampler, opt.solver_order, None, opt.eta)
+        kw["scheduler"] = make_scheduler(DDIMSchedule.from_config_dir(opt.weights, **sched), opt.sampler, opt.solver_order, opt.eta)
+    elif opt.sampler != "ddim" or opt.eta != 0.0:
+        kw.update(sampler=opt.sampler, solver_order=opt.solver_order, eta=opt.eta)
     extra = {}
     if opt.condition_image:
         from PIL import Image

@@ -116,6 +116,10 @@ SIGNATURES = {
     "ed_phase_epilogue_ms": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                              _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f,
                              _f, _f, _f, _f, _i, _vp, _vp, _f, _f, _vp, _vp],
+    "ed_cfg_ddim_step_sde": [_vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _f, _i64, _i, _vp, _f, _f, _i, _vp, _i, _f, _vp, _vp],
+    "ed_phase_epilogue_sde": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                              _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f,
+                              _f, _f, _f, _f, _i, _vp, _vp, _f, _f, _vp, _i, _f, _vp, _vp],
     "ed_region_weights": [_vp, _vp, _i, _i64, _vp, _vp],
     "ed_assemble_rows_n": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp,
                            _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp],

@@ -486,52 +486,79 @@ struct Multistep {
   float hb, r_inv;
 };
 
-template <bool VP, bool GR = false, int ST = ST_DDIM>
+// The noise variant (compile-time, orthogonal to ST): the stochastic samplers -- DDIM with eta > 0, SDE-DPM-Solver++
+// (2M), LCM -- are the deterministic update with other host scalars plus c_n * noise, `noise` one more fp32 operand at the output
+// element's index (drawn on the host in the reference's order):   prev = prev + c_n * noise,   the product rounded on its own.  The
+// <.., false> instantiations are the code they were before the variant existed; their argument blocks keep their types.
+struct MultistepNZ : Multistep {
+  const float* noise;
+  float c_n;
+};
+template <bool NZ> struct MultistepOf { typedef Multistep type; };
+template <> struct MultistepOf<true> { typedef MultistepNZ type; };
+
+template <bool VP, bool GR = false, int ST = ST_DDIM, bool NZ = false>
 __device__ __forceinline__ void ddim_one(float l, float d, float xv, float g, float sb, float sa, float sp, float sd,
                                          float& prev, float& x0, float r = 0.0f, float gr = 0.0f, float omgr = 0.0f,
-                                         float x0h = 0.0f, float hb = 0.0f, float r_inv = 0.0f) {
+                                         float x0h = 0.0f, float hb = 0.0f, float r_inv = 0.0f, float c_n = 0.0f,
+                                         float nz = 0.0f) {
   float m = rescaled<GR>(__fadd_rn(l, __fmul_rn(g, d)), r, gr, omgr);
   x0 = pred_x0<VP>(m, xv, sb, sa);
   if (ST != ST_DDIM) {
     prev = __fsub_rn(__fmul_rn(sp, xv), __fmul_rn(sd, x0));
     if (ST == ST_MS2) prev = __fsub_rn(prev, __fmul_rn(hb, __fmul_rn(r_inv, __fsub_rn(x0, x0h))));
+    if (NZ) prev = __fadd_rn(prev, __fmul_rn(c_n, nz));
     return;
   }
   float eps = VP ? __fadd_rn(__fmul_rn(sa, m), __fmul_rn(sb, xv)) : m;
   prev = __fadd_rn(__fmul_rn(sp, x0), __fmul_rn(sd, eps));
+  if (NZ) prev = __fadd_rn(prev, __fmul_rn(c_n, nz));
 }
 
 // The <VP, true> instantiation is only launched with rs.per % 4 == 0 (cfg_ddim_x4), so the 4 elements of a thread belong to
 // one sample; <VP, false> never reads rs.
-template <bool VP, bool GR = false, int ST = ST_DDIM>
+template <bool VP, bool GR = false, int ST = ST_DDIM, bool NZ = false>
 __global__ void __launch_bounds__(ED_BLOCK)
 k_cfg_ddim_v4(const float4* __restrict__ local, const float4* __restrict__ dir, const float4* __restrict__ x,
               float4* __restrict__ prev, float4* __restrict__ x0, float g, float sb, float sa, float sp, float sd,
-              int64_t n4, const Rescale rs, const Multistep ms) {
+              int64_t n4, const Rescale rs, const typename MultistepOf<NZ>::type ms) {
   int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
   if (t >= n4) return;
   float4 l = local[t], d = dir[t], xv = x[t], p, o;
   const float r = GR ? rs.ratio[(t << 2) / rs.per] : 0.0f;
   float4 hx = {0.0f, 0.0f, 0.0f, 0.0f};
   if (ST == ST_MS2) hx = ((const float4*)ms.x0_hist)[t];
-  ddim_one<VP, GR, ST>(l.x, d.x, xv.x, g, sb, sa, sp, sd, p.x, o.x, r, rs.gr, rs.omgr, hx.x, ms.hb, ms.r_inv);
-  ddim_one<VP, GR, ST>(l.y, d.y, xv.y, g, sb, sa, sp, sd, p.y, o.y, r, rs.gr, rs.omgr, hx.y, ms.hb, ms.r_inv);
-  ddim_one<VP, GR, ST>(l.z, d.z, xv.z, g, sb, sa, sp, sd, p.z, o.z, r, rs.gr, rs.omgr, hx.z, ms.hb, ms.r_inv);
-  ddim_one<VP, GR, ST>(l.w, d.w, xv.w, g, sb, sa, sp, sd, p.w, o.w, r, rs.gr, rs.omgr, hx.w, ms.hb, ms.r_inv);
+  if constexpr (NZ) {
+    const float4 nz = ((const float4*)ms.noise)[t];
+    ddim_one<VP, GR, ST, true>(l.x, d.x, xv.x, g, sb, sa, sp, sd, p.x, o.x, r, rs.gr, rs.omgr, hx.x, ms.hb, ms.r_inv, ms.c_n, nz.x);
+    ddim_one<VP, GR, ST, true>(l.y, d.y, xv.y, g, sb, sa, sp, sd, p.y, o.y, r, rs.gr, rs.omgr, hx.y, ms.hb, ms.r_inv, ms.c_n, nz.y);
+    ddim_one<VP, GR, ST, true>(l.z, d.z, xv.z, g, sb, sa, sp, sd, p.z, o.z, r, rs.gr, rs.omgr, hx.z, ms.hb, ms.r_inv, ms.c_n, nz.z);
+    ddim_one<VP, GR, ST, true>(l.w, d.w, xv.w, g, sb, sa, sp, sd, p.w, o.w, r, rs.gr, rs.omgr, hx.w, ms.hb, ms.r_inv, ms.c_n, nz.w);
+  } else {
+    ddim_one<VP, GR, ST>(l.x, d.x, xv.x, g, sb, sa, sp, sd, p.x, o.x, r, rs.gr, rs.omgr, hx.x, ms.hb, ms.r_inv);
+    ddim_one<VP, GR, ST>(l.y, d.y, xv.y, g, sb, sa, sp, sd, p.y, o.y, r, rs.gr, rs.omgr, hx.y, ms.hb, ms.r_inv);
+    ddim_one<VP, GR, ST>(l.z, d.z, xv.z, g, sb, sa, sp, sd, p.z, o.z, r, rs.gr, rs.omgr, hx.z, ms.hb, ms.r_inv);
+    ddim_one<VP, GR, ST>(l.w, d.w, xv.w, g, sb, sa, sp, sd, p.w, o.w, r, rs.gr, rs.omgr, hx.w, ms.hb, ms.r_inv);
+  }
   prev[t] = p;
   x0[t] = o;
 }
 
-template <bool VP, bool GR = false, int ST = ST_DDIM>
+template <bool VP, bool GR = false, int ST = ST_DDIM, bool NZ = false>
 __global__ void __launch_bounds__(ED_BLOCK)
 k_cfg_ddim_s(const float* __restrict__ local, const float* __restrict__ dir, const float* __restrict__ x,
              float* __restrict__ prev, float* __restrict__ x0, float g, float sb, float sa, float sp, float sd,
-             int64_t n, const Rescale rs, const Multistep ms) {
+             int64_t n, const Rescale rs, const typename MultistepOf<NZ>::type ms) {
   int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
   if (t >= n) return;
   float p, o;
-  ddim_one<VP, GR, ST>(local[t], dir[t], x[t], g, sb, sa, sp, sd, p, o, GR ? rs.ratio[t / rs.per] : 0.0f, rs.gr, rs.omgr,
-                       ST == ST_MS2 ? ms.x0_hist[t] : 0.0f, ms.hb, ms.r_inv);
+  if constexpr (NZ) {
+    ddim_one<VP, GR, ST, true>(local[t], dir[t], x[t], g, sb, sa, sp, sd, p, o, GR ? rs.ratio[t / rs.per] : 0.0f, rs.gr, rs.omgr,
+                               ST == ST_MS2 ? ms.x0_hist[t] : 0.0f, ms.hb, ms.r_inv, ms.c_n, ms.noise[t]);
+  } else {
+    ddim_one<VP, GR, ST>(local[t], dir[t], x[t], g, sb, sa, sp, sd, p, o, GR ? rs.ratio[t / rs.per] : 0.0f, rs.gr, rs.omgr,
+                         ST == ST_MS2 ? ms.x0_hist[t] : 0.0f, ms.hb, ms.r_inv);
+  }
   prev[t] = p;
   x0[t] = o;
 }
@@ -663,8 +690,14 @@ struct EpilogueArgsMS : EpilogueArgs {
   const float* x0_hist;
   float hb, r_inv;
 };
-template <int ST> struct EpilogueArgsOf { typedef EpilogueArgsMS type; };
-template <> struct EpilogueArgsOf<ST_DDIM> { typedef EpilogueArgs type; };
+// ... and of the noise variants (section 29), for every ST: again a type of its own.
+struct EpilogueArgsNZ : EpilogueArgsMS {
+  const float* noise;  // [B,C,H,W]
+  float c_n;
+};
+template <int ST, bool NZ = false> struct EpilogueArgsOf { typedef EpilogueArgsMS type; };
+template <> struct EpilogueArgsOf<ST_DDIM, false> { typedef EpilogueArgs type; };
+template <int ST> struct EpilogueArgsOf<ST, true> { typedef EpilogueArgsNZ type; };
 
 template <typename Tag>
 __device__ __forceinline__ float direction_at(const EpilogueArgs& a, int b, int c, int Y, int X) {
@@ -707,9 +740,9 @@ __device__ __forceinline__ float uncond_last_at(const EpilogueArgs& a, int b, in
   return ld<Tag>(a.g_out, (((int64_t)(a.K - 1) * 2 + 0) * a.B + b) * a.C * plane + e);
 }
 
-template <typename Tag, bool VP, bool GR = false, int ST = ST_DDIM>
+template <typename Tag, bool VP, bool GR = false, int ST = ST_DDIM, bool NZ = false>
 __global__ void __launch_bounds__(ED_BLOCK)
-k_phase_epilogue(const typename EpilogueArgsOf<ST>::type a) {
+k_phase_epilogue(const typename EpilogueArgsOf<ST, NZ>::type a) {
   const int64_t nfull = (int64_t)a.B * a.C * a.H * a.W;
   const int64_t nlow = (int64_t)a.B * a.C * a.h * a.w;
   int64_t t = (int64_t)blockIdx.x * ED_BLOCK + threadIdx.x;
@@ -735,7 +768,12 @@ k_phase_epilogue(const typename EpilogueArgsOf<ST>::type a) {
   float loc = local_at<Tag>(a, b, c, Y, X);
   float d = direction_at<Tag>(a, b, c, Y, X);
   float pv, z0;
-  if constexpr (ST == ST_DDIM) {
+  if constexpr (NZ) {  // x_next below is formed from the prev that carries the noise
+    float x0h = 0.0f;
+    if constexpr (ST == ST_MS2) x0h = a.x0_hist[t];
+    ddim_one<VP, GR, ST, true>(loc, d, a.x[t], a.g, a.sb, a.sa, a.sp, a.sd, pv, z0, GR ? a.ratio[b] : 0.0f, a.gr, a.omgr, x0h, a.hb,
+                               a.r_inv, a.c_n, a.noise[t]);
+  } else if constexpr (ST == ST_DDIM) {
     ddim_one<VP, GR>(loc, d, a.x[t], a.g, a.sb, a.sa, a.sp, a.sd, pv, z0, GR ? a.ratio[b] : 0.0f, a.gr, a.omgr);
   } else {
     float x0h = 0.0f;
@@ -1663,6 +1701,17 @@ static inline bool hist_overlaps(const float* x0_hist, const float* prev, const 
   return (h < p + bytes && p < h + bytes) || (h < o + bytes && o < h + bytes);
 }
 
+// The noise operand of the stochastic samplers (section 29) and its scalar, as the *_sde entry points take them.
+struct Noise {
+  const float* noise;
+  float c_n;
+};
+
+// does the noise [noise, noise + n) share an element with an output of the step (x_next may be NULL)?
+static inline bool noise_overlaps(const float* noise, const float* prev, const float* x0, const float* x_next, int64_t n) {
+  return hist_overlaps(noise, prev, x0, n) || (x_next && hist_overlaps(noise, x_next, x_next, n));
+}
+
 static int phase_epilogue_launch(bool vp, const void* g_out, const void* v_out, int dtype, const float* x, const int8_t* stamp,
                       const int32_t* inv_row, const int32_t* inv_col, const int32_t* up_row, const int32_t* up_col,
                       const int32_t* down_row, const int32_t* down_col, const int32_t* row_blk, const int32_t* row_src,
@@ -1672,13 +1721,15 @@ static int phase_epilogue_launch(bool vp, const void* g_out, const void* v_out, 
                       int n_col_blocks, float g, float sqrt_beta_t, float sqrt_alpha_t, float sqrt_alpha_prev,
                       float sqrt_1m_alpha_prev, float rrg_norm, float rrg_weight, void* stream,
                       const float* ratio = nullptr, const float* ratio_low = nullptr, float gr = 0.0f, float omgr = 0.0f,
-                      const Multistep* ms = nullptr) {
+                      const Multistep* ms = nullptr, const Noise* nz = nullptr) {
   int64_t n = (int64_t)B * C * H * W + (int64_t)B * C * h * w;
   if ((int64_t)B * C * H * W == 0) return 0;
   if (x_next && !low_latent) return (int)hipErrorInvalidValue;
   if (ratio && x_next && !ratio_low) return (int)hipErrorInvalidValue;
   if (ms && hist_overlaps(ms->x0_hist, prev, x0, (int64_t)B * C * H * W)) return (int)hipErrorInvalidValue;
-  EpilogueArgsMS a;  // launched as its EpilogueArgs base without `ms`
+  if (nz && noise_overlaps(nz->noise, prev, x0, x_next, (int64_t)B * C * H * W)) return (int)hipErrorInvalidValue;
+  EpilogueArgsNZ a;  // launched as its EpilogueArgsMS base without `nz`, as its EpilogueArgs base without `ms` either
+  a.noise = nz ? nz->noise : nullptr, a.c_n = nz ? nz->c_n : 0.0f;
   a.ratio = ratio, a.ratio_low = ratio_low, a.gr = gr, a.omgr = omgr;
   a.x0_hist = ms ? ms->x0_hist : nullptr, a.hb = ms ? ms->hb : 0.0f, a.r_inv = ms ? ms->r_inv : 0.0f;
   a.g_out = g_out, a.v_out = v_out, a.x = x, a.stamp = stamp;
@@ -1690,6 +1741,25 @@ static int phase_epilogue_launch(bool vp, const void* g_out, const void* v_out, 
   a.g_off_x = g_off_x, a.vPH = vPH, a.vPW = vPW, a.ncb = n_col_blocks;
   a.g = g, a.sb = sqrt_beta_t, a.sa = sqrt_alpha_t, a.sp = sqrt_alpha_prev, a.sd = sqrt_1m_alpha_prev;
   a.rrg_norm = rrg_norm, a.rrg_weight = rrg_weight;
+  // the noise variants (section 29): the same choice of ST, <.., true>; without `nz` nothing below changed
+#define ED_EPI_NZ(T, ST)                                                                                            \
+  if (ratio && vp) k_phase_epilogue<T, true, true, ST, true><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(a);  \
+  else if (ratio) k_phase_epilogue<T, false, true, ST, true><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(a);  \
+  else if (vp) k_phase_epilogue<T, true, false, ST, true><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(a);     \
+  else k_phase_epilogue<T, false, false, ST, true><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(a);
+#define ED_EPI_NZ_T(ST)                        \
+  switch (dtype) {                             \
+    case ED_F32: ED_EPI_NZ(F32, ST) break;     \
+    case ED_F16: ED_EPI_NZ(F16, ST) break;     \
+    case ED_BF16: ED_EPI_NZ(BF16, ST) break;   \
+    default: return (int)hipErrorInvalidValue; \
+  }
+  if (nz) {
+    if (!ms) { ED_EPI_NZ_T(ST_DDIM) } else if (ms->x0_hist) { ED_EPI_NZ_T(ST_MS2) } else { ED_EPI_NZ_T(ST_MS1) }
+    return done();
+  }
+#undef ED_EPI_NZ_T
+#undef ED_EPI_NZ
   // the multistep variants: <.., ST_MS2> when a history is given, <.., ST_MS1> otherwise (sqrt_alpha_prev / sqrt_1m_alpha_prev
   // carry c_x / b); without `ms` the launches below are the ones there always were
 #define ED_EPI_MS(T, ST)                                                                                       \
@@ -1838,6 +1908,38 @@ static int cfg_ms_launch(bool vp, const float* local, const float* direction, co
   ED_LAUNCH_MS(vp, rs.ratio, ST, k_cfg_ddim_s, n, local, direction, x, prev, x0, g, sqrt_beta_t, sqrt_alpha_t, c_x, b, n, rs, ms)
     if (ms.x0_hist) ED_MS_S(ST_MS2); else ED_MS_S(ST_MS1);
 #undef ED_MS_S
+  }
+  return done();
+}
+
+// The noise launch (section 29): `st` is ST_DDIM (sp / sd = sqrt(abar_prev) / sd_eta) or ST_MS1 / ST_MS2 as cfg_ms_launch chooses them.
+// The 16-byte form under cfg_ms_x4's conditions and an aligned noise; the scalar form otherwise.
+#define ED_LAUNCH_NZ(vp, gr, ST, KERNEL, n, ...)                                                                     \
+  do {                                                                                                               \
+    if ((gr) && (vp)) KERNEL<true, true, ST, true><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(__VA_ARGS__);   \
+    else if (gr) KERNEL<false, true, ST, true><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(__VA_ARGS__);       \
+    else if (vp) KERNEL<true, false, ST, true><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(__VA_ARGS__);       \
+    else KERNEL<false, false, ST, true><<<grid_for(n), ED_BLOCK, 0, (hipStream_t)stream>>>(__VA_ARGS__);              \
+  } while (0)
+
+static int cfg_nz_launch(bool vp, int st, const float* local, const float* direction, const float* x, float* prev, float* x0,
+                         float g, float sqrt_beta_t, float sqrt_alpha_t, float sp, float sd, int64_t n, void* stream,
+                         const Rescale rs, const Multistep ms, const Noise nz) {
+  if (n == 0) return 0;
+  if (hist_overlaps(ms.x0_hist, prev, x0, n) || noise_overlaps(nz.noise, prev, x0, nullptr, n)) return (int)hipErrorInvalidValue;
+  MultistepNZ a;
+  a.x0_hist = ms.x0_hist, a.hb = ms.hb, a.r_inv = ms.r_inv, a.noise = nz.noise, a.c_n = nz.c_n;
+  if (cfg_ms_x4(local, direction, x, prev, x0, n, rs, ms.x0_hist) && aligned16(nz.noise)) {
+#define ED_NZ_V4(ST)                                                                                                       \
+  ED_LAUNCH_NZ(vp, rs.ratio, ST, k_cfg_ddim_v4, n / 4, (const float4*)local, (const float4*)direction, (const float4*)x, \
+               (float4*)prev, (float4*)x0, g, sqrt_beta_t, sqrt_alpha_t, sp, sd, n / 4, rs, a)
+    if (st == ST_DDIM) ED_NZ_V4(ST_DDIM); else if (st == ST_MS2) ED_NZ_V4(ST_MS2); else ED_NZ_V4(ST_MS1);
+#undef ED_NZ_V4
+  } else {
+#define ED_NZ_S(ST) \
+  ED_LAUNCH_NZ(vp, rs.ratio, ST, k_cfg_ddim_s, n, local, direction, x, prev, x0, g, sqrt_beta_t, sqrt_alpha_t, sp, sd, n, rs, a)
+    if (st == ST_DDIM) ED_NZ_S(ST_DDIM); else if (st == ST_MS2) ED_NZ_S(ST_MS2); else ED_NZ_S(ST_MS1);
+#undef ED_NZ_S
   }
   return done();
 }
@@ -2070,6 +2172,57 @@ int ed_phase_epilogue_ms(const void* g_out, const void* v_out, int dtype, const 
                                uncond_last, direction, local, K, B, C, H, W, h, w, gPH, gPW, g_off_y, g_off_x, vPH, vPW,
                                n_col_blocks, g, sqrt_beta_t, sqrt_alpha_t, c_x, b, rrg_norm, rrg_weight, stream, ratio, ratio_low,
                                gr, omgr, &ms);
+}
+
+// ---- stochastic samplers: DDIM eta > 0, SDE-DPM-Solver++(2M), LCM ------------------
+static inline bool bad_sde_arguments(int form, float c_n, const float* noise, const float* x0_hist, int prediction_type) {
+  if (bad_prediction_type(prediction_type) || (form != ED_FORM_DDIM && form != ED_FORM_MULTISTEP)) return true;
+  if (!noise || !__builtin_isfinite(c_n)) return true;
+  return form == ED_FORM_DDIM && x0_hist != nullptr;
+}
+
+int ed_cfg_ddim_step_sde(const float* local, const float* direction, const float* x, float* prev, float* x0, float g,
+                         float sqrt_beta_t, float sqrt_alpha_t, float c_x, float b, float half_b, float r_inv, int64_t n,
+                         int prediction_type, const float* ratio, float gr, float omgr, int B, const float* x0_hist, int form,
+                         float c_n, const float* noise, void* stream) {
+  if (bad_sde_arguments(form, c_n, noise, x0_hist, prediction_type)) return (int)hipErrorInvalidValue;
+  if (noise_overlaps(noise, prev, x0, nullptr, n)) return (int)hipErrorInvalidValue;
+  Rescale rs = NO_RESCALE;
+  if (ratio) {
+    if (B <= 0 || n % B) return (int)hipErrorInvalidValue;
+    rs.ratio = ratio, rs.gr = gr, rs.omgr = omgr, rs.per = n / B;
+    if (rs.per == 0) return 0;
+  }
+  const bool vp = prediction_type == ED_PRED_V;
+  Multistep ms = {x0_hist, half_b, r_inv};
+  if (c_n == 0.0f) {  // not a stochastic step: the deterministic launch, which never reads the noise
+    if (form == ED_FORM_DDIM) return cfg_ddim_launch(vp, local, direction, x, prev, x0, g, sqrt_beta_t, sqrt_alpha_t, c_x, b, n, stream, rs);
+    return cfg_ms_launch(vp, local, direction, x, prev, x0, g, sqrt_beta_t, sqrt_alpha_t, c_x, b, n, stream, rs, ms);
+  }
+  Noise nz = {noise, c_n};
+  return cfg_nz_launch(vp, form == ED_FORM_DDIM ? ST_DDIM : x0_hist ? ST_MS2 : ST_MS1, local, direction, x, prev, x0, g, sqrt_beta_t,
+                       sqrt_alpha_t, c_x, b, n, stream, rs, ms, nz);
+}
+
+int ed_phase_epilogue_sde(const void* g_out, const void* v_out, int dtype, const float* x, const int8_t* stamp,
+                          const int32_t* inv_row, const int32_t* inv_col, const int32_t* up_row, const int32_t* up_col,
+                          const int32_t* down_row, const int32_t* down_col, const int32_t* row_blk, const int32_t* row_src,
+                          const int32_t* col_blk, const int32_t* col_src, const float* low_latent, float* prev, float* x0,
+                          float* x_next, float* low_dir, float* uncond_last, float* direction, float* local, int K, int B,
+                          int C, int H, int W, int h, int w, int gPH, int gPW, int g_off_y, int g_off_x, int vPH, int vPW,
+                          int n_col_blocks, float g, float sqrt_beta_t, float sqrt_alpha_t, float c_x, float b, float half_b,
+                          float r_inv, float rrg_norm, float rrg_weight, int prediction_type, const float* ratio,
+                          const float* ratio_low, float gr, float omgr, const float* x0_hist, int form, float c_n,
+                          const float* noise, void* stream) {
+  if (bad_sde_arguments(form, c_n, noise, x0_hist, prediction_type)) return (int)hipErrorInvalidValue;
+  if (noise_overlaps(noise, prev, x0, x_next, (int64_t)B * C * H * W)) return (int)hipErrorInvalidValue;
+  Multistep ms = {x0_hist, half_b, r_inv};
+  Noise nz = {noise, c_n};
+  return phase_epilogue_launch(prediction_type == ED_PRED_V, g_out, v_out, dtype, x, stamp, inv_row, inv_col, up_row, up_col,
+                               down_row, down_col, row_blk, row_src, col_blk, col_src, low_latent, prev, x0, x_next, low_dir,
+                               uncond_last, direction, local, K, B, C, H, W, h, w, gPH, gPW, g_off_y, g_off_x, vPH, vPW,
+                               n_col_blocks, g, sqrt_beta_t, sqrt_alpha_t, c_x, b, rrg_norm, rrg_weight, stream, ratio, ratio_low,
+                               gr, omgr, form == ED_FORM_DDIM ? nullptr : &ms, c_n == 0.0f ? nullptr : &nz);
 }
 
 // ---- img2img / inpainting -----------------------------------------------------------------------------

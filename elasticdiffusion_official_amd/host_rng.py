@@ -10,6 +10,7 @@ Reference lines ("ED:n" = /root/reference/elastic_diffusion.py):
   pick indices     random_sample_exclude_mask ED:501-520, random_downsample ED:534-544, exclude mask ED:673-675
   pad-strip reseed make_denoised_background ED:331-335, 359 (md5 seed -> draws -> reseed from numpy)
   RePaint noise    undo_step ED:692-704
+  step noise       a stochastic sampler's draw inside scheduler.step ED:776, 920, 1033, 1054
 """
 import hashlib
 
@@ -118,3 +119,9 @@ def draw_noise_into(buf):
     for k in range(buf.shape[0]):
         buf[k].normal_()
     return buf
+
+
+def skip_noise(shape):
+    """Advance the generator by one ``torch.randn(shape)`` whose values nobody reads: the draw a stochastic scheduler makes in the
+    reduced-resolution step inside RRG (ED:920), whose ``prev_sample`` the reference discards."""
+    torch.randn(tuple(shape))

@@ -1,6 +1,8 @@
 """Torch-tensor wrappers over the C ABI (include/elastic_hip.h).  PyTorch is only plumbing here: it owns the device
 buffers and the stream; every wrapper validates its arguments, passes raw device pointers and raises on a HIP
 error.  No wrapper has a fallback path -- a tensor that is not on a ROCm device is an error."""
+import math
+
 import torch
 
 from . import _hip
@@ -384,6 +386,26 @@ def _multistep(multistep, prev, x0, what):
     return scalars, x0_hist
 
 
+def _noise(noise, like, outputs, what):
+    """``noise`` = (c_n, tensor): the scalar of the stochastic samplers' noise term (``noise_coefficient`` of the schedule) and the
+    host's draw (f32, ``like``'s shape) -> (c_n as a float, tensor).  A non-finite c_n, and a tensor that shares memory with an output
+    of the launch (they are written while it is being read), are refused."""
+    try:
+        c_n, tensor = noise
+        c_n = float(c_n)
+    except (TypeError, ValueError):
+        _reject(f"{what}: noise must be (c_n, tensor), got {noise!r}")
+    if not math.isfinite(c_n):
+        _reject(f"{what}: the noise coefficient must be finite, got {c_n!r}")
+    if not isinstance(tensor, torch.Tensor) or tuple(tensor.shape) != tuple(like.shape):
+        _reject(f"{what}: the noise must be an f32 tensor of shape {tuple(like.shape)}, got {tuple(getattr(tensor, 'shape', ()))}")
+    lo, hi = tensor.data_ptr(), tensor.data_ptr() + 4 * tensor.numel()
+    for t_ in outputs:
+        if isinstance(t_, torch.Tensor) and t_.data_ptr() < hi and lo < t_.data_ptr() + 4 * t_.numel():
+            _reject(f"{what}: the noise overlaps an output of the launch")
+    return c_n, tensor
+
+
 def guidance_moments_workspace(B, n_full, n_low=0, device=None):
     """The partials buffer of guidance_moments / phase_moments for B samples of ``n_full`` elements (+ the
     reduced-resolution pair of ``n_low`` elements): an f64 tensor, allocate once and reuse (launches on one stream)."""
@@ -460,7 +482,7 @@ def phase_moments(g_out, v_out, shape, stamp, pick_tables, view_tables, n_col_bl
 def phase_epilogue(g_out, v_out, x, stamp, pick_tables, view_tables, n_col_blocks, g_off, K, h, w, g, coef, prev, x0,
                    low_dir=None, uncond_last=None, direction=None, local=None, x_next=None, low_latent=None,
                    rrg_norm=0.0, rrg_weight=0.0, prediction_type="epsilon", ratio=None, ratio_low=None,
-                   guidance_rescale=0.0, multistep=None, region_w=None):
+                   guidance_rescale=0.0, multistep=None, region_w=None, noise=None):
     """unpad_direction + fill_directions + scatter_centres + cfg_ddim_step (+ rrg_update when ``x_next`` is given) in
     one launch (see ed_phase_epilogue / ed_phase_epilogue_pt).  pick_tables = (inv_row, inv_col, up_row, up_col,
     down_row, down_col); view_tables = (row_blk, row_src, col_blk, col_src); coef = DDIMSchedule.step_coefficients(t);
@@ -470,7 +492,10 @@ def phase_epilogue(g_out, v_out, x, stamp, pick_tables, view_tables, n_col_block
     DDIM one's place (ed_phase_epilogue_ms; only coef[:2] are then used); None launches what it always launched.
     ``region_w`` (f32 [P,H,W] from ``region_weights``; regional prompts): g_out holds 1 + P rows per step and
     sample, [(K*(1+P)*B),C,gPH,gPW], and the class direction of a pixel is the weighted sum of the P directions cond_p - uncond
-    (ed_phase_epilogue_rg, one launch with every other keyword as above); None launches what it always launched."""
+    (ed_phase_epilogue_rg, one launch with every other keyword as above); None launches what it always launched.
+    ``noise`` = (c_n, f32 [B,C,H,W]): the stochastic samplers' term, prev += c_n * noise, before the fused RRG output is formed
+    (ed_phase_epilogue_sde; with ``multistep`` the multistep form, otherwise the DDIM form with coef[3] =
+    sd_eta); at c_n == 0 the deterministic kernels run and the tensor is not read.  None launches what it always launched."""
     pt = _pred_code(prediction_type)
     B, C, H, W = x.shape
     gr, C2, gPH, gPW = g_out.shape
@@ -491,6 +516,33 @@ def phase_epilogue(g_out, v_out, x, stamp, pick_tables, view_tables, n_col_block
     f32 = torch.float32
     if ratio is None and (ratio_low is not None or float(guidance_rescale) != 0.0):
         _reject("phase_epilogue: guidance_rescale / ratio_low need ratio (phase_moments)")
+    if noise is not None:
+        if region_w is not None:
+            _reject("phase_epilogue: the regional epilogue has no noise variant (regions with a stochastic sampler)")
+        c_n, nz = _noise(noise, x, (prev, x0, x_next, low_dir, uncond_last, direction, local), "phase_epilogue")
+        ms, x0_hist = (tuple(float(c) for c in coef[2:4]) + (0.0, 0.0), None)
+        if multistep is not None:
+            ms, x0_hist = _multistep(multistep, prev, x0, "phase_epilogue")
+            if x0_hist is not None and tuple(x0_hist.shape) != tuple(x0.shape):
+                _reject(f"phase_epilogue: x0_hist must have x0's shape {tuple(x0.shape)}, got {tuple(x0_hist.shape)}")
+        gr_f, omgr_f = 0.0, 0.0
+        if ratio is not None:
+            if x_next is not None and ratio_low is None:
+                _reject("phase_epilogue: the fused RRG term with a rescale needs ratio_low")
+            if ratio_low is not None and tuple(ratio_low.shape) != (B,):
+                _reject(f"ratio_low must be f32 [{B}], got {tuple(ratio_low.shape)}")
+            gr_f, omgr_f = rescale_coefficients(guidance_rescale)
+        _call("ed_phase_epilogue_sde", _dev(g_out, None, "g_out"), _dev(v_out, None, "v_out"), _code(g_out, "g_out"),
+              _dev(x, f32, "x"), _dev(stamp, torch.int8, "stamp"), *(_dev(t_, torch.int32) for t_ in pick_tables),
+              *(_dev(t_, torch.int32) for t_ in view_tables), _opt(low_latent, f32, "low_latent"), _dev(prev, f32, "prev"),
+              _dev(x0, f32, "x0"), _opt(x_next, f32, "x_next"), _opt(low_dir, f32, "low_dir"),
+              _opt(uncond_last, f32, "uncond_last"), _opt(direction, f32, "direction"), _opt(local, f32, "local"),
+              K, B, C, H, W, h, w, gPH, gPW, g_off[0], g_off[1], vPH, vPW, n_col_blocks, float(g), float(coef[0]), float(coef[1]),
+              *ms, float(rrg_norm), float(rrg_weight), pt, None if ratio is None else _ratio_ptr(ratio, B, "ratio"),
+              _opt(ratio_low, f32, "ratio_low"), gr_f, omgr_f, _opt(x0_hist, f32, "x0_hist"), int(multistep is not None), c_n,
+              _dev(nz, f32, "noise"), _stream())
+        TIMER.note_work("ed_phase_epilogue_sde", nbytes=4.0 * x.numel())  # the read the variant adds to the epilogue's
+        return prev, x0
     if region_w is not None:
         ms, x0_hist = (tuple(float(c) for c in coef[2:4]) + (0.0, 0.0), None)
         if multistep is not None:
@@ -591,17 +643,38 @@ def fill_directions(dirs, stamp, inv_row, inv_col, up_row, up_col, down_row, dow
 
 
 def cfg_ddim_step(local, direction, x, prev, x0, g, sqrt_beta_t, sqrt_alpha_t, sqrt_alpha_prev, sqrt_1m_alpha_prev,
-                  prediction_type="epsilon", ratio=None, guidance_rescale=0.0, multistep=None):
+                  prediction_type="epsilon", ratio=None, guidance_rescale=0.0, multistep=None, noise=None):
     """``ratio`` (f32 [B] from guidance_moments; the buffers are then B equal samples) applies the guidance rescale to
     local + g * direction before the update (ed_cfg_ddim_step_gr); None is the plain launch.  ``multistep`` = (c_x, b, half_b,
     r_inv, x0_hist or None): the DPM-Solver++(2M) update in the DDIM one's place (ed_cfg_ddim_step_ms; sqrt_alpha_prev and
-    sqrt_1m_alpha_prev are then unused); None launches what it always launched."""
+    sqrt_1m_alpha_prev are then unused); None launches what it always launched.  ``noise`` = (c_n, f32 tensor of x's shape): the
+    stochastic samplers' term prev += c_n * noise (ed_cfg_ddim_step_sde; the multistep form with
+    ``multistep``, otherwise the DDIM form with sqrt_1m_alpha_prev = sd_eta); at c_n == 0 the deterministic kernels run and the
+    tensor is not read.  None launches what it always launched."""
     pt = _pred_code(prediction_type)
     n = x.numel()
     for t in (local, direction, prev, x0):
         assert t.numel() == n
     if ratio is None and float(guidance_rescale) != 0.0:
         _reject("cfg_ddim_step: guidance_rescale needs ratio (guidance_moments)")
+    if noise is not None:
+        c_n, nz = _noise(noise, x, (prev, x0), "cfg_ddim_step")
+        ms, x0_hist = (float(sqrt_alpha_prev), float(sqrt_1m_alpha_prev), 0.0, 0.0), None
+        if multistep is not None:
+            ms, x0_hist = _multistep(multistep, prev, x0, "cfg_ddim_step")
+        B, gr_f, omgr_f = 0, 0.0, 0.0
+        if ratio is not None:
+            B = ratio.numel()
+            if B == 0 or n % B:
+                _reject(f"cfg_ddim_step: {n} elements are not {B} equal samples")
+            gr_f, omgr_f = rescale_coefficients(guidance_rescale)
+        _call("ed_cfg_ddim_step_sde",
+              _dev(local, torch.float32), _dev(direction, torch.float32), _dev(x, torch.float32),
+              _dev(prev, torch.float32), _dev(x0, torch.float32), float(g), float(sqrt_beta_t), float(sqrt_alpha_t), *ms, n, pt,
+              None if ratio is None else _ratio_ptr(ratio, B, "ratio"), gr_f, omgr_f, B,
+              _opt(x0_hist, torch.float32, "x0_hist"), int(multistep is not None), c_n, _dev(nz, torch.float32, "noise"), _stream())
+        TIMER.note_work("ed_cfg_ddim_step_sde", nbytes=4.0 * n)  # the read the variant adds to the step's
+        return prev, x0
     if multistep is not None:
         ms, x0_hist = _multistep(multistep, prev, x0, "cfg_ddim_step")
         B, gr_f, omgr_f = 0, 0.0, 0.0

@@ -28,7 +28,7 @@ import torch.nn as nn
 
 from . import geometry, host_rng, ops
 from .graphs import GraphedForward
-from .schedule import SAMPLERS, CosineScheduler, DDIMSchedule, DPMSolverSchedule
+from .schedule import SAMPLERS, CosineScheduler, DDIMSchedule, DPMSolverSchedule, LCMSchedule, check_eta
 from .sharding import RowSharder
 
 
@@ -105,18 +105,59 @@ MASK_MODES = ("binary", "graded")
 INPAINT_IN_CHANNELS = 9
 
 
-def check_sampler_arguments(sampler=None, solver_order=2, scheduler=None):
-    """ValueError for a ``sampler`` / ``solver_order`` ElasticDiffusion cannot honour (before anything is built): ``sampler`` is
-    None (= "ddim" without a ``scheduler``, the scheduler's own kind with one), "ddim" or "dpmsolver++"; with a ``scheduler``
-    object it has to name that object's kind."""
+def scheduler_kind(scheduler):
+    """The ``sampler`` name a scheduler object answers to ("euler_a" is spelled ``DDIMSchedule(eta=1)`` and answers to both)."""
+    if isinstance(scheduler, LCMSchedule):
+        return "lcm"
+    if isinstance(scheduler, DPMSolverSchedule):
+        return "dpmsolver++sde" if scheduler.algorithm_type == "sde-dpmsolver++" else "dpmsolver++"
+    return "ddim"
+
+
+def check_sampler_arguments(sampler=None, solver_order=2, scheduler=None, eta=0.0):
+    """ValueError for a ``sampler`` / ``solver_order`` / ``eta`` ElasticDiffusion cannot honour (before anything is built):
+    ``sampler`` is None (= "ddim" without a ``scheduler``, the scheduler's own kind with one) or one of ``schedule.SAMPLERS``; with
+    a ``scheduler`` object it has to name that object's kind.  ``eta`` lies in [0, 1] and belongs to "ddim" alone ("euler_a" is
+    its eta = 1 by name; a ``scheduler`` object carries its own)."""
     if sampler is not None and sampler not in SAMPLERS:
         raise ValueError(f"sampler must be one of {SAMPLERS}, got {sampler!r}")
     if solver_order not in (1, 2):
         raise ValueError(f"solver_order must be 1 or 2, got {solver_order!r}")
+    eta = check_eta(eta)
+    if eta != 0.0 and (sampler or "ddim") != "ddim":
+        raise ValueError(f"eta={eta!r} belongs to sampler='ddim', got sampler={sampler!r}")
+    if eta != 0.0 and scheduler is not None:
+        raise ValueError("eta is given together with a scheduler object: pass DDIMSchedule(eta=...) instead")
     if scheduler is not None and sampler is not None:
-        kind = "dpmsolver++" if isinstance(scheduler, DPMSolverSchedule) else "ddim"
+        kind = scheduler_kind(scheduler)
+        if sampler == "euler_a" and kind == "ddim" and scheduler.eta == 1.0:
+            kind = "euler_a"
         if kind != sampler:
             raise ValueError(f"sampler={sampler!r} but the scheduler object given is a {type(scheduler).__name__} ({kind!r})")
+
+
+def check_regions_sampler(regions, scheduler):
+    """ValueError for ``regions`` under a stochastic sampler, before anything launches: the regional epilogue has no noise variant
+    (DESIGN.md section 29.6)."""
+    if regions is None:
+        return
+    if getattr(scheduler, "eta", 0.0) != 0.0 or scheduler_kind(scheduler) in ("dpmsolver++sde", "lcm"):
+        raise ValueError("regions are not supported with a stochastic sampler (DDIM with eta > 0, euler_a, dpmsolver++sde, lcm): "
+                         "the regional epilogue has no noise variant")
+
+
+def make_scheduler(base, sampler=None, solver_order=2, eta=0.0):
+    """The scheduler of ``sampler`` with the settings of ``base`` (a DDIMSchedule read from a snapshot / the defaults)."""
+    cfg = vars(base.config)
+    if sampler == "dpmsolver++":  # the same schedule settings, the multistep update (DESIGN.md section 25)
+        return DPMSolverSchedule(**cfg, solver_order=solver_order)
+    if sampler == "dpmsolver++sde":  # ... and its stochastic form (section 29)
+        return DPMSolverSchedule(**cfg, solver_order=solver_order, algorithm_type="sde-dpmsolver++")
+    if sampler == "lcm":
+        return LCMSchedule(**cfg)
+    if sampler == "euler_a" or eta != 0.0:
+        return DDIMSchedule(**cfg, eta=1.0 if sampler == "euler_a" else eta)
+    return base
 
 
 def check_inpaint_unet_arguments(in_channels, init_image=None, mask_image=None, mask_mode="binary", controlnet=False,
@@ -413,14 +454,19 @@ class ElasticDiffusion(nn.Module):
 
     ``sampler`` / ``solver_order`` (keyword-only): ``"dpmsolver++"`` samples with DPM-Solver++(2M) at order
     ``solver_order`` (1 or 2) on the same timestep grid instead of DDIM -- the update is a variant of the same step launches, reading
-    the previous timestep's x0; passing ``scheduler=DPMSolverSchedule(...)`` does the same.  None / ``"ddim"``: the loop as it was."""
+    the previous timestep's x0; passing ``scheduler=DPMSolverSchedule(...)`` does the same.  None / ``"ddim"``: the loop as it was.
+
+    The stochastic samplers: ``sampler="ddim"`` with ``eta`` in (0, 1], ``"euler_a"`` (= DDIM at eta = 1, the
+    ancestral step on this timestep grid), ``"dpmsolver++sde"`` (SDE-DPM-Solver++(2M)) and ``"lcm"`` (the scheduler an LCM-LoRA is
+    sampled with) add ``c_n * noise`` to the same update in the same launches; the noise is one latent-sized host draw per phase, in
+    the order a stochastic scheduler would draw inside the reference.  ``regions`` are refused with them."""
 
     def __init__(self, device, sd_version="2.0", verbose=False, log_freq=5, view_batch_size=1, low_vram=False, *,
                  unet=None, vae=None, scheduler=None, text_encoder=None, controlnet=None, process_group=None,
                  model_dtype=None, weights=None, cache_backgrounds=False, use_graphs=True, residual_fp32=None,
-                 max_prompt_chunks=1, prompt_weighting=False, sampler=None, solver_order=2):
+                 max_prompt_chunks=1, prompt_weighting=False, sampler=None, solver_order=2, eta=0.0):
         super().__init__()
-        check_sampler_arguments(sampler, solver_order, scheduler)
+        check_sampler_arguments(sampler, solver_order, scheduler, eta)
         device = torch.device(device)
         if device.type == "cuda" and device.index is None and torch.cuda.is_available():
             device = torch.device("cuda", torch.cuda.current_device())
@@ -463,8 +509,7 @@ class ElasticDiffusion(nn.Module):
         self.controlnet = self._model_layout(controlnet.to(device)) if controlnet is not None else None
         if scheduler is None:
             scheduler = DDIMSchedule.from_config_dir(weights) if weights else DDIMSchedule()  # ED:153
-            if sampler == "dpmsolver++":  # the same schedule settings, the multistep update
-                scheduler = DPMSolverSchedule(**vars(scheduler.config), solver_order=solver_order)
+            scheduler = make_scheduler(scheduler, sampler, solver_order, float(eta))
         self.scheduler = scheduler
         if text_encoder is None and weights:
             # real UNet/VAE weights with synthetic prompt embeddings would be prompt-independent garbage: a snapshot
@@ -486,6 +531,7 @@ class ElasticDiffusion(nn.Module):
         self.set_view_config()
         self.default_size = None
         self._stager = _Stager()
+        self.host_s = {"picks": 0.0, "phase_total": 0.0, "noise": 0.0, "stager_wait": 0.0}  # reset per image by _setup_run
         self.last_latents = None
         self.last_init_latents = None  # z0 of the last image started with ``init_image`` (its encoded, scaled latent)
         self.last_init_pixels = None   # uint8 [height,width,3]: the (resized) 8-bit init picture of the last such image, on the device
@@ -938,7 +984,7 @@ class ElasticDiffusion(nn.Module):
 
     # ---- one estimation phase (ED:1016-1035 or ED:1043-1056) ---------------------------------------
     def _phase_steps(self, P, x, ti, K, g, drop_p, emb, cond=None, direct=True, rrg_w=None, rrg_norm=0.0, frames=None,
-                     rescale=None, extras=None, multistep=None, keep_scores=False, region_w=None):
+                     rescale=None, extras=None, multistep=None, keep_scores=False, region_w=None, step_noise=None):
         """Generator: pre-model glue -> ``yield _ModelCall`` (receives the model output rows) -> post-model glue;
         returns (prev, x0, info).  ``direct``: assemble straight into the hipGraph's static input (one image in flight,
         one rank); otherwise into a scratch batch the driver concatenates / the sharder slices.  ``rrg_w``: this is the
@@ -952,7 +998,10 @@ class ElasticDiffusion(nn.Module):
         ``keep_scores``: info["direction"] / info["local"] are kept as ``verbose`` keeps them (the inputs of the score PCA maps).
         ``region_w`` (f32 [P,Hl,Wl]; regional prompts): a step holds 1 + P rows per sample and the class direction
         is the per-pixel weighted sum of the P directions -- ``ops.assemble_rows_n`` and the regional epilogue in the places of the
-        plain launches; None launches what it always did."""
+        plain launches; None launches what it always did.  ``step_noise`` (the step's c_n, section 29; None for a step that is not
+        stochastic): the phase's latent-sized normal draw is made with the other host draws -- after the picks and the strip
+        reseeds, where the reference's ``scheduler.step`` would draw -- and added by the step's own launch; with ``rrg_w`` the
+        reduced-resolution step's draw, whose result the reference discards, only advances the generator."""
         ms_kw = {} if multistep is None else dict(multistep=multistep)
         B, C = x.shape[:2]
         CR = C if extras is None else C + extras[0].shape[1]  # channels of a model INPUT row
@@ -972,6 +1021,9 @@ class ElasticDiffusion(nn.Module):
         if P.vpad.strips:
             for _ in range(math.ceil(P.views.V / self.view_batch_size)):
                 host_rng.replay_strip_reseeds(len(P.vpad.strips))
+        if step_noise is not None:
+            assert region_w is None
+            ms_kw["noise"] = (step_noise, self._draw_step_noise(x.shape, None if rrg_w is None else (B, C, P.h, P.w)))
         gframes, vframes = frames if frames is not None else (self._gframes, self._vframes)
         gframe = None if gframes is None else gframes[ti]
         vframe = None if vframes is None else vframes[ti]
@@ -1079,6 +1131,25 @@ class ElasticDiffusion(nn.Module):
         info = {"low_latent": low[K - 1], "uncond_score": uncond_last, "low_direction": low_dir,
                 "direction": direction, "local": local, "init_low": low[0], "x_next": x_next, "ratio_low": ratio_low}
         return prev, x0, info
+
+    def _draw_step_noise(self, shape, discarded=None):
+        """The noise of one stochastic step (section 29): ``torch.randn(shape)`` on the host generator, staged through pinned memory
+        like ``_undo``'s; then, for ``discarded`` (the reduced-resolution step inside RRG), a draw of that shape whose values nobody
+        reads -- no staging, no upload."""
+        h0 = time.perf_counter()
+        host = self._stager.host(tuple(shape), torch.float32)
+        self.host_s["stager_wait"] += time.perf_counter() - h0
+        host_rng.draw_noise_into(host[None])
+        if discarded is not None:
+            host_rng.skip_noise(discarded)
+        self.host_s["noise"] += time.perf_counter() - h0
+        return self._stager.upload(host, self.device)
+
+    def _step_noise(self, t):
+        """``step_noise`` of ``_phase_steps`` at timestep ``t``: the schedule's noise coefficient, None where the step is not
+        stochastic (c_n == 0.0: nothing is drawn and the deterministic kernels run)."""
+        c_n = self.scheduler.noise_coefficient(t)
+        return c_n if c_n != 0.0 else None
 
     def _multistep_args(self, t, hist, is_last):
         """The ``multistep`` argument of the step kernels at timestep ``t``: None under a DDIM scheduler; under a
@@ -1515,13 +1586,14 @@ class ElasticDiffusion(nn.Module):
             pca_ws = ops.score_pca_workspace(B, P.Hl * P.Wl, self.device)
         for i, t in enumerate(progress(self._timesteps[S.t_start:]), start=S.t_start):  # absolute index; t_start = 0 without strength
             ms = self._multistep_args(t, hist, i == S.T - 1)  # both phases of a timestep step from the same history
+            nz = self._step_noise(t)  # every phase of a stochastic timestep draws its own noise
             w_i = S.rrg(i)
             rrg_w = w_i if w_i > 10 else None  # ED:1061-1062
             two_phase = S.repaint and i < S.T - 1
             mapped = score_maps is not None and i % self.log_freq == 0
             prev, x0, info = yield from self._phase_steps(P, x, i, S.R + 1, S.guidance, S.drop_p, emb, cond, direct,
                                                           None if two_phase else rrg_w, S.norm, frames, rescale, extras, ms,
-                                                          keep_scores=mapped, **rg_kw)
+                                                          keep_scores=mapped, step_noise=nz, **rg_kw)
             if mapped:  # PCA:165-196 on the R + 1-pass direction estimate and the per-view score, before the RePaint phase
                 score_maps["pca_cls_dir"][i] = ops.score_pca(info["direction"], normalize=True, workspace=pca_ws)
                 score_maps["pca_uncond"][i] = ops.score_pca(info["local"], workspace=pca_ws)
@@ -1536,7 +1608,7 @@ class ElasticDiffusion(nn.Module):
                 x = self._undo(prev, i + 1)
                 cfg = S.guidance / 3
                 prev, x0, info = yield from self._phase_steps(P, x, i, 1, cfg, S.drop_p, emb, cond, direct, rrg_w, S.norm,
-                                                              frames, rescale, extras, ms, **rg_kw)
+                                                              frames, rescale, extras, ms, step_noise=nz, **rg_kw)
             hist = (x0, t)
             if logs is not None:  # verbose image logs (ED:1058-1059, 1073-1076)
                 if i % self.log_freq == 0:
@@ -1628,6 +1700,7 @@ class ElasticDiffusion(nn.Module):
         (plane 0 the base prompt's) of the last run, or None."""
         regions, region_blur = check_region_arguments(regions, height, width, self.vae_scale_factor, region_blur,
                                                       self.unet.config.in_channels)
+        check_regions_sampler(regions, getattr(self, "scheduler", None))
         self._check_ip_adapter(ip_adapter_image, ip_adapter_image_embeds)
         check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
         score_pca = check_score_pca_arguments(score_pca, self._score_channels())
@@ -1686,6 +1759,8 @@ class ElasticDiffusion(nn.Module):
         n_chunks = None
         job_regions = [check_region_arguments(job.get("regions"), height, width, self.vae_scale_factor, job.get("region_blur", 0.0),
                                               self.unet.config.in_channels) for job in jobs]
+        for rg, _ in job_regions:
+            check_regions_sampler(rg, getattr(self, "scheduler", None))
         for job, (rg, _) in zip(jobs, job_regions):
             n = self._prompt_chunks(job["prompts"], job.get("negative_prompts", ""))
             if n is not None:
@@ -1859,10 +1934,12 @@ class ElasticDiffusion(nn.Module):
             if rs_kw:
                 ops.guidance_moments(uncond, direction, np.float32(guidance_scale), rs_kw["ratio"], ws, text=cnd)
             ms = self._multistep_args(t, hist, i == len(ts) - 1)
+            nz = self._step_noise(t)  # a stochastic step draws where the reference calls scheduler.step (ED:776)
             ops.cfg_ddim_step(uncond, direction, x, prev, x0, np.float32(guidance_scale),
                               *self.scheduler.step_coefficients(t),
                               prediction_type=self.scheduler.config.prediction_type, **rs_kw,
-                              **({} if ms is None else dict(multistep=ms)))
+                              **({} if ms is None else dict(multistep=ms)),
+                              **({} if nz is None else dict(noise=(nz, self._draw_step_noise(x.shape)))))
             hist = (x0, t)
             x = prev
             if i % self.log_freq == 0:
@@ -1950,6 +2027,7 @@ class ElasticDiffusion(nn.Module):
         ``regions`` / ``region_blur``: regional prompts (see ``generate_latents``).
         Returns ``(images, image_log)``; images are PIL by default, a float tensor with ``output_type='pt'``."""
         check_region_arguments(regions, height, width, self.vae_scale_factor, region_blur, self.unet.config.in_channels)
+        check_regions_sampler(regions, getattr(self, "scheduler", None))
         self._check_ip_adapter(ip_adapter_image, ip_adapter_image_embeds)
         check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
         check_soft_inpaint_arguments(init_image, mask_image, mask_blur, mask_mode, composite, output_type, grid,
@@ -2154,6 +2232,7 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
                        composite=False, ip_adapter_image=None, ip_adapter_image_embeds=None, score_pca=False, regions=None,
                        region_blur=0.0):
         check_region_arguments(regions, height, width, self.vae_scale_factor, region_blur, self.unet.config.in_channels)
+        check_regions_sampler(regions, getattr(self, "scheduler", None))
         self._check_ip_adapter(ip_adapter_image, ip_adapter_image_embeds)
         check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
         check_soft_inpaint_arguments(init_image, mask_image, mask_blur, mask_mode, composite, output_type, grid,

@@ -469,6 +469,40 @@ int ed_phase_epilogue_ms(const void* g_out, const void* v_out, int dtype, const 
                          const float* ratio_low, float gr, float omgr, const float* x0_hist, void* stream);
 
 /*
+ * Stochastic samplers: DDIM with eta > 0 ("Euler a" is eta = 1), SDE-DPM-Solver++(2M) and LCM are the
+ * deterministic update with other host scalars plus one term,
+ *     prev = <the update> + c_n * noise,
+ * the product rounded on its own, added last.  noise f32 [n] / [B,C,H,W] is read at the output element's index; the host draws it.
+ *
+ * ed_cfg_ddim_step_sde / ed_phase_epilogue_sde -- the *_ms entry points plus `form`, `c_n` and `noise`.
+ *   form ED_FORM_DDIM:       prev = (c_x * x0 + b * eps) + c_n * noise -- the DDIM update of the *_gr entry points with c_x / b in
+ *                            the places of sqrt_alpha_prev / sqrt_1m_alpha_prev (the host passes (1 - abar_prev - c_n^2)^0.5 as b);
+ *                            half_b / r_inv are unused and x0_hist must be NULL.
+ *   form ED_FORM_MULTISTEP:  prev = ((c_x * x - b * x0) - half_b * (r_inv * (x0 - x0_hist))) + c_n * noise, first order with a
+ *                            NULL x0_hist as in *_ms.  LCM is this form at first order with its own c_x, b, c_n.
+ * The fused RRG output x_next is formed from the prev that carries the noise.  c_n == 0 is not a stochastic step: the
+ * deterministic kernels are launched and `noise` is not read.
+ * hipErrorInvalidValue before any launch: what the *_ms entry point refuses, a NULL noise, a non-finite c_n, a form other
+ * than ED_FORM_*, an x0_hist with ED_FORM_DDIM, and a noise that shares an element with prev, x0 or x_next.  The 16-byte form of
+ * the flat step additionally needs noise 16-byte aligned; the scalar form otherwise.
+ */
+enum { ED_FORM_DDIM = 0, ED_FORM_MULTISTEP = 1 };
+int ed_cfg_ddim_step_sde(const float* local, const float* direction, const float* x, float* prev, float* x0,
+                         float g, float sqrt_beta_t, float sqrt_alpha_t, float c_x, float b, float half_b, float r_inv,
+                         int64_t n, int prediction_type, const float* ratio, float gr, float omgr, int B,
+                         const float* x0_hist, int form, float c_n, const float* noise, void* stream);
+int ed_phase_epilogue_sde(const void* g_out, const void* v_out, int dtype, const float* x, const int8_t* stamp,
+                          const int32_t* inv_row, const int32_t* inv_col, const int32_t* up_row, const int32_t* up_col,
+                          const int32_t* down_row, const int32_t* down_col, const int32_t* row_blk, const int32_t* row_src,
+                          const int32_t* col_blk, const int32_t* col_src, const float* low_latent, float* prev, float* x0,
+                          float* x_next, float* low_dir, float* uncond_last, float* direction, float* local, int K, int B,
+                          int C, int H, int W, int h, int w, int gPH, int gPW, int g_off_y, int g_off_x, int vPH, int vPW,
+                          int n_col_blocks, float g, float sqrt_beta_t, float sqrt_alpha_t, float c_x, float b, float half_b,
+                          float r_inv, float rrg_norm, float rrg_weight, int prediction_type, const float* ratio,
+                          const float* ratio_low, float gr, float omgr, const float* x0_hist, int form, float c_n,
+                          const float* noise, void* stream);
+
+/*
  * Regional prompts: P = n + 1 conditional rows per resampling step and sample -- the base prompt and n
  * regions, 1 <= P <= 8 -- whose class directions cond_p - uncond are summed per pixel with the weights region_w f32 [P,H,W].
  * Model rows are step-major: [(K*(1+P)*B),C,gPH,gPW], within a step uncond first, then cond 0..P-1, each x B.  Additions, no
