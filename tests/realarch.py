@@ -32,6 +32,9 @@ REAL_CASES = {
     "cfg3_xl_1024x2048": dict(sd="XL1.0", H=1024, W=2048, vbs=16, steps=2, R=2, seed=1),
     "cfg5_cn_xl_1024x2048": dict(sd="XL1.0", H=1024, W=2048, vbs=16, steps=2, R=1, seed=2, controlnet=True),
 }
+# SD 1.5 with a ControlNet: the configuration in which the product's DEFAULT mode (fp32 residual stream, ``residual_fp32=None``) adds
+# 16-bit ControlNet residuals onto fp32 skips.  Not in REAL_CASES: it runs the 16-bit legs only (plain and default, no fp32 product leg).
+CONTROLNET_SD_CASE = dict(sd="1.5", H=512, W=1024, vbs=4, steps=2, R=1, seed=3, controlnet=True)
 LOOP_KW = dict(guidance_scale=10.0, new_p=0.3, rrg_stop_t=0.2, rrg_init_weight=1000, cosine_scale=10.0,
                repaint_sampling=True)
 
@@ -129,15 +132,20 @@ def run_oracle(case, unet, vae, cn):
     return trace, torch.rand(4)
 
 
-def run_product(case, unet, vae, cn, dtype, device="cuda:0", residual_fp32=False):
-    """The HIP product path with copies of the given modules on the GPU (UNet/ControlNet in ``dtype``, VAE fp32).
-    ``residual_fp32``: the round-6 tolerance mode (fp32 residual stream under the 16-bit branches)."""
+def make_product(case, unet, vae, cn, dtype, device="cuda:0", residual_fp32=False):
+    """The product pipeline of ``run_product`` with copies of the given modules on the GPU, not yet run.  ``residual_fp32=None``: the
+    pipeline's own default, resolved per model family (``pipe.residual_fp32`` says what it became)."""
     from elasticdiffusion_official_amd import ElasticDiffusion
     c = REAL_CASES[case] if isinstance(case, str) else case
     xl = c["sd"].startswith("XL")
-    pipe = ElasticDiffusion(device, c["sd"], view_batch_size=c["vbs"], unet=copy.deepcopy(unet).to(dtype),
+    return ElasticDiffusion(device, c["sd"], view_batch_size=c["vbs"], unet=copy.deepcopy(unet).to(dtype),
                             vae=copy.deepcopy(vae), controlnet=None if cn is None else copy.deepcopy(cn).to(dtype),
                             text_encoder=embed_fn(xl), residual_fp32=residual_fp32)
+
+
+def run_pipe(case, pipe, cn):
+    """one seeded generate_latents of ``pipe`` -> (per-timestep latents on the CPU, RNG tail, pipe)"""
+    c = REAL_CASES[case] if isinstance(case, str) else case
     kw = dict(LOOP_KW)
     if cn is not None:
         ds = pipe.get_downsample_size(c["H"], c["W"])
@@ -150,6 +158,12 @@ def run_product(case, unet, vae, cn, dtype, device="cuda:0", residual_fp32=False
     return [z.cpu() for z in trace], tail, pipe
 
 
+def run_product(case, unet, vae, cn, dtype, device="cuda:0", residual_fp32=False):
+    """The HIP product path with copies of the given modules on the GPU (UNet/ControlNet in ``dtype``, VAE fp32).
+    ``residual_fp32``: the round-6 tolerance mode (fp32 residual stream under the 16-bit branches); None: the pipeline's default."""
+    return run_pipe(case, make_product(case, unet, vae, cn, dtype, device, residual_fp32), cn)
+
+
 DTYPES = {"bf16": torch.bfloat16, "fp16": torch.float16}
 
 # Longer runs at reduced width: how the 16-bit drift behaves over many denoising steps, not just the first two
@@ -160,7 +174,11 @@ LONG_CASES = {
 }
 
 
-def drift_report(case, dtype=torch.bfloat16, device="cuda:0", with_fp32=True, with_batching=True, dtypes=None, comparator="autocast"):
+DEFAULT_LEG = "_default"     # out[d + DEFAULT_LEG]: the product leg of dtype d built with residual_fp32=None
+
+
+def drift_report(case, dtype=torch.bfloat16, device="cuda:0", with_fp32=True, with_batching=True, dtypes=None, comparator="autocast",
+                 default_legs=False):
     """-> dict of per-timestep rel-L2 lists (see module docstring) + RNG-tail equality flags.
 
     ``dtypes`` (names from DTYPES, default: just ``dtype`` reported under its name; bf16 is also reported under the
@@ -170,7 +188,13 @@ def drift_report(case, dtype=torch.bfloat16, device="cuda:0", with_fp32=True, wi
                                           plain torch ops: AutocastOnDevice; ``comparator="pure16"``: the round 2-4 comparator,
                                           this repo's module with d weights)                      vs fp32 oracle
         out["batching_" + d]              product in d vs that reference-pattern run
-    fp16 is the dtype the reference's own GPU path runs the UNet in (CUDA autocast, ED:1012)."""
+    fp16 is the dtype the reference's own GPU path runs the UNet in (CUDA autocast, ED:1012).
+
+    ``default_legs`` (needs ``with_batching``): for every d one more product leg, built with ``residual_fp32=None`` -- the mode a caller
+    who says nothing gets (SD 1.x / 2.x: the fp32 residual stream; SDXL: plain) -- reported under d + "_default" with the same keys as
+    the plain leg, against the SAME oracle trace and the SAME reference-pattern run (so ``gate_16bit(rep, d + "_default")`` holds it to
+    the bar of its dtype), plus out[d + "_default_residual_fp32"] = what the default resolved to (out[d + "_residual_fp32"]: the plain
+    leg's, False).  Where the default resolves to the plain mode the leg would repeat the plain run and is not run: only the flag is set."""
     c = REAL_CASES[case] if isinstance(case, str) else case
     if dtypes is None:
         dtypes = [k for k, v in DTYPES.items() if v == dtype]
@@ -196,6 +220,22 @@ def drift_report(case, dtype=torch.bfloat16, device="cuda:0", with_fp32=True, wi
             out["ref_pattern_vs_fp32_" + name] = [rel_l2(a, b) for a, b in zip(ref_pattern, want)]
             if name == "bf16":
                 out["batching"], out["ref_pattern_vs_fp32"] = out["batching_bf16"], out["ref_pattern_vs_fp32_bf16"]
+        out[name + "_residual_fp32"] = bool(pipe.residual_fp32)
+        if default_legs:
+            if not with_batching:
+                raise ValueError("default_legs are held to the reference-pattern run: with_batching must be on")
+            leg = name + DEFAULT_LEG
+            pipe_d = make_product(c, unet, vae, cn, dt, device, residual_fp32=None)
+            out[leg + "_residual_fp32"] = bool(pipe_d.residual_fp32)
+            if pipe_d.residual_fp32 != pipe.residual_fp32:
+                got_d, t_d, _ = run_pipe(c, pipe_d, cn)
+                out[leg] = [rel_l2(a, b) for a, b in zip(got_d, want)]
+                out[leg + "_rng_tail_equal"] = bool(torch.equal(t_d, tail))
+                out[leg + "_finite"] = bool(all(torch.isfinite(z).all() for z in got_d))
+                out[leg + "_graphs"] = pipe_d._runner.stats()
+                out["batching_" + leg] = [rel_l2(a, b) for a, b in zip(got_d, ref_pattern)]
+                out["ref_pattern_vs_fp32_" + leg] = out["ref_pattern_vs_fp32_" + name]
+            del pipe_d
     return out
 
 
@@ -214,10 +254,13 @@ def gate_16bit(rep, name):
     reference's own GPU arithmetic (fp32 weights under torch.autocast, ED:1012) -- i.e. K-batching, the fused kernels, the 16-bit
     weights and the hipGraph add at most a quarter to what the dtype itself costs the reference -- and the two 16-bit runs may
     differ from each other by no more than 2x that (independent rounding noise adds in quadrature: sqrt(2) expected).
+    ``name``: a dtype's plain leg ("fp16") or its default-mode leg ("fp16_default", drift_report's ``default_legs``): the factor is the
+    dtype's either way, and the comparator is the reference's pattern under autocast, which knows nothing of the product's mode.
     -> (ok, message)"""
     ours, ref = max(rep[name]), max(rep["ref_pattern_vs_fp32_" + name])
     both = max(rep["batching_" + name])
-    ok = ours <= GATE_FACTOR_BY_DTYPE.get(name, GATE_FACTOR) * ref + GATE_SLACK and both <= 2.0 * ref + GATE_SLACK and rep[name + "_finite"]
+    dtype_name = name[:-len(DEFAULT_LEG)] if name.endswith(DEFAULT_LEG) else name
+    ok = ours <= GATE_FACTOR_BY_DTYPE.get(dtype_name, GATE_FACTOR) * ref + GATE_SLACK and both <= 2.0 * ref + GATE_SLACK and rep[name + "_finite"]
     return ok, f"{name}: product {ours:.3e}, reference pattern {ref:.3e}, product-vs-pattern {both:.3e}"
 
 

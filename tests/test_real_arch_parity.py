@@ -11,6 +11,10 @@ Bars:
     the drift of the REFERENCE'S call pattern (batch-2 calls per resampling step, view batches) driving the same 16-bit
     model, and the two 16-bit runs within 2x that of each other (realarch.gate_16bit) -- 16-bit rounding through a
     random-init UNet under guidance 10 is a property of the dtype; what this repo adds on top of it is what is gated;
+  * the mode a caller who says nothing gets (``ElasticDiffusion(residual_fp32=None)``: the fp32 residual stream for the SD 1.x / 2.x
+    family, plain 16 bits for SDXL): the legs above pin ``residual_fp32=False``, so the SD 1.5 cases -- without and with a ControlNet,
+    2-3 steps and 6 -- run one more leg per dtype in the default mode under the SAME gate (``drift_report(default_legs=True)``); the SDXL
+    cases assert only that their default is the plain mode they already run.
 The measured numbers are written to gpurun_out/parity_real_arch.json for DESIGN.md.
 """
 import copy
@@ -33,7 +37,7 @@ def reports():
 
 @pytest.mark.parametrize("case", list(R.REAL_CASES))
 def test_real_architecture_in_the_loop(case, reports):
-    rep = R.drift_report(case, dtypes=["bf16", "fp16"])
+    rep = R.drift_report(case, dtypes=["bf16", "fp16"], default_legs=True)
     reports[case] = rep
     print(json.dumps(rep))
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
@@ -45,6 +49,39 @@ def test_real_architecture_in_the_loop(case, reports):
     for name in ("bf16", "fp16"):  # fp16 = the dtype of the reference's own GPU path (CUDA autocast, ED:1012)
         ok, msg = R.gate_16bit(rep, name)
         assert ok, msg
+        assert rep[name + "_residual_fp32"] is False      # the legs above pin the plain mode
+    # the mode a caller who says nothing gets (ElasticDiffusion(residual_fp32=None)): the fp32 residual stream for the SD 1.x / 2.x
+    # family -- under the same gate, whose comparator (the reference's pattern under autocast) is independent of the mode -- plain for SDXL
+    if R.REAL_CASES[case]["sd"].startswith("XL"):
+        assert rep["bf16_default_residual_fp32"] is False and rep["fp16_default_residual_fp32"] is False
+    else:
+        _default_legs_meet_the_gate(rep)
+
+
+def _default_legs_meet_the_gate(rep):
+    for name in ("bf16", "fp16"):
+        leg = name + R.DEFAULT_LEG
+        assert rep[leg + "_residual_fp32"] is True, leg
+        assert rep[leg + "_rng_tail_equal"], leg
+        assert rep[leg + "_graphs"]["eager"] == 0 and rep[leg + "_graphs"]["captured"] >= 1, rep[leg + "_graphs"]
+        ok, msg = R.gate_16bit(rep, leg)
+        print(msg, "| stream32 / plain drift", [float(f"{a / b:.3f}") for a, b in zip(rep[leg], rep[name])])
+        assert ok, msg
+
+
+def test_sd15_with_controlnet_in_its_default_mode():
+    """SD 1.5 architecture (reduced width) with a ControlNet, 512x1024, 2 steps, R = 1, conditioning scale 0.2: in the default mode the
+    ControlNet's 16-bit residuals are added onto the UNet's fp32 skips.  Plain and default legs in fp16 and bf16, each under gate_16bit
+    against the reference's call pattern under autocast and with the oracle's RNG tail (no fp32 product leg: the case is about the modes)."""
+    rep = R.drift_report(R.CONTROLNET_SD_CASE, dtypes=["bf16", "fp16"], with_fp32=False, default_legs=True)
+    rep["case"] = "cn_sd_512x1024"
+    print(json.dumps(rep))
+    assert rep["graphs"]["eager"] == 0 and rep["graphs"]["captured"] >= 1, rep["graphs"]
+    for name in ("bf16", "fp16"):
+        assert rep[name + "_rng_tail_equal"] and rep[name + "_residual_fp32"] is False
+        ok, msg = R.gate_16bit(rep, name)
+        assert ok, msg
+    _default_legs_meet_the_gate(rep)
 
 
 def test_16bit_drift_over_many_steps_stays_at_the_reference_patterns():
@@ -52,11 +89,12 @@ def test_16bit_drift_over_many_steps_stays_at_the_reference_patterns():
     profiles/r3_precision.json: flat after the second step): the 16-bit loops must stay finite and within
     1.25x of the drift the reference's own call pattern shows in its own GPU arithmetic (fp32 weights under autocast) at EVERY step -- the two-step cases
     above cannot show a trend."""
-    rep = R.drift_report(R.LONG_CASES["cfg2_sd_512x1024_6steps"], dtypes=["bf16", "fp16"], with_fp32=False)
+    rep = R.drift_report(R.LONG_CASES["cfg2_sd_512x1024_6steps"], dtypes=["bf16", "fp16"], with_fp32=False, default_legs=True)
     print(json.dumps({k: [float(f"{v:.3e}") for v in rep[k]] for k in rep if isinstance(rep[k], list)}))
     for name in ("bf16", "fp16"):
         ok, msg = R.gate_16bit(rep, name)
         assert ok, msg
+    _default_legs_meet_the_gate(rep)    # the product's default for this family (fp32 residual stream), same gate at every step
 
 
 def test_full_width_sdxl_forward_16bit_error_is_the_dtypes():

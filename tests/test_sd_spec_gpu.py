@@ -6,7 +6,8 @@ executed on the GPU in the same dtype with plain torch ops (``e_spec``).  Bar: e
 16-bit output dtype (ulp as in test_unet_kernels.py: 2^-11 fp16, 2^-8 bf16; relative to max |ref|), 2e-6 for fp32 outputs.  Blocks: per-element maximum of |got - ref| / max |ref|; whole
 forwards: relative L2.  Parameters are randomised (no trivial affine, 0.2-sized biases: a lost bias is an error of order 10 %) and
 rounded to the dtype BEFORE both sides read them.  Every launch sequence runs twice and must be bit-identical (``judge`` says how for the
-cases on the library's convolutions).
+cases on the library's convolutions).  The last section runs the same blocks and forwards on the fp32 residual stream of a 16-bit model
+(``residual_fp32``: the dispatch tree the SD 1.x / 2.x family takes by default) under the same bar.
 """
 import functools
 
@@ -495,3 +496,258 @@ def test_vae_encode_and_decode(mods):
           expect=common + ("ed_conv3x3_nhwc_f32out_s2",), whole=True, library_conv=True)
     judge(ops, "small VAE decode", lambda: m.decode(z).sample, lambda: S.vae_decode(gpu_sd, boc, z), ref_dec,
           expect=common + ("ed_conv3x3_nhwc_f32out",), whole=True, library_conv=True)
+
+
+# ---- the fp32 residual stream under a 16-bit model (UNet2DConditionModel.residual_fp32, the default of the SD 1.x / 2.x family) ---------
+# The stream input of every case is the case's 16-bit-representable x carried as fp32; the yardstick stays the all-16-bit spec on the GPU.
+# Every case also prints its error beside the plain-mode (16-bit stream) error of the same case: recorded, not asserted.
+CONV3X3_KERNELS = ("ed_conv3x3_nhwc", "ed_conv3x3_nhwc_up2x", "ed_conv3x3_nhwc_s2", "ed_conv3x3_nhwc_f32out", "ed_conv3x3_nhwc_f32out_s2")
+NHWC_KERNELS = CONV3X3_KERNELS + ("ed_groupnorm_nhwc", "ed_groupnorm_nhwc_s32", "ed_groupnorm_nhwc_cat")
+
+
+def _as_stream(x, cl=True):
+    """the same (16-bit-representable) values as the fp32 residual stream"""
+    return x.float().contiguous(memory_format=CL) if cl else x.float().contiguous()
+
+
+def _beside_plain(name, run32, run_plain, ref, whole=False):
+    """print the stream32 error beside the plain-mode error of the same case (the ratio is a record, the asserted bar is ``judge``'s)"""
+    err = (lambda a: S.rel_l2(_listed(a), _listed(ref))) if whole else (lambda a: _max_err(a, ref))
+    with torch.no_grad():
+        e32, e16 = err(run32()), err(run_plain())
+    print(f"{name}: stream32 {e32:.3e} plain {e16:.3e} stream32/plain {e32 / max(e16, 1e-300):.2f}")
+    return e32, e16
+
+
+def _deterministic(run):
+    """one run with the library asked for deterministic solvers: for bit-for-bit comparisons of runs that reach its convolutions"""
+    keep = torch.backends.cudnn.deterministic
+    torch.backends.cudnn.deterministic = True
+    try:
+        with torch.no_grad():
+            return run()
+    finally:
+        torch.backends.cudnn.deterministic = keep
+
+
+@pytest.mark.parametrize("cin,cout", RES_SHAPES)
+def test_bf16_resnet_on_the_fp32_residual_stream(cin, cout, mods, admit):
+    """bf16 has no fp32-output convolution: conv2 is the 16-bit ed_conv3x3_nhwc (bias in its epilogue), its result is added to the stream
+    by ONE fp32 torch add, the shortcut (cin != cout) is ed_linear over the token view of the narrowed stream"""
+    M, ops = mods
+    dtype = torch.bfloat16
+    blk, x, emb, ref, spec = _resnet(M, cin, cout, dtype, cl=True)
+    x32 = _as_stream(x)
+    name = f"ResnetBlock2D fp32 stream {cin}->{cout} bfloat16"
+    stats = judge(ops, name, lambda: blk(x32, emb), spec, ref,
+                  expect=("ed_groupnorm_nhwc_s32", "ed_groupnorm_nhwc", "ed_conv3x3_nhwc") + (("ed_linear",) if cin != cout else ()),
+                  forbid=("ed_conv3x3_nhwc_f32out", "ed_bias_residual_add"))
+    assert stats["ed_conv3x3_nhwc"][0] == 2 and stats["ed_groupnorm_nhwc"][0] == 1 and stats["ed_groupnorm_nhwc_s32"][0] == 1, stats
+    with torch.no_grad():
+        out = blk(x32, emb)
+    assert out.dtype == torch.float32 and ops.is_nhwc(out)
+    _beside_plain(name, lambda: blk(x32, emb), lambda: blk(x, emb), ref)
+
+
+@pytest.mark.parametrize("dtype", HALF, ids=_name)
+@pytest.mark.parametrize("cin,cout", RES_SHAPES)
+def test_resnet_on_the_fp32_residual_stream_default_policy(cin, cout, dtype, mods, monkeypatch):
+    """no admission: at this size the policy leaves both convolutions with the library.  norm1 reads the stream (ed_groupnorm_nhwc_s32),
+    conv1 keeps its bias, the time embedding is folded into norm2 (ed_groupnorm_nhwc's chan_bias), conv2's result and the shortcut's are
+    summed in fp32 by torch"""
+    M, ops = mods
+    blk, x, emb, ref, spec = _resnet(M, cin, cout, dtype, cl=True)
+    x32 = _as_stream(x)
+    folded = []
+    inner = ops.groupnorm_nhwc
+
+    def spy(*a, **k):
+        folded.append((k.get("chan_bias") is not None, k.get("conv_bias") is not None))
+        return inner(*a, **k)
+    monkeypatch.setattr(ops, "groupnorm_nhwc", spy)
+    name = f"ResnetBlock2D fp32 stream, default policy {cin}->{cout} {_name(dtype)}"
+    stats = judge(ops, name, lambda: blk(x32, emb), spec, ref, expect=("ed_groupnorm_nhwc_s32", "ed_groupnorm_nhwc"),
+                  forbid=CONV3X3_KERNELS + ("ed_bias_residual_add", "ed_groupnorm"), library_conv=True)
+    assert stats["ed_groupnorm_nhwc_s32"][0] == 1 and stats["ed_groupnorm_nhwc"][0] == 1, stats
+    assert folded and all(f == (True, False) for f in folded), folded     # the time embedding in the kernel; conv1's bias stayed in conv1
+    with torch.no_grad():
+        out = blk(x32, emb)
+    assert out.dtype == torch.float32 and ops.is_nhwc(out)
+    _beside_plain(name, lambda: blk(x32, emb), lambda: blk(x, emb), ref)
+
+
+@pytest.mark.parametrize("dtype", HALF, ids=_name)
+@pytest.mark.parametrize("policy", ["default", "admitted"])
+def test_resnet_with_small_groups_on_the_fp32_residual_stream(policy, dtype, mods, monkeypatch):
+    """64 -> 128 channels, 2 and 4 channels per group, on the stream: torch's GroupNorm with fp32 parameters and the library's
+    convolutions, nothing of ours launched.  With the GEMM kernels admitted no normalisation or convolution kernel takes the block either;
+    the one launch is the 1x1 shortcut, which the stream path runs as a linear over the token view of the narrowed stream (ed_linear)."""
+    M, ops = mods
+    if policy == "admitted":
+        _admit(monkeypatch, ops)
+    blk, x, emb, ref, spec = _resnet(M, 64, 128, dtype, cl=True)
+    x32 = _as_stream(x)
+    name = f"ResnetBlock2D fp32 stream 64->128 (C/G < 8), {policy}, {_name(dtype)}"
+    stats = judge(ops, name, lambda: blk(x32, emb), spec, ref, library_conv=True)
+    assert set(stats) == ({"ed_linear"} if policy == "admitted" else set()), sorted(stats)
+    if stats:
+        assert stats["ed_linear"][0] == 1, stats
+    with torch.no_grad():
+        assert blk(x32, emb).dtype == torch.float32
+    _beside_plain(name, lambda: blk(x32, emb), lambda: blk(x, emb), ref)
+
+
+@pytest.mark.parametrize("dtype", HALF, ids=_name)
+@pytest.mark.parametrize("cin,cout", RES_SHAPES)
+def test_resnet_on_an_nchw_fp32_residual_stream(cin, cout, dtype, mods, admit, monkeypatch):
+    """CHANNELS_LAST off: an NCHW-contiguous fp32 stream and NCHW weights.  No channels-last kernel may take it (even with the GEMM kernels
+    admitted): torch's GroupNorm reads the stream, norm2 is the NCHW ed_groupnorm with the time embedding folded in"""
+    M, ops = mods
+    monkeypatch.setattr(M, "CHANNELS_LAST", False)
+    blk, x, emb, ref, spec = _resnet(M, cin, cout, dtype, cl=False)
+    x32 = _as_stream(x, cl=False)
+    name = f"ResnetBlock2D NCHW fp32 stream {cin}->{cout} {_name(dtype)}"
+    judge(ops, name, lambda: blk(x32, emb), spec, ref, expect=("ed_groupnorm",), forbid=NHWC_KERNELS + ("ed_linear", "ed_bias_residual_add"),
+          library_conv=True)
+    with torch.no_grad():
+        out = blk(x32, emb)
+    assert out.dtype == torch.float32 and out.is_contiguous()
+    _beside_plain(name, lambda: blk(x32, emb), lambda: blk(x, emb), ref)
+
+
+@pytest.mark.parametrize("dtype", HALF, ids=_name)
+@pytest.mark.parametrize("cout", [256, 320])
+def test_resnet_on_a_concatenation_of_two_fp32_streams(cout, dtype, mods, admit):
+    """forward_cat on fp32 x and skip: ed_groupnorm_nhwc_cat is a 16-bit kernel, so the concatenation is materialised (channels-last fp32)
+    and the block runs its stream path on it -- ed_groupnorm_nhwc_s32, the HIP convolutions, the 384 -> cout shortcut through ed_linear"""
+    M, ops = mods
+    c1, c2 = 256, 128
+    sd, gpu_sd, x, skip, emb, ref = _cat_case(c1, c2, cout, dtype)
+    blk = _load(M.ResnetBlock2D(c1 + c2, cout, TEMB), sd, dtype, cl=True)
+    x32, s32 = _as_stream(x), _as_stream(skip)
+    xc, sc = x.contiguous(memory_format=CL), skip.contiguous(memory_format=CL)
+    name = f"ResnetBlock2D.forward_cat on fp32 streams {c1}+{c2}->{cout} {_name(dtype)}"
+    closing = ("ed_conv3x3_nhwc_f32out",) if dtype == torch.float16 else ()
+    stats = judge(ops, name, lambda: blk.forward_cat(x32, s32, emb), lambda: S.resnet_cat(gpu_sd, "blk", x, skip, emb), ref,
+                  expect=("ed_groupnorm_nhwc_s32", "ed_groupnorm_nhwc", "ed_conv3x3_nhwc", "ed_linear") + closing,
+                  forbid=("ed_groupnorm_nhwc_cat", "ed_bias_residual_add") + (() if closing else ("ed_conv3x3_nhwc_f32out",)))
+    assert stats["ed_groupnorm_nhwc_s32"][0] == 1 and stats["ed_linear"][0] == 1, stats
+    with torch.no_grad():
+        out = blk.forward_cat(x32, s32, emb)
+        assert out.dtype == torch.float32 and ops.is_nhwc(out)
+        assert torch.equal(out, blk(torch.cat([x32, s32], 1), emb))
+    _beside_plain(name, lambda: blk.forward_cat(x32, s32, emb), lambda: blk.forward_cat(xc, sc, emb), ref)
+
+
+@pytest.mark.parametrize("dtype", HALF, ids=_name)
+@pytest.mark.parametrize("mode", ["default", "admitted"])
+@pytest.mark.parametrize("linear", [True, False], ids=["linear-proj", "conv-proj"])
+@pytest.mark.parametrize("C,heads", [(256, 4), (320, 8)], ids=["hd64", "hd40"])
+def test_transformer_2d_on_the_fp32_residual_stream(C, heads, linear, mode, dtype, mods, monkeypatch):
+    """Transformer2DModel, depth 2, on a channels-last fp32 stream: the GroupNorm reads it (ed_groupnorm_nhwc_s32), the token stream is
+    widened after proj_in, every LayerNorm is a stream kernel (ed_layernorm_s32 once, ed_add_layernorm_s32 for the five that follow an add),
+    the token stream is narrowed before proj_out and the closing add is torch's in fp32.  ``admitted``: the projections through ed_linear /
+    ed_geglu_gemm -- and with FUSED_RESIDUAL_LINEAR on as well no `x + branch` may ride in ed_linear's 16-bit residual epilogue while the
+    residual is fp32: the result is bit-identical to the run with the switch off."""
+    M, ops = mods
+    if mode == "admitted":
+        _admit(monkeypatch, ops)
+    monkeypatch.setattr(M, "FUSED_RESIDUAL_LINEAR", False)
+    sd, gpu_sd, x, ctx, ref = _transformer_case(C, heads, linear, dtype)
+    m = _load(M.Transformer2DModel(C, heads, 2, CROSS, linear), sd, dtype, cl=True)
+    x32, xc = _as_stream(x), x.contiguous(memory_format=CL)
+    expect = {"ed_groupnorm_nhwc_s32", "ed_layernorm_s32", "ed_add_layernorm_s32", "ed_flash_attention"}
+    forbid = {"ed_tokens_add_nchw", "ed_layernorm", "ed_add_layernorm", "ed_groupnorm", "ed_groupnorm_nhwc"}
+    if mode == "admitted":
+        expect |= {"ed_geglu_gemm", "ed_linear"}
+        forbid.add("ed_geglu")
+    else:
+        expect.add("ed_geglu")
+        forbid |= {"ed_geglu_gemm", "ed_linear"}
+    name = f"Transformer2DModel fp32 stream C={C} heads={heads} {'linear' if linear else 'conv'} projection, {mode}, {_name(dtype)}"
+    stats = judge(ops, name, lambda: m(x32, ctx), lambda: S.transformer_2d(gpu_sd, "blk", x, ctx, heads, 2, linear), ref,
+                  expect=expect, forbid=forbid, library_conv=not linear)
+    assert stats["ed_layernorm_s32"][0] == 1 and stats["ed_add_layernorm_s32"][0] == 5 and stats["ed_groupnorm_nhwc_s32"][0] == 1, stats
+    off = _deterministic(lambda: m(x32, ctx))        # (conv-proj reaches the library's 1x1 convolutions: see judge)
+    assert off.dtype == torch.float32 and ops.is_nhwc(off)
+    residuals = []
+    inner = ops.linear
+
+    def spy(*a, **k):
+        residuals.append(k.get("residual") is not None or len(a) > 3)
+        return inner(*a, **k)
+    monkeypatch.setattr(ops, "linear", spy)
+    monkeypatch.setattr(M, "FUSED_RESIDUAL_LINEAR", True)
+    ops.TIMER.start()
+    try:
+        on = _deterministic(lambda: m(x32, ctx))
+    finally:
+        on_stats = ops.TIMER.stop()
+    assert not any(residuals), "an fp32 residual rode in ed_linear's 16-bit epilogue"
+    assert (mode == "admitted") == bool(residuals)
+    assert torch.equal(on, off), (name, "FUSED_RESIDUAL_LINEAR changes the stream path")
+    assert on_stats["ed_add_layernorm_s32"][0] == 5 and "ed_layernorm" not in on_stats and "ed_add_layernorm" not in on_stats, on_stats
+    monkeypatch.setattr(M, "FUSED_RESIDUAL_LINEAR", False)
+    _beside_plain(name, lambda: m(x32, ctx), lambda: m(xc, ctx), ref)
+
+
+@pytest.mark.parametrize("dtype", HALF, ids=_name)
+@pytest.mark.parametrize("C", [128, 320])
+def test_samplers_on_the_fp32_residual_stream(C, dtype, mods, admit, monkeypatch):
+    """Downsample2D / Upsample2D on a stream: narrow, the same convolution kernels as on a 16-bit activation, widen -- exactly"""
+    M, ops = mods
+    monkeypatch.setattr(ops, "gemm_rows_mode", lambda *a: False)     # as test_samplers_on_the_convolution_main_loop
+    monkeypatch.setattr(M, "HIP_DOWNSAMPLE_CONV", True)
+    for kind, ctor, hw, fn, kernel in (("Downsample2D", lambda: M.Downsample2D(C), (32, 32), S.downsample, "ed_conv3x3_nhwc_s2"),
+                                       ("Upsample2D", lambda: M.Upsample2D(C), (16, 16), S.upsample, "ed_conv3x3_nhwc_up2x")):
+        sd = _rounded(ctor(), 500 + C, dtype)
+        ref_sd, gpu_sd = _sides(sd)
+        x64, x = _x(7, (3, C) + hw, dtype)
+        with torch.no_grad():
+            ref = fn(ref_sd, "blk", x64)
+        m = _load(ctor(), sd, dtype, cl=True)
+        xc, x32 = x.contiguous(memory_format=CL), _as_stream(x)
+        name = f"{kind}({C}) fp32 stream {_name(dtype)}"
+        stats = judge(ops, name, lambda: m(x32), lambda: fn(gpu_sd, "blk", x), ref, expect=(kernel,))
+        assert set(stats) == {kernel} and stats[kernel][0] == 1, stats
+        with torch.no_grad():
+            out, plain = m(x32), m(xc)
+        assert out.dtype == torch.float32 and plain.dtype == dtype
+        assert torch.equal(out, plain.float())       # widening is exact
+        _beside_plain(name, lambda: m(x32), lambda: m(xc), ref)
+
+
+@pytest.mark.parametrize("dtype", HALF, ids=_name)
+@pytest.mark.parametrize("fam", ["sd15", "sdxl"])
+def test_unet_forward_on_the_fp32_residual_stream(fam, dtype, mods):
+    """test_unet_forward's three cases with ``residual_fp32`` on, against the same fp64 outputs: conv_in's result is widened, every block
+    reads and writes the fp32 stream (ControlNet residuals are 16-bit tensors added onto fp32 skips), conv_norm_out reads it and the
+    output is the model dtype again.  Switched off again, the model must compute bit for bit what it computed before the switch: the
+    mode leaves nothing behind in the derived-weight caches."""
+    M, ops = mods
+    cfg, usd, _, i64, res, ref = _net_case(fam, dtype)
+    m = _load(M.UNet2DConditionModel(**cfg), usd, dtype, cl=M.CHANNELS_LAST)
+    gpu_sd = _sides(usd, "")[1]
+    i = _to_dev(i64, dtype)
+    down, mid = [d.to(DEV) for d in res[0]], res[1].to(DEV)
+    expect = {"ed_layernorm_s32", "ed_add_layernorm_s32", "ed_flash_attention"} | ({"ed_groupnorm_nhwc_s32"} if M.CHANNELS_LAST else set())
+    for case, t, extra, sx in (("per-row", i["t"], {}, ()), ("scalar", i["t"][0], {}, ()),
+                               ("residuals", i["t"], dict(down_block_additional_residuals=down, mid_block_additional_residual=mid), (down, mid))):
+        def run():
+            return m(i["sample"], t, encoder_hidden_states=i["context"], added_cond_kwargs=i["added"], **extra).sample
+        assert not getattr(m, "residual_fp32", False)
+        before = _deterministic(run)
+        m.residual_fp32 = True
+        try:
+            name = f"{fam} UNet fp32 stream {_name(dtype)}, {case}"
+            judge(ops, name, run, lambda: S.unet_forward(gpu_sd, cfg, i["sample"], t, i["context"], i["added"], *sx), ref[case],
+                  expect=expect, forbid=("ed_layernorm", "ed_add_layernorm"), whole=True, library_conv=True)
+            with torch.no_grad():
+                got = run()
+            assert got.dtype == dtype
+        finally:
+            m.residual_fp32 = False
+        after = _deterministic(run)
+        assert torch.equal(before, after), (name, "the plain mode computes something else after a stream32 forward")
+        e32, e16 = S.rel_l2([got], [ref[case]]), S.rel_l2([before], [ref[case]])
+        print(f"{name}: stream32 {e32:.3e} plain {e16:.3e} stream32/plain {e32 / max(e16, 1e-300):.2f}")
