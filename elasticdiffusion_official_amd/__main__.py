@@ -10,7 +10,9 @@ text_encoder*/ ...); without it the architecture is randomly initialised and the
 ``type=bool`` treats every non-empty string as True).  ``--condition_image FILE`` selects the ControlNet pipeline and is
 the already extracted condition by default; ``--process_condition true`` treats it as a raw photo like the reference's
 flag of the same name (resize to the reduced resolution, canny on the device / injected depth estimator) and saves the
-extracted condition as ``condition.png``.  ``--prediction_type``, ``--timestep_spacing`` and
+extracted condition as ``condition.png``.  ``--condition_image``, ``--controlnet_model`` and
+``--controlnet_conditioning_scale`` may be repeated, once per ControlNet, with ``--control_guidance_start`` /
+``--control_guidance_end`` giving each net its window of the steps; the conditions are then saved as ``condition_{n}.png``.  ``--prediction_type``, ``--timestep_spacing`` and
 ``--rescale_betas_zero_snr`` override what the snapshot's ``scheduler/scheduler_config.json`` says (or the SD defaults
 without ``--weights``); the reference takes these from the hub config only.  ``--guidance_rescale`` is diffusers' keyword of
 that name (0 = off), what such checkpoints are meant to be sampled with.  ``--sampler dpmsolver++`` (``--solver_order`` 1 / 2) samples with
@@ -80,12 +82,17 @@ def build_parser():
     ap.add_argument("--log_freq", type=int, default=5)
     ap.add_argument("--verbose", type=_bool, default=False)
     ap.add_argument("--weights", type=str, default=None, help="local HF snapshot directory (optional)")
-    ap.add_argument("--condition_image", type=str, default=None, help="condition image => ControlNet path (pre-processed "
-                    "unless --process_condition true)")
+    ap.add_argument("--condition_image", type=str, action="append", default=None, help="condition image => ControlNet path "
+                    "(pre-processed unless --process_condition true); repeat it, with --controlnet_model, once per ControlNet")
     ap.add_argument("--process_condition", type=_bool, default=False, help="true: --condition_image is a raw photo; resize it "
                     "and extract the canny / depth condition from it as the reference command line does (EDC:1390-1393)")
-    ap.add_argument("--controlnet_conditioning_scale", type=float, default=0.2)
-    ap.add_argument("--controlnet_model", type=str, default="depth")
+    ap.add_argument("--controlnet_conditioning_scale", type=float, action="append", default=None,
+                    help="default 0.2; once for all ControlNets or once per ControlNet")
+    ap.add_argument("--controlnet_model", type=str, action="append", default=None, help="default depth; once per --condition_image")
+    ap.add_argument("--control_guidance_start", type=float, action="append", default=None,
+                    help="fraction of the executed steps at which a ControlNet starts to act (default 0); once or once per ControlNet")
+    ap.add_argument("--control_guidance_end", type=float, action="append", default=None,
+                    help="fraction of the executed steps after which a ControlNet is released (default 1); once or once per ControlNet")
     ap.add_argument("--prediction_type", type=str, default=None, choices=["epsilon", "v_prediction"],
                     help="what the UNet predicts; default: the snapshot's scheduler_config.json, else epsilon")
     ap.add_argument("--timestep_spacing", type=str, default=None, choices=["leading", "linspace", "trailing"],
@@ -208,8 +215,26 @@ def _outpaint_borders(text):
     return pads
 
 
+def _control_flags(opt):
+    """The repeatable ControlNet flags after parsing: one occurrence (or none) leaves the scalar it always was; several
+    --condition_image make the Multi-ControlNet run -> the number of ControlNets (0 without one)."""
+    n = len(opt.condition_image or ())
+    for name, default in (("controlnet_model", "depth"), ("controlnet_conditioning_scale", 0.2), ("control_guidance_start", 0.0),
+                          ("control_guidance_end", 1.0)):
+        v = getattr(opt, name)
+        if v is None:
+            v = [default]
+        if len(v) not in (1, n) or (name == "controlnet_model" and n > 1 and len(v) != n):
+            raise SystemExit(f"--{name}: given {len(v)} times for {n} --condition_image")
+        setattr(opt, name, v[0] if len(v) == 1 and (n <= 1 or name != "controlnet_model") else v)
+    if n <= 1:
+        opt.condition_image = opt.condition_image[0] if n else None
+    return n
+
+
 def main(argv=None):
     opt = build_parser().parse_args(argv)
+    n_control = _control_flags(opt)
     if not 0.0 <= opt.guidance_rescale <= 1.0:
         raise SystemExit(f"--guidance_rescale must be in [0, 1], got {opt.guidance_rescale}")
     if opt.max_prompt_chunks < 1:
@@ -287,10 +312,12 @@ def main(argv=None):
         sd = ElasticDiffusionControlNet(device, opt.sd_version, opt.controlnet_model, verbose=opt.verbose,
                                         log_freq=opt.log_freq, view_batch_size=opt.view_batch_size,
                                         low_vram=opt.low_vram, **kw)
-        condition_image = Image.open(opt.condition_image)
+        condition_image = [Image.open(f) for f in opt.condition_image] if n_control > 1 else Image.open(opt.condition_image)
         if opt.process_condition:
             condition_image = sd.prepare_condition_image(condition_image, opt.H, opt.W)
         extra = dict(condition_image=condition_image, controlnet_conditioning_scale=opt.controlnet_conditioning_scale)
+        if opt.control_guidance_start != 0.0 or opt.control_guidance_end != 1.0:
+            extra.update(control_guidance_start=opt.control_guidance_start, control_guidance_end=opt.control_guidance_end)
     else:
         sd = ElasticDiffusion(device, opt.sd_version, verbose=opt.verbose, log_freq=opt.log_freq,
                               view_batch_size=opt.view_batch_size, low_vram=opt.low_vram, **kw)
@@ -337,7 +364,11 @@ def main(argv=None):
     for i, img in enumerate(imgs):
         img.save(f"{save_dir}/{i}.png")
     if opt.condition_image and opt.process_condition:
-        extra["condition_image"].save(f"{save_dir}/condition.png")  # the extracted condition, next to the images
+        if n_control > 1:
+            for n, img in enumerate(extra["condition_image"]):
+                img.save(f"{save_dir}/condition_{n}.png")
+        else:
+            extra["condition_image"].save(f"{save_dir}/condition.png")  # the extracted condition, next to the images
     for key, logged in image_log.items():  # ED:1201-1205: the verbose image log next to the images
         if isinstance(logged, dict):
             for label, img in logged.items():

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "elastic_hip.h"
 
@@ -1148,6 +1149,118 @@ k_softmax_rows_f32(float* __restrict__ x, int64_t cols, float scale_log2e, const
   for (int64_t i = 4 * nv + tid; i < cols; i += NT) row[i] = __builtin_amdgcn_exp2f(sc1(row[i], i) - gm) * inv;
 }
 
+// ---- Multi-ControlNet hand-off: out = skip + sum_n w[b, n] * r_n over a table of levels, ONE launch ------
+// A workgroup owns one tile of ED_CONTROL_TILE consecutive elements of one batch row of one level; it finds the level by a binary
+// search of its block index in the table's prefix sum of tile counts (as k_lora_merge does).  The batch row is uniform over the
+// workgroup, so are its weights: a closed net (w == 0) costs no load at all.  Streaming, no LDS, 64-bit element offsets.
+constexpr int CR_THREADS = 256;
+constexpr int CR_WORDS = ED_CONTROL_LEVEL_WORDS, CR_TILE = ED_CONTROL_TILE, CR_NETS = ED_CONTROL_MAX_NETS;
+enum { CR_SKIP = 0, CR_OUT, CR_COUNT, CR_B, CR_DTYPE, CR_RDTYPE, CR_TILE0, CR_ZERO, CR_RES0 };
+static_assert(CR_RES0 + CR_NETS == CR_WORDS && CR_TILE % (8 * CR_THREADS) == 0, "control table layout");
+
+__device__ __forceinline__ float cr_ld1(const void* p, int64_t i, int dtype) {
+  if (dtype == ED_F32) return ((const float*)p)[i];
+  if (dtype == ED_F16) return F16::to_f32(((const uint16_t*)p)[i]);
+  return BF16::to_f32(((const uint16_t*)p)[i]);
+}
+
+__device__ __forceinline__ void cr_st1(void* p, int64_t i, float v, int dtype) {
+  if (dtype == ED_F32) ((float*)p)[i] = v;
+  else if (dtype == ED_F16) ((uint16_t*)p)[i] = F16::from_f32(v);
+  else ((uint16_t*)p)[i] = BF16::from_f32(v);
+}
+
+// 8 consecutive elements from a 16-byte aligned address: one 16-byte access of a 16-bit type, two of fp32
+__device__ __forceinline__ void cr_ld8(const void* p, int64_t i, int dtype, float (&v)[8]) {
+  if (dtype == ED_F32) {
+    const float4 a = *reinterpret_cast<const float4*>((const float*)p + i);
+    const float4 b = *reinterpret_cast<const float4*>((const float*)p + i + 4);
+    v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w, v[4] = b.x, v[5] = b.y, v[6] = b.z, v[7] = b.w;
+    return;
+  }
+  const U16x8 u = *reinterpret_cast<const U16x8*>((const uint16_t*)p + i);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) v[e] = dtype == ED_F16 ? F16::to_f32(u.v[e]) : BF16::to_f32(u.v[e]);
+}
+
+__device__ __forceinline__ void cr_st8(void* p, int64_t i, int dtype, const float (&v)[8]) {
+  if (dtype == ED_F32) {
+    *reinterpret_cast<float4*>((float*)p + i) = make_float4(v[0], v[1], v[2], v[3]);
+    *reinterpret_cast<float4*>((float*)p + i + 4) = make_float4(v[4], v[5], v[6], v[7]);
+    return;
+  }
+  U16x8 u;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) u.v[e] = dtype == ED_F16 ? F16::from_f32(v[e]) : BF16::from_f32(v[e]);
+  *reinterpret_cast<U16x8*>((uint16_t*)p + i) = u;
+}
+
+struct ControlTable { int64_t words[ED_CONTROL_MAX_LEVELS * CR_WORDS]; };  // by value: 3 KiB of the 4 KiB argument space
+
+__global__ void __launch_bounds__(CR_THREADS)
+k_control_residuals(const ControlTable tab, int n_levels, int n_nets, const float* __restrict__ w) {
+  const int64_t* table = tab.words;  // kernel arguments: uniform, read through the scalar cache
+  const int64_t blk = blockIdx.x;
+  int lo = 0, hi = n_levels - 1;  // the last level whose first tile is <= this block (tile0 ascending, level 0 starts at 0)
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (table[(int64_t)mid * CR_WORDS + CR_TILE0] <= blk) lo = mid;
+    else hi = mid - 1;
+  }
+  const int64_t* T = table + (int64_t)lo * CR_WORDS;
+  const void* skip = reinterpret_cast<const void*>(T[CR_SKIP]);
+  void* out = reinterpret_cast<void*>(T[CR_OUT]);
+  const int64_t count = T[CR_COUNT];
+  const int dtype = (int)T[CR_DTYPE], rdtype = (int)T[CR_RDTYPE];
+  const int64_t tiles_per_row = (count + CR_TILE - 1) / CR_TILE;
+  const int64_t local = blk - T[CR_TILE0];
+  const int64_t b = local / tiles_per_row, e0 = (local - b * tiles_per_row) * CR_TILE;
+  const int len = (int)(count - e0 < CR_TILE ? count - e0 : CR_TILE);
+  const int64_t base = b * count + e0;
+
+  float wn[CR_NETS];
+  const void* res[CR_NETS];
+  int64_t ptrs = T[CR_SKIP] | T[CR_OUT];
+#pragma unroll
+  for (int n = 0; n < CR_NETS; ++n) {
+    wn[n] = n < n_nets ? w[b * n_nets + n] : 0.0f;
+    res[n] = reinterpret_cast<const void*>(T[CR_RES0 + n]);
+    ptrs |= T[CR_RES0 + n];
+  }
+  // count % 8 == 0: every batch row and every tile of it starts a multiple of 8 elements from the 16-byte aligned base
+  const bool wide = (count & 7) == 0 && (ptrs & 15) == 0;
+  if (wide) {
+    for (int i = threadIdx.x * 8; i < len; i += CR_THREADS * 8) {
+      float acc[8], r[8];
+      if (skip) {
+        cr_ld8(skip, base + i, dtype, acc);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] = 0.0f;
+      }
+#pragma unroll
+      for (int n = 0; n < CR_NETS; ++n) {
+        if (wn[n] != 0.0f) {
+          cr_ld8(res[n], base + i, rdtype, r);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) acc[e] = __fadd_rn(acc[e], __fmul_rn(wn[n], r[e]));
+        }
+      }
+      cr_st8(out, base + i, dtype, acc);
+    }
+  } else {
+    for (int i = threadIdx.x; i < len; i += CR_THREADS) {
+      float acc = skip ? cr_ld1(skip, base + i, dtype) : 0.0f;
+#pragma unroll
+      for (int n = 0; n < CR_NETS; ++n)
+        if (wn[n] != 0.0f) acc = __fadd_rn(acc, __fmul_rn(wn[n], cr_ld1(res[n], base + i, rdtype)));
+      cr_st1(out, base + i, acc, dtype);
+    }
+  }
+}
+
+inline bool cr_overlap(int64_t a, int64_t a_bytes, int64_t b, int64_t b_bytes) { return a < b + b_bytes && b < a + a_bytes; }
+
 inline int done() { return (int)hipGetLastError(); }
 
 }  // namespace
@@ -1502,6 +1615,45 @@ int64_t ed_groupnorm_nhwc_workspace(int N, int C, int HW, int G) {
   if (N <= 0 || C <= 0 || HW <= 0 || G <= 0) return 0;
   const GnPlan pl = gn_plan(N, C, HW);
   return ((int64_t)N * pl.nchunks * G * 2 + (int64_t)N * G * 2) * (int64_t)sizeof(float);
+}
+
+int ed_control_residuals(const int64_t* table_host, int n_levels, int n_nets, const float* w, int64_t n_tiles, void* stream) {
+  if (!table_host || !w || n_levels < 1 || n_levels > ED_CONTROL_MAX_LEVELS || n_nets < 1 || n_nets > CR_NETS ||
+      n_tiles < 1 || n_tiles > INT32_MAX || (((uintptr_t)w) & 3u) != 0)
+    return (int)hipErrorInvalidValue;
+  int64_t tile = 0;
+  const int64_t B = table_host[CR_B];
+  for (int l = 0; l < n_levels; ++l) {
+    const int64_t* T = table_host + (int64_t)l * CR_WORDS;
+    const int64_t dtype = T[CR_DTYPE], rdtype = T[CR_RDTYPE], count = T[CR_COUNT];
+    if ((dtype != ED_F32 && dtype != ED_F16 && dtype != ED_BF16) || (rdtype != ED_F32 && rdtype != ED_F16 && rdtype != ED_BF16))
+      return (int)hipErrorInvalidValue;
+    // skip / out and the residuals share a type, or 16-bit residuals join an fp32 stream; without a skip, out has the residuals' type
+    if (dtype != rdtype && (dtype != ED_F32 || !T[CR_SKIP])) return (int)hipErrorInvalidValue;
+    if (T[CR_B] != B || B < 1 || B > INT32_MAX || count < 1 || count > (((int64_t)1 << 46) / B) || T[CR_ZERO] != 0)
+      return (int)hipErrorInvalidValue;
+    const int64_t esz = dtype == ED_F32 ? 4 : 2, rsz = rdtype == ED_F32 ? 4 : 2;
+    const int64_t bytes = B * count * esz, rbytes = B * count * rsz;
+    if (!T[CR_OUT] || ((T[CR_OUT] | T[CR_SKIP]) & (esz - 1)) != 0) return (int)hipErrorInvalidValue;
+    if (T[CR_SKIP] && T[CR_SKIP] != T[CR_OUT] && cr_overlap(T[CR_SKIP], bytes, T[CR_OUT], bytes)) return (int)hipErrorInvalidValue;
+    for (int n = 0; n < CR_NETS; ++n) {
+      const int64_t r = T[CR_RES0 + n];
+      if (n >= n_nets) {
+        if (r) return (int)hipErrorInvalidValue;
+        continue;
+      }
+      if (!r || (r & (rsz - 1)) != 0 || cr_overlap(r, rbytes, T[CR_OUT], bytes)) return (int)hipErrorInvalidValue;
+    }
+    if (T[CR_TILE0] != tile) return (int)hipErrorInvalidValue;
+    tile += B * ((count + CR_TILE - 1) / CR_TILE);
+    if (tile > INT32_MAX) return (int)hipErrorInvalidValue;
+  }
+  if (tile != n_tiles) return (int)hipErrorInvalidValue;
+  ControlTable tab;
+  memset(&tab, 0, sizeof tab);
+  memcpy(tab.words, table_host, sizeof(int64_t) * CR_WORDS * (size_t)n_levels);
+  k_control_residuals<<<(unsigned)n_tiles, CR_THREADS, 0, (hipStream_t)stream>>>(tab, n_levels, n_nets, w);
+  return done();
 }
 
 }  // extern "C"

@@ -54,28 +54,35 @@ class GraphedForward:
         self.epoch += 1
 
     @staticmethod
-    def _key(shape, dtype, cond, t_shape=(), fresh_side=False, text=None, pooled=None):
+    def _key(shape, dtype, cond, t_shape=(), fresh_side=False, text=None, pooled=None, ctl=None):
         """One graph per (rows shape, dtype, condition rows, timestep shape, fresh side inputs, text shape, pooled shape): the
         timestep is a 0-d tensor when all rows share it and a per-row vector when the rows of several images in flight were
         fused into one batch.  The text / pooled shapes (None when absent) keep a prompt of two or three 77-token chunks from
-        being copied into the static text rows -- and the hoisted cross-attention k|v -- of a graph captured for another length."""
+        being copied into the static text rows -- and the hoisted cross-attention k|v -- of a graph captured for another length.
+        ``ctl`` = (open ControlNet indices, per-row weights) on the Multi-ControlNet path: the SET of open nets is part of the key
+        -- two different single nets both have 3 condition channels, the condition shape alone would replay one net's graph for
+        the other -- the weights are not: they are data (``ent["w"]``)."""
         return (tuple(shape), dtype, None if cond is None else (tuple(cond.shape), cond.dtype), tuple(t_shape), bool(fresh_side),
-                None if text is None else tuple(text.shape), None if pooled is None else tuple(pooled.shape))
+                None if text is None else tuple(text.shape), None if pooled is None else tuple(pooled.shape),
+                None if ctl is None else (tuple(ctl[0]), tuple(ctl[1].shape)))
 
-    def input_rows(self, shape, dtype, device, cond=None, text=None, pooled=None):
+    def input_rows(self, shape, dtype, device, cond=None, text=None, pooled=None, ctl=None):
         """The static model-input tensor for this batch shape and these side inputs (allocated on first request; 0-d timestep)."""
         if not self.enabled:
             return torch.empty(shape, dtype=dtype, device=device)
-        key = self._key(shape, dtype, cond, text=text, pooled=pooled)
+        key = self._key(shape, dtype, cond, text=text, pooled=pooled, ctl=ctl)
         ent = self.entries.get(key)
         if ent is None:
             ent = {"x": torch.empty(shape, dtype=dtype, device=device), "graph": None, "epoch": -1, "eager": False}
             self.entries[key] = ent
         return ent["x"]
 
-    def _capture(self, ent, t, text, pooled, cond, fresh_side=False):
+    def _capture(self, ent, t, text, pooled, cond, fresh_side=False, ctl=None):
         x = ent["x"]
         ent["t"] = t.clone()
+        # Multi-ControlNet weights: a static device tensor of the entry, rewritten before every replay like ``t``
+        ent["w"] = None if ctl is None else ctl[1].clone()
+        more = () if ctl is None else ((tuple(ctl[0]), ent["w"]),)
         ent["text"] = None if text is None else text.clone()
         ent["pooled"] = None if pooled is None else pooled.clone()
         ent["cond"] = None if cond is None else cond.clone()
@@ -87,7 +94,7 @@ class GraphedForward:
         side.wait_stream(cur)
         with torch.cuda.stream(side):  # warm-up off the capture: MIOpen find / allocator growth happen here
             for _ in range(self.warmup_iters):
-                self.fwd(x, ent["t"], ent["text"], ent["pooled"], ent["cond"], ent["extra"])
+                self.fwd(x, ent["t"], ent["text"], ent["pooled"], ent["cond"], ent["extra"], *more)
         cur.wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         # No Python GC pass may run while the stream is capturing: collecting an old pipeline's hipGraph / memory pool
@@ -99,37 +106,41 @@ class GraphedForward:
             # thread_local: the RCCL watchdog thread polls events while we capture; in "global" mode that would
             # invalidate the capture on multi-GPU runs
             with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                ent["out"] = self.fwd(x, ent["t"], ent["text"], ent["pooled"], ent["cond"], ent["extra"])
+                ent["out"] = self.fwd(x, ent["t"], ent["text"], ent["pooled"], ent["cond"], ent["extra"], *more)
         finally:
             if gc_was_enabled:
                 gc.enable()
         ent["graph"] = graph
 
-    def __call__(self, x, t, text=None, pooled=None, cond=None, fresh_side=False):
+    def __call__(self, x, t, text=None, pooled=None, cond=None, fresh_side=False, ctl=None):
         """``fresh_side``: the text / pooled / condition rows differ from call to call (fused batches of several images
-        in flight), so they are copied into the graph's static buffers on every replay, not once per image."""
+        in flight), so they are copied into the graph's static buffers on every replay, not once per image.  ``ctl``: see ``_key``;
+        the forward receives it as one more argument."""
+        more = () if ctl is None else (ctl,)
         if not self.enabled:
-            return self.fwd(x, t, text, pooled, cond, None)
-        key = self._key(x.shape, x.dtype, cond, t.shape, fresh_side, text, pooled)
+            return self.fwd(x, t, text, pooled, cond, None, *more)
+        key = self._key(x.shape, x.dtype, cond, t.shape, fresh_side, text, pooled, ctl)
         ent = self.entries.get(key)
         if ent is None:
             ent = {"x": torch.empty_like(x), "graph": None, "epoch": -1, "eager": False}
             self.entries[key] = ent
         if ent["eager"]:
-            return self.fwd(x, t, text, pooled, cond, None)
+            return self.fwd(x, t, text, pooled, cond, None, *more)
         if x.data_ptr() != ent["x"].data_ptr():
             ent["x"].copy_(x)
         if ent["graph"] is None:
             try:
-                self._capture(ent, t, text, pooled, cond, fresh_side)
+                self._capture(ent, t, text, pooled, cond, fresh_side, ctl)
             except Exception as e:  # noqa: BLE001 -- a library that cannot be captured must not take the path down
                 warnings.warn(f"hipGraph capture failed for rows {tuple(x.shape)} ({type(e).__name__}: {e}); "
                               "running this shape eagerly")
                 ent["eager"] = True
                 torch.cuda.synchronize()
-                return self.fwd(x, t, text, pooled, cond, None)
+                return self.fwd(x, t, text, pooled, cond, None, *more)
             ent["epoch"] = self.epoch
         ent["t"].copy_(t)
+        if ctl is not None:
+            ent["w"].copy_(ctl[1])
         if fresh_side or ent["epoch"] != self.epoch:
             for name, src in (("text", text), ("pooled", pooled), ("cond", cond)):
                 if src is not None:

@@ -1120,7 +1120,12 @@ class UNet2DConditionModel(nn.Module):
         return self.ip_image_proj(clip_embeds.to(device=p.device, dtype=p.dtype))
 
     def forward(self, sample, timestep, encoder_hidden_states=None, added_cond_kwargs=None,
-                down_block_additional_residuals=None, mid_block_additional_residual=None, cross_kv=None, **_):
+                down_block_additional_residuals=None, mid_block_additional_residual=None, cross_kv=None, control_residuals=None, **_):
+        """``control_residuals`` = (per-net lists of raw down residuals, per-net raw mid residuals, w f32 [B, N]): the hand-off of
+        several ControlNets -- every skip and the mid-block output receive sum_n w[:, n] * r_n in ONE
+        ``ops.control_residuals`` launch, in place.  Mutually exclusive with the two ``*_additional_residual(s)`` keywords."""
+        if control_residuals is not None and (down_block_additional_residuals is not None or mid_block_additional_residual is not None):
+            raise ValueError("control_residuals and down_block_additional_residuals / mid_block_additional_residual exclude each other")
         x = sample.to(self.dtype)
         if CHANNELS_LAST and x.is_cuda and x.dtype != torch.float32:
             x = x.contiguous(memory_format=torch.channels_last)
@@ -1141,6 +1146,14 @@ class UNet2DConditionModel(nn.Module):
         x = self.mid_block(x, emb, ctx, cross_kv)
         if mid_block_additional_residual is not None:
             x = x + mid_block_additional_residual
+        if control_residuals is not None:
+            # every down block and the mid block have read their inputs: the skips and x are written in place (a skip that IS the
+            # mid block's output cannot occur, the mid block ends in a ResnetBlock2D that allocates its result)
+            downs, mids, w = control_residuals
+            if any(len(d) != len(skips) for d in downs) or len(mids) != len(downs):
+                raise ValueError(f"control_residuals: {len(skips)} skips, got residual lists of {[len(d) for d in downs]} and {len(mids)} mids")
+            summed = ops.control_residuals(skips + [x], [list(d) + [m] for d, m in zip(downs, mids)], w)
+            skips, x = summed[:-1], summed[-1]
         for blk in self.up_blocks:
             x = blk(x, skips, emb, ctx, cross_kv)
         x = self.conv_out(group_norm_act(self.conv_norm_out, x, silu=True))
@@ -1204,7 +1217,9 @@ class ControlNetModel(nn.Module):
     cross_attention_kv = UNet2DConditionModel.cross_attention_kv
 
     def forward(self, sample, timestep, encoder_hidden_states=None, controlnet_cond=None, conditioning_scale=1.0,
-                guess_mode=False, return_dict=False, added_cond_kwargs=None, cross_kv=None, **_):
+                guess_mode=False, return_dict=False, added_cond_kwargs=None, cross_kv=None, raw_residuals=False, **_):
+        """``raw_residuals``: return the zero-convolution outputs as they are, without the ``* conditioning_scale`` launches (the
+        weights of ``UNet2DConditionModel.forward(control_residuals=)`` take the scale's place)"""
         x = sample.to(self.dtype)
         cond = controlnet_cond.to(self.dtype)
         if CHANNELS_LAST and x.is_cuda and x.dtype != torch.float32:
@@ -1218,6 +1233,8 @@ class ControlNetModel(nn.Module):
             x, outs = blk(x, emb, ctx, cross_kv)
             skips.extend(outs)
         x = self.mid_block(x, emb, ctx, cross_kv)
+        if raw_residuals:
+            return [conv(s) for conv, s in zip(self.controlnet_down_blocks, skips)], self.controlnet_mid_block(x)
         down = [conv(s) * conditioning_scale for conv, s in zip(self.controlnet_down_blocks, skips)]
         mid = self.controlnet_mid_block(x) * conditioning_scale
         return down, mid
@@ -1522,3 +1539,24 @@ def build_models(sd_version, device="cuda", dtype=None, weights=None, vae_dtype=
             m = m.to(memory_format=torch.channels_last)
         out.append(m)
     return tuple(out)
+
+
+def build_controlnet(sd_version, device="cuda", dtype=None, weights=None, index=0, seed=0, small=False):
+    """ControlNet number ``index`` of a Multi-ControlNet, built as ``build_models`` builds the first: from the
+    snapshot's subfolder ``controlnet`` (index 0), ``controlnet_1``, ``controlnet_2``, ... (diffusers' ``MultiControlNetModel`` layout)
+    where it exists, seeded otherwise."""
+    cn_cfg = unet_config(family(sd_version), small, 4)
+    dtype = dtype or DEFAULT_MODEL_DTYPE
+    with torch.device("meta"):
+        cn = ControlNetModel(cn_cfg)
+    cn = cn.to_empty(device=device)
+    sub = "controlnet" if index == 0 else f"controlnet_{index}"
+    f = os.path.join(weights, sub, "diffusion_pytorch_model.safetensors") if weights else None
+    if f and os.path.isfile(f):
+        load_weights(cn, f)
+    else:
+        _seeded_init(cn, seed + 2 + index)
+    cn = cn.to(dtype=dtype).eval().requires_grad_(False)
+    if CHANNELS_LAST and dtype != torch.float32:
+        cn = cn.to(memory_format=torch.channels_last)
+    return cn

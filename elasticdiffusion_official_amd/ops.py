@@ -1,6 +1,7 @@
 """Torch-tensor wrappers over the C ABI (include/elastic_hip.h).  PyTorch is only plumbing here: it owns the device
 buffers and the stream; every wrapper validates its arguments, passes raw device pointers and raises on a HIP
-error.  No wrapper has a fallback path -- a tensor that is not on a ROCm device is an error."""
+error.  No wrapper has a fallback path -- a tensor that is not on a ROCm device is an error.  (One stated exception:
+``control_residuals`` runs the torch op sequence it replaces for a level whose tensors do not share dense strides, and for host tensors.)"""
 import math
 
 import torch
@@ -2127,3 +2128,95 @@ def lora_merge(table):
                 _reject(f"lora_merge: up {tuple(up.shape)} / down {tuple(down.shape)} do not fit a weight of {tuple(base.shape)}")
     _call("ed_lora_merge", host.data_ptr(), p_dev, table.n_tensors, table.n_adapters, table.n_tiles, _stream())
     TIMER.note_work("ed_lora_merge", flops=table.flops, nbytes=table.nbytes)
+
+
+# ---- Multi-ControlNet hand-off -------------------------------------------------------------------------
+CONTROL_MAX_NETS = 4        # ED_CONTROL_MAX_NETS
+CONTROL_MAX_LEVELS = 32     # ED_CONTROL_MAX_LEVELS
+CONTROL_LEVEL_WORDS = 12    # ED_CONTROL_LEVEL_WORDS
+CONTROL_TILE = 4096         # ED_CONTROL_TILE
+_CONTROL_PAIRS = {(torch.float16, torch.float16), (torch.bfloat16, torch.bfloat16), (torch.float32, torch.float32),
+                  (torch.float32, torch.float16), (torch.float32, torch.bfloat16)}  # (skip / out, residuals)
+
+
+def control_residuals_torch(skip, residuals, w, out_dtype=None):
+    """One level of ``control_residuals`` as the torch op sequence it replaces: ``acc = f32(skip)`` (or +0), then per net in order
+    ``acc = acc + w[:, n] * f32(r_n)`` for the batch rows whose weight is not zero, one cast at the end.  Any device, any strides."""
+    r0 = residuals[0]
+    acc = torch.zeros(r0.shape, dtype=torch.float32, device=r0.device) if skip is None else skip.float()
+    for n, r in enumerate(residuals):
+        wn = w[:, n].to(device=r.device, dtype=torch.float32).view(-1, *([1] * (r.dim() - 1)))
+        acc = torch.where(wn != 0, acc + wn * r.float(), acc)
+    return acc.to(out_dtype or (r0.dtype if skip is None else skip.dtype))
+
+
+def _control_dense(t):
+    return t.is_contiguous() or (t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last))
+
+
+def control_table(levels, n_nets):
+    """The descriptor table of one ``ed_control_residuals`` launch (layout: include/elastic_hip.h) for ``levels`` = [(skip or None,
+    out, [r_0 .. r_{N-1}])] -> (host int64 tensor, n_tiles)."""
+    words, tile = [], 0
+    for skip, out, rs in levels:
+        B = int(out.shape[0])
+        count = out.numel() // B
+        words += [0 if skip is None else skip.data_ptr(), out.data_ptr(), count, B, _DTYPE[out.dtype], _DTYPE[rs[0].dtype], tile, 0]
+        words += [r.data_ptr() for r in rs] + [0] * (CONTROL_MAX_NETS - n_nets)
+        tile += B * ((count + CONTROL_TILE - 1) // CONTROL_TILE)
+    return torch.tensor(words, dtype=torch.int64), tile
+
+
+def control_residuals(skips, residuals, w, outs=None):
+    """The hand-off of N ControlNets' residuals to the UNet: for every level l,
+    ``out[l] = skip[l] + sum_n w[:, n] * residuals[n][l]`` -- fp32 products and sums in net order, one rounding to the type of the
+    skip -- in ONE ``ed_control_residuals`` launch over all levels.  ``skips``: list of tensors, entries (or the whole list) may be
+    None: the level is then the weighted sum alone, in the residuals' type.  ``residuals``: per net, the list of its raw residuals.
+    ``w``: f32 [B, N] on the device, one weight per batch row and net; a zero leaves the term out and the residual unread.
+    ``outs``: per level a tensor to write, or None = in place into the skip (a fresh tensor where there is no skip).
+    Returns the list of outputs.  The tensors of a level must be dense with identical strides (contiguous or channels-last alike);
+    a level where they are not runs ``control_residuals_torch``, and so does every level of tensors that are not on a ROCm device."""
+    N = len(residuals)
+    if not 1 <= N <= CONTROL_MAX_NETS:
+        raise ValueError(f"control_residuals: 1 .. {CONTROL_MAX_NETS} ControlNets, got {N}")
+    L = len(residuals[0])
+    skips = [None] * L if skips is None else list(skips)
+    outs = [None] * L if outs is None else list(outs)
+    if L < 1 or any(len(r) != L for r in residuals) or len(skips) != L or len(outs) != L:
+        raise ValueError("control_residuals: every net, the skips and the outputs must list the same levels")
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or w.dim() != 2 or w.shape[1] != N:
+        raise ValueError(f"control_residuals: w must be a float32 [B, {N}] tensor")
+    B = int(w.shape[0])
+    result, fused = [None] * L, []
+    for l in range(L):
+        rs, skip = [residuals[n][l] for n in range(N)], skips[l]
+        out = outs[l] if outs[l] is not None else (skip if skip is not None else torch.empty_like(rs[0]))
+        like = rs + [out] + ([] if skip is None else [skip])
+        if any(t.shape != out.shape or t.device != out.device for t in like) or out.shape[0] != B or out.numel() == 0:
+            raise ValueError(f"control_residuals: level {l}: skip, residuals and output must share one shape with {B} batch rows "
+                             "and one device")
+        if any(r.dtype != rs[0].dtype for r in rs) or (skip is not None and skip.dtype != out.dtype) or \
+                (out.dtype, rs[0].dtype) not in _CONTROL_PAIRS or (skip is None and out.dtype != rs[0].dtype):
+            raise ValueError(f"control_residuals: level {l}: unsupported types (skip / out {out.dtype}, residuals "
+                             f"{[r.dtype for r in rs]})")
+        lo, hi = out.data_ptr(), out.data_ptr() + out.numel() * out.element_size()
+        if any(r.data_ptr() < hi and lo < r.data_ptr() + r.numel() * r.element_size() for r in rs):
+            raise ValueError(f"control_residuals: level {l}: the output overlaps a residual")
+        result[l] = out
+        if out.is_cuda and w.is_cuda and all(_control_dense(t) and t.stride() == out.stride() for t in like):
+            fused.append((skip, out, rs))
+        else:
+            out.copy_(control_residuals_torch(skip, rs, w, out.dtype))
+    for i in range(0, len(fused), CONTROL_MAX_LEVELS):  # (a UNet has 10 -- 13 levels: one launch)
+        part = fused[i:i + CONTROL_MAX_LEVELS]
+        host, n_tiles = control_table(part, N)
+        p_w = _dev(w, torch.float32, "w")
+        for skip, out, rs in part:
+            for t in rs + [out] + ([] if skip is None else [skip]):
+                if t.device != w.device:
+                    _reject(f"control_residuals: a level lives on {t.device} but w on {w.device}")
+        nbytes = sum(out.numel() * ((0 if skip is None else out.element_size()) + out.element_size() + N * rs[0].element_size())
+                     for skip, out, rs in part)
+        _call("ed_control_residuals", host.data_ptr(), len(part), N, p_w, n_tiles, _stream())
+        TIMER.note_work("ed_control_residuals", nbytes=float(nbytes))
+    return result

@@ -185,6 +185,39 @@ def check_inpaint_unet_arguments(in_channels, init_image=None, mask_image=None, 
     return True
 
 
+def control_keep(n_steps, start, end):
+    """diffusers 0.21.4's ``controlnet_keep`` for ``n_steps`` executed timesteps and per-net windows ``start`` / ``end`` (lists of N
+    floats): keep[i][n] = 1.0 - float(i / T < start[n] or (i + 1) / T > end[n]), in Python floats exactly so."""
+    return [[1.0 - float(i / n_steps < s or (i + 1) / n_steps > e) for s, e in zip(start, end)] for i in range(n_steps)]
+
+
+def check_control_arguments(n_nets, nets_listed, scale, start=0.0, end=1.0, condition_image=None):
+    """The argument rules of Multi-ControlNet and guidance windows (diffusers 0.21.4's ``check_inputs``), pure
+    host code -> None for today's single-net path (one net that was not given as a list, a scalar scale, the default window), else
+    (scales, starts, ends), three lists of ``n_nets`` floats.  ValueError: list lengths other than the number of nets, more than
+    ``ops.CONTROL_MAX_NETS`` nets, a window outside 0 <= start < end <= 1, a list of condition images without a list of as many nets."""
+    if isinstance(condition_image, (list, tuple)) and (not nets_listed or len(condition_image) != n_nets):
+        raise ValueError(f"{len(condition_image)} condition images for " +
+                         (f"{n_nets} ControlNets" if nets_listed else "a ControlNet that was not given as a list (controlnet=[...])"))
+    listed = [isinstance(v, (list, tuple)) for v in (scale, start, end)]
+    if not nets_listed and not any(listed) and float(start) == 0.0 and float(end) == 1.0:
+        return None
+    if n_nets < 1:
+        raise ValueError("controlnet_conditioning_scale lists / control_guidance_start / control_guidance_end need a ControlNet")
+    if n_nets > ops.CONTROL_MAX_NETS:
+        raise ValueError(f"at most {ops.CONTROL_MAX_NETS} ControlNets, got {n_nets}")
+    out = []
+    for name, v, is_list in zip(("controlnet_conditioning_scale", "control_guidance_start", "control_guidance_end"),
+                                (scale, start, end), listed):
+        if is_list and len(v) != n_nets:
+            raise ValueError(f"{name} lists {len(v)} values for {n_nets} ControlNet{'s' if n_nets != 1 else ''}")
+        out.append([float(x) for x in v] if is_list else [float(v)] * n_nets)
+    for s0, e0 in zip(out[1], out[2]):
+        if not 0.0 <= s0 < e0 <= 1.0:  # (NaN fails every comparison)
+            raise ValueError(f"control guidance window must satisfy 0 <= start < end <= 1, got start {s0}, end {e0}")
+    return tuple(out)
+
+
 SCORE_PCA_KEYS = ("pca_cls_dir", "pca_uncond")  # the reference script's file names (pca_diffusion_scores.py:181, 196)
 
 
@@ -376,10 +409,13 @@ class _ModelCall:
     ``t`` (0-d device tensor) with per-row text / pooled / ControlNet-condition rows.  Programs are generators that
     yield these and receive the model output rows (see ``_phase_steps``): the driver decides whether a call runs on its
     own (one image in flight) or fused with the calls of other images (``generate_latents_interleaved``)."""
-    __slots__ = ("rows", "t", "text", "pooled", "cond", "direct")
+    __slots__ = ("rows", "t", "text", "pooled", "cond", "direct", "ctl")
 
-    def __init__(self, rows, t, text, pooled, cond=None, direct=False):
+    def __init__(self, rows, t, text, pooled, cond=None, direct=False, ctl=None):
         self.rows, self.t, self.text, self.pooled, self.cond, self.direct = rows, t, text, pooled, cond, direct
+        # Multi-ControlNet (section 31): (indices of the nets this call runs, f32 [n, len(indices)] per-row weights); ``cond``
+        # then holds those nets' condition rows stacked along the channels
+        self.ctl = ctl
 
 
 class _HostRng:
@@ -506,7 +542,12 @@ class ElasticDiffusion(nn.Module):
         if isinstance(self.vae, torch.nn.Module) and self.device.type == "cuda":
             from .models import prepare_vae_split
             prepare_vae_split(self.vae)     # split fp16 weights of the fp32 VAE's MFMA convolutions, built at load time
-        self.controlnet = self._model_layout(controlnet.to(device)) if controlnet is not None else None
+        # a LIST of ControlNets (even of one) takes the multi path of DESIGN.md section 31; ``self.controlnet`` stays the first net
+        self.controlnets_listed = isinstance(controlnet, (list, tuple))
+        nets = list(controlnet) if self.controlnets_listed else ([] if controlnet is None else [controlnet])
+        self.controlnets = [self._model_layout(cn.to(device)) for cn in nets]
+        self.controlnet = self.controlnets[0] if self.controlnets else None
+        self._check_controlnets()
         if scheduler is None:
             scheduler = DDIMSchedule.from_config_dir(weights) if weights else DDIMSchedule()  # ED:153
             scheduler = make_scheduler(scheduler, sampler, solver_order, float(eta))
@@ -539,6 +580,32 @@ class ElasticDiffusion(nn.Module):
         self.last_masked_image_latents = None  # zm of the last image on a 9-channel UNet (the blanked picture's scaled latent)
         self.last_score_pca = None     # the PCA maps of the last ``generate_latents(score_pca=True)``, else None
         self.last_region_weights = None  # f32 [n + 1,Hl,Wl] of the last run with ``regions`` (plane 0 the base prompt's), else None
+
+    def _check_controlnets(self):
+        """All nets of a Multi-ControlNet share one parameter dtype and the UNet's 4-channel family (latent channels, context width)"""
+        nets = self.controlnets
+        if not self.controlnets_listed:  # (a single net is taken as it always was)
+            return
+        if not 1 <= len(nets) <= ops.CONTROL_MAX_NETS:
+            raise ValueError(f"controlnet lists {len(nets)} nets: 1 .. {ops.CONTROL_MAX_NETS} are supported")
+        def sig(m):
+            p = next(m.parameters(), None) if isinstance(m, torch.nn.Module) else None
+            c = getattr(m, "config", None)
+            return (None if p is None else p.dtype, getattr(c, "in_channels", None), getattr(c, "cross_attention_dim", None),
+                    getattr(c, "block_out_channels", None))
+        if len(nets) > 1:
+            sigs = [sig(m) for m in nets]
+            if any(g != sigs[0] for g in sigs[1:]):
+                raise ValueError(f"the ControlNets of one pipeline must share dtype and model family, got {sigs}")
+        for m in nets:
+            c, u = getattr(m, "config", None), getattr(self.unet, "config", None)
+            for name in ("cross_attention_dim", "block_out_channels"):
+                a, b = getattr(c, name, None), getattr(u, name, None)
+                if a is not None and b is not None and (tuple(a) if isinstance(a, (list, tuple)) else a) != \
+                        (tuple(b) if isinstance(b, (list, tuple)) else b):
+                    raise ValueError(f"a ControlNet's {name} {a} does not match the UNet's {b}")
+            if getattr(c, "in_channels", 4) != 4:
+                raise ValueError(f"a ControlNet takes the 4 latent channels, got in_channels {c.in_channels}")
 
     @staticmethod
     def _model_layout(module):
@@ -950,6 +1017,9 @@ class ElasticDiffusion(nn.Module):
         out["unet"] = self.unet.cross_attention_kv(txt, out.get("unet"))
         if self.controlnet is not None and hasattr(self.controlnet, "cross_attention_kv"):
             out["controlnet"] = self.controlnet.cross_attention_kv(self._text_part(txt), out.get("controlnet"))
+            if len(self.controlnets) > 1:  # prepared per net, open or closed at this step (section 31)
+                more = out.get("controlnets_more") or [None] * (len(self.controlnets) - 1)
+                out["controlnets_more"] = [cn.cross_attention_kv(self._text_part(txt), m) for cn, m in zip(self.controlnets[1:], more)]
         return out
 
     def _text_part(self, txt):
@@ -957,8 +1027,11 @@ class ElasticDiffusion(nn.Module):
         ni = getattr(self.unet, "ip_tokens", 0)
         return txt[:, :txt.shape[1] - ni].contiguous() if ni else txt
 
-    def _forward_rows(self, x, t_dev, txt, pl, cond, text_kv=None):
-        """ED:413-426 / EDC:476-518 for an arbitrary batch of d x d rows (this is what a hipGraph captures)."""
+    def _forward_rows(self, x, t_dev, txt, pl, cond, text_kv=None, ctl=None):
+        """ED:413-426 / EDC:476-518 for an arbitrary batch of d x d rows (this is what a hipGraph captures).  ``ctl`` = (active
+        net indices, w f32 [rows, len(active)]): the Multi-ControlNet path -- ``cond`` holds the active
+        nets' condition rows stacked along the channels, every active net returns its raw residuals and ONE
+        ``ops.control_residuals`` launch hands sum_n w[:, n] * r_n to the UNet."""
         kw, ckw = {}, {}
         if self.sd_version.startswith("XL"):
             ids = self._time_ids.to(txt.dtype).expand(x.shape[0], -1)
@@ -966,16 +1039,44 @@ class ElasticDiffusion(nn.Module):
         if text_kv is not None:
             kw["cross_kv"] = text_kv["unet"]
             ckw["cross_kv"] = text_kv.get("controlnet")
-        if cond is not None:
+        if cond is not None and ctl is not None:
+            from . import models
+            active, w = ctl
+            cn_kw = {k: v for k, v in kw.items() if k != "cross_kv"}
+            downs, mids = [], []
+            for k, n in enumerate(active):
+                cn, nkw = self.controlnets[n], {}
+                if text_kv is not None and text_kv.get("controlnet") is not None:
+                    nkw["cross_kv"] = text_kv["controlnet"] if n == 0 else text_kv["controlnets_more"][n - 1]
+                if isinstance(cn, models.ControlNetModel):
+                    nkw["raw_residuals"] = True
+                c = cond if len(active) == 1 else cond[:, 3 * k:3 * k + 3].contiguous()
+                down, mid = cn(x, t_dev, encoder_hidden_states=self._text_part(txt), controlnet_cond=c, conditioning_scale=1.0,
+                               guess_mode=False, return_dict=False, **cn_kw, **nkw)
+                downs.append(list(down))
+                mids.append(mid)
+            if isinstance(self.unet, models.UNet2DConditionModel):
+                kw["control_residuals"] = (downs, mids, w)
+            else:  # a stand-in UNet takes the sums through the keywords it knows: the same launch without skips
+                sums = ops.control_residuals(None, [d + [m] for d, m in zip(downs, mids)], w)
+                kw["down_block_additional_residuals"], kw["mid_block_additional_residual"] = sums[:-1], sums[-1]
+        elif cond is not None:
             cn_kw = {k: v for k, v in kw.items() if k != "cross_kv"}
             down, mid = self.controlnet(x, t_dev, encoder_hidden_states=self._text_part(txt), controlnet_cond=cond,
                                         conditioning_scale=self._cn_scale, guess_mode=False, return_dict=False, **cn_kw, **ckw)
             kw["down_block_additional_residuals"], kw["mid_block_additional_residual"] = down, mid
         return self.unet(x, t_dev, encoder_hidden_states=txt, **kw)["sample"].contiguous()
 
-    def _run_model(self, x_rows, t_dev, text, pooled, cond_rows=None, fresh_side=False):
+    def _run_model(self, x_rows, t_dev, text, pooled, cond_rows=None, fresh_side=False, ctl=None):
         """Rows are sharded across ranks (sharding.py); each rank's share runs as one (graph-replayed) forward.
-        ``t_dev``: 0-d timestep shared by all rows, or one timestep per row (fused batches of several images)."""
+        ``t_dev``: 0-d timestep shared by all rows, or one timestep per row (fused batches of several images).  ``ctl``
+        (``_ModelCall.ctl``): its per-row weights shard with the rows, like a per-row timestep."""
+        if ctl is not None:
+            active, per_row = ctl[0], t_dev.dim() != 0
+
+            def fn(x, txt, pl, cond, *more):
+                return self._runner(x, more[0] if per_row else t_dev, txt, pl, cond, fresh_side, ctl=(active, more[-1]))
+            return self.sharder.run(fn, x_rows, text, pooled, cond_rows, *((t_dev,) if per_row else ()), ctl[1])
         if t_dev.dim() == 0:
             return self.sharder.run(lambda x, txt, pl, cond: self._runner(x, t_dev, txt, pl, cond, fresh_side),
                                     x_rows, text, pooled, cond_rows)
@@ -984,7 +1085,7 @@ class ElasticDiffusion(nn.Module):
 
     # ---- one estimation phase (ED:1016-1035 or ED:1043-1056) ---------------------------------------
     def _phase_steps(self, P, x, ti, K, g, drop_p, emb, cond=None, direct=True, rrg_w=None, rrg_norm=0.0, frames=None,
-                     rescale=None, extras=None, multistep=None, keep_scores=False, region_w=None, step_noise=None):
+                     rescale=None, extras=None, multistep=None, keep_scores=False, region_w=None, step_noise=None, ctl=None):
         """Generator: pre-model glue -> ``yield _ModelCall`` (receives the model output rows) -> post-model glue;
         returns (prev, x0, info).  ``direct``: assemble straight into the hipGraph's static input (one image in flight,
         one rank); otherwise into a scratch batch the driver concatenates / the sharder slices.  ``rrg_w``: this is the
@@ -1031,7 +1132,8 @@ class ElasticDiffusion(nn.Module):
         direct = direct and P.one_batch and self.sharder.world_size == 1
         if P.one_batch:
             shape = (n_g + n_v, CR, P.gpad.PH, P.gpad.PW)
-            rows = (self._runner.input_rows(shape, mdt, dev, None if cond is None else cond[K], *emb[K]) if direct
+            rows = (self._runner.input_rows(shape, mdt, dev, None if cond is None else cond[K], *emb[K],
+                                            ctl=None if ctl is None else ctl[K]) if direct
                     else torch.empty(shape, device=dev, dtype=mdt))
             g_rows, v_rows = rows[:n_g], rows[n_g:]
         else:
@@ -1062,14 +1164,15 @@ class ElasticDiffusion(nn.Module):
         t_dev = self._t_dev[ti]
         self.host_s["phase_total"] += time.perf_counter() - h0
         if P.one_batch:
-            out = yield _ModelCall(rows, t_dev, text, pooled, None if cond is None else cond[K], direct)
+            out = yield _ModelCall(rows, t_dev, text, pooled, None if cond is None else cond[K], direct,
+                                   None if ctl is None else ctl[K])
             g_out, v_out = out[:n_g], out[n_g:]
         else:
             g_out = yield _ModelCall(g_rows, t_dev, text[:n_g].contiguous(), pooled[:n_g].contiguous(),
-                                     None if cond is None else cond[K][0])
+                                     None if cond is None else cond[K][0], ctl=None if ctl is None else ctl[K][0])
             g_out = g_out.clone()  # the two calls may share one graph output buffer when their shapes coincide
             v_out = yield _ModelCall(v_rows, t_dev, text[n_g:].contiguous(), pooled[n_g:].contiguous(),
-                                     None if cond is None else cond[K][1])
+                                     None if cond is None else cond[K][1], ctl=None if ctl is None else ctl[K][1])
         h0 = time.perf_counter()
         uncond_last = torch.empty(B, C, P.h, P.w, device=dev, dtype=torch.float32)
         low_dir = torch.empty(B, C, P.h, P.w, device=dev, dtype=torch.float32)
@@ -1165,7 +1268,7 @@ class ElasticDiffusion(nn.Module):
         try:
             call = next(program)
             while True:
-                call = program.send(self._run_model(call.rows, call.t, call.text, call.pooled, call.cond))
+                call = program.send(self._run_model(call.rows, call.t, call.text, call.pooled, call.cond, ctl=call.ctl))
         except StopIteration as stop:
             return stop.value
 
@@ -1183,6 +1286,42 @@ class ElasticDiffusion(nn.Module):
         return out
 
     # ---- ControlNet condition rows (EDC:457-461, 932-949) -- constant over the whole image ------------
+    def _control_rows(self, S, condition_image, B, ckw):
+        """Multi-ControlNet (section 31): ``_condition_rows`` per net, then -> ``at(step)``: (cond, ctl) of the executed step --
+        cond = {K: the rows of the nets open at that step stacked along the channels}, ctl = {K: (their indices, per-row weights
+        f32 [rows, n_open])}; (None, None) when every net is closed (the step is a plain UNet forward).  Steps with equal
+        weights share their tensors."""
+        imgs = list(condition_image) if isinstance(condition_image, (list, tuple)) else [condition_image]
+        N = len(self.controlnets)
+        if len(imgs) != N:
+            raise ValueError(f"{len(imgs)} condition image{'s' if len(imgs) != 1 else ''} for {N} ControlNet{'s' if N != 1 else ''}")
+        per_net = [self._condition_rows(S.P, im, B, S.Ks, **ckw) for im in imgs]
+        cache = {}
+
+        def build(weights):
+            active = tuple(n for n, v in enumerate(weights) if v != 0)
+            if not active:
+                return None, None
+            wv = torch.tensor([[float(weights[n]) for n in active]], dtype=torch.float32).to(self.device)
+            cond, ctl = {}, {}
+            for K in S.Ks:
+                parts = [per_net[n][K] for n in active]
+                if S.P.one_batch:
+                    cond[K] = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1).contiguous()
+                    ctl[K] = (active, wv.expand(cond[K].shape[0], -1).contiguous())
+                else:
+                    cond[K] = tuple(parts[0][j] if len(parts) == 1 else torch.cat([q[j] for q in parts], dim=1).contiguous()
+                                    for j in (0, 1))
+                    ctl[K] = tuple((active, wv.expand(c.shape[0], -1).contiguous()) for c in cond[K])
+            return cond, ctl
+
+        def at(step):
+            weights = S.control[step]
+            if weights not in cache:
+                cache[weights] = build(weights)
+            return cache[weights]
+        return at
+
     def _condition_rows(self, P, cond_img, B, Ks, copies=2):
         s = self.vae_scale_factor
         cond_img = cond_img.to(self.device, torch.float32).contiguous()
@@ -1415,11 +1554,13 @@ class ElasticDiffusion(nn.Module):
     # ---- the loop (ED:953-1078) --------------------------------------------------------------------
     def _setup_run(self, height, width, num_inference_steps, guidance_scale, resampling_steps, new_p, rrg_stop_t,
                    rrg_init_weight, rrg_scherduler_cls, cosine_scale, repaint_sampling, controlnet_conditioning_scale,
-                   guidance_rescale=0.0, strength=1.0):
+                   guidance_rescale=0.0, strength=1.0, control_guidance_start=0.0, control_guidance_end=1.0):
         """Everything of one ``generate_image`` call that does not depend on the prompt, the seed or the condition
         image: geometry tables, schedules, the noised pad-background frames.  Shared by all images in flight."""
         inpaint9 = self.unet.config.in_channels == INPAINT_IN_CHANNELS  # (the callers checked the arguments: _check_inpaint9)
         ops.rescale_coefficients(guidance_rescale)  # ValueError outside [0, 1], before anything is launched
+        control = check_control_arguments(len(self.controlnets), self.controlnets_listed, controlnet_conditioning_scale,
+                                          control_guidance_start, control_guidance_end)  # ValueError likewise
         t_start = DDIMSchedule.img2img_window(num_inference_steps, strength)  # ValueError likewise
         self._mark("start")
         self.host_s = {"picks": 0.0, "phase_total": 0.0, "noise": 0.0, "stager_wait": 0.0}
@@ -1457,9 +1598,16 @@ class ElasticDiffusion(nn.Module):
         self._vframes = self._strip_frames(P.vpad, self._timesteps, C)
         self._mark("setup_done")
         S.Ks = sorted({R + 1, 1} if S.repaint else {R + 1})
-        if getattr(self, "_cn_scale", controlnet_conditioning_scale) != controlnet_conditioning_scale:
-            self._runner.entries.clear()  # the scale is a constant inside captured graphs
-        self._cn_scale = controlnet_conditioning_scale
+        S.control = None
+        if control is not None:
+            # Multi-ControlNet / guidance windows (section 31): per executed timestep the weights scale[n] * keep[i][n]; they are
+            # device data of the graphs (``GraphedForward``'s static ``w``), so no change of scale or window re-captures anything
+            keep = control_keep(S.T - t_start, control[1], control[2])
+            S.control = [tuple(np.float32(sc * k) for sc, k in zip(control[0], row)) for row in keep]
+        else:
+            if getattr(self, "_cn_scale", controlnet_conditioning_scale) != controlnet_conditioning_scale:
+                self._runner.entries.clear()  # the scale is a constant inside captured graphs
+            self._cn_scale = controlnet_conditioning_scale
         S.guidance, S.drop_p = guidance_scale, 1 - new_p
         S.guidance_rescale = float(guidance_rescale)  # 0 = plain CFG: the loop launches what it always launched
         S.norm = np.float32(2.0 / (C * P.Hl * P.Wl))
@@ -1567,11 +1715,18 @@ class ElasticDiffusion(nn.Module):
             emb = {K: self._embed_rows(K, P.views.V, un, co, pun, pco) for K in S.Ks}
         self.last_region_weights = region_w
         rg_kw = {} if region_w is None else dict(region_w=region_w)
-        cond = None
+        cond = control_at = None
         if condition_image is not None:
             if self.controlnet is None:
                 raise ValueError("condition_image given but no controlnet was supplied")
-            cond = self._condition_rows(P, condition_image, B, S.Ks, **({} if region_w is None else dict(copies=1 + len(cos))))
+            ckw = {} if region_w is None else dict(copies=1 + len(cos))
+            check_control_arguments(len(self.controlnets), self.controlnets_listed, 1.0, condition_image=condition_image)
+            if S.control is None:
+                cond = self._condition_rows(P, condition_image, B, S.Ks, **ckw)
+            else:
+                control_at = self._control_rows(S, condition_image, B, ckw)
+        elif S.control is not None:
+            raise ValueError("controlnet_conditioning_scale lists and guidance windows need condition_image")
         logs = {"x0": [], "rrg_x0": [], "init_low": None, "embeds": (un, co, pun, pco)} if self.verbose else None
         self._logs = logs
         rescale = None
@@ -1591,6 +1746,9 @@ class ElasticDiffusion(nn.Module):
             rrg_w = w_i if w_i > 10 else None  # ED:1061-1062
             two_phase = S.repaint and i < S.T - 1
             mapped = score_maps is not None and i % self.log_freq == 0
+            if control_at is not None:  # every phase of timestep i runs the nets open at i, with its weights
+                cond, ctl = control_at(i - S.t_start)
+                rg_kw["ctl"] = ctl
             prev, x0, info = yield from self._phase_steps(P, x, i, S.R + 1, S.guidance, S.drop_p, emb, cond, direct,
                                                           None if two_phase else rrg_w, S.norm, frames, rescale, extras, ms,
                                                           keep_scores=mapped, step_noise=nz, **rg_kw)
@@ -1649,8 +1807,14 @@ class ElasticDiffusion(nn.Module):
                          progress=_identity_progress, condition_image=None, controlnet_conditioning_scale=1.0,
                          trace=None, guidance_rescale=0.0, init_image=None, strength=1.0, mask_image=None, *, mask_blur=0.0,
                          mask_mode="binary", min_chunks=None, ip_adapter_image=None, ip_adapter_image_embeds=None,
-                         score_pca=False, regions=None, region_blur=0.0):
-        """``guidance_rescale`` in [0, 1] (diffusers' keyword; 0 = off): the std rescale of the guided model output of
+                         score_pca=False, regions=None, region_blur=0.0, control_guidance_start=0.0, control_guidance_end=1.0):
+        """``condition_image`` / ``controlnet_conditioning_scale`` / ``control_guidance_start`` / ``control_guidance_end``
+        (diffusers 0.21.4's Multi-ControlNet keywords): with a pipeline built on a LIST of N ControlNets,
+        ``condition_image`` is a list of N conditions and the other three are floats (applied to every net) or lists of N; net n
+        acts with weight ``scale[n]`` on the executed timesteps i with start[n] <= i / T and (i + 1) / T <= end[n] and is not run on
+        the others.  A single net given as such, with a scalar scale and the default window, runs the path it always ran.
+
+        ``guidance_rescale`` in [0, 1] (diffusers' keyword; 0 = off): the std rescale of the guided model output of
         arXiv 2305.08891 section 3.4, what zero-terminal-SNR / v-prediction checkpoints are meant to be sampled with
         (DESIGN.md section 17).
 
@@ -1709,7 +1873,7 @@ class ElasticDiffusion(nn.Module):
         self._check_inpaint9(height, width, init_image, mask_image, mask_mode)
         S = self._setup_run(height, width, num_inference_steps, guidance_scale, resampling_steps, new_p, rrg_stop_t,
                             rrg_init_weight, rrg_scherduler_cls, cosine_scale, repaint_sampling,
-                            controlnet_conditioning_scale, guidance_rescale, strength)
+                            controlnet_conditioning_scale, guidance_rescale, strength, control_guidance_start, control_guidance_end)
         self._runner.new_image()
         maps = {} if score_pca else None
         x = self._drive(self._program(S, prompts, negative_prompts, condition_image, trace, progress, direct=True,
@@ -1729,7 +1893,7 @@ class ElasticDiffusion(nn.Module):
                                      guidance_scale=10.0, resampling_steps=20, new_p=0.3, rrg_stop_t=0.2,
                                      rrg_init_weight=1000, rrg_scherduler_cls=CosineScheduler, cosine_scale=3.0,
                                      repaint_sampling=True, controlnet_conditioning_scale=1.0, on_done=None,
-                                     guidance_rescale=0.0, strength=1.0):
+                                     guidance_rescale=0.0, strength=1.0, control_guidance_start=0.0, control_guidance_end=1.0):
         """Several images of the SAME size / settings in flight at once (new; the reference has nothing like it).
 
         ``jobs`` = list of dicts {prompts, negative_prompts="", seed, condition_image=None, init_image=None,
@@ -1776,7 +1940,7 @@ class ElasticDiffusion(nn.Module):
             self._check_inpaint9(height, width, job.get("init_image"), job.get("mask_image"), job.get("mask_mode", "binary"))
         S = self._setup_run(height, width, num_inference_steps, guidance_scale, resampling_steps, new_p, rrg_stop_t,
                             rrg_init_weight, rrg_scherduler_cls, cosine_scale, repaint_sampling,
-                            controlnet_conditioning_scale, guidance_rescale, strength)
+                            controlnet_conditioning_scale, guidance_rescale, strength, control_guidance_start, control_guidance_end)
         self._runner.new_image()
         results = [None] * len(jobs)
         queue = list(range(len(jobs)))
@@ -1824,20 +1988,23 @@ class ElasticDiffusion(nn.Module):
                 groups = {}
                 for ent in live:
                     c = ent[3]
-                    groups.setdefault((tuple(c.rows.shape[1:]), c.cond is None, tuple(c.text.shape[1:])), []).append(ent)
+                    # (Multi-ControlNet: calls fuse when the same nets are open; their per-row weights ride along)
+                    groups.setdefault((tuple(c.rows.shape[1:]), c.cond is None, tuple(c.text.shape[1:]),
+                                       None if c.ctl is None else c.ctl[0]), []).append(ent)
                 for ents in groups.values():
                     calls = [e[3] for e in ents]
                     sizes = [c.rows.shape[0] for c in calls]
                     if len(calls) == 1:
                         c = calls[0]
-                        outs = [self._run_model(c.rows, c.t, c.text, c.pooled, c.cond, fresh_side=True)]
+                        outs = [self._run_model(c.rows, c.t, c.text, c.pooled, c.cond, fresh_side=True, ctl=c.ctl)]
                     else:
                         rows = torch.cat([c.rows for c in calls])
                         t = torch.cat([c.t.reshape(1).expand(n) for c, n in zip(calls, sizes)])
                         text = torch.cat([c.text for c in calls])
                         pooled = torch.cat([c.pooled for c in calls])
                         cond = None if calls[0].cond is None else torch.cat([c.cond for c in calls])
-                        outs = self._run_model(rows, t, text, pooled, cond, fresh_side=True).split(sizes)
+                        ctl = None if calls[0].ctl is None else (calls[0].ctl[0], torch.cat([c.ctl[1] for c in calls]))
+                        outs = self._run_model(rows, t, text, pooled, cond, fresh_side=True, ctl=ctl).split(sizes)
                     self.ticks += 1
                     for ent, out in zip(ents, outs):
                         j, prog, rng = ent[0], ent[1], ent[2]
@@ -2015,7 +2182,8 @@ class ElasticDiffusion(nn.Module):
                        progress=_default_progress, tiled_decoder=False, grid=False, guidance_rescale=0.0, *,
                        condition_image=None, controlnet_conditioning_scale=1.0, output_type="pil", init_image=None,
                        strength=1.0, mask_image=None, mask_blur=0.0, mask_mode="binary", composite=False,
-                       ip_adapter_image=None, ip_adapter_image_embeds=None, score_pca=False, regions=None, region_blur=0.0):
+                       ip_adapter_image=None, ip_adapter_image_embeds=None, score_pca=False, regions=None, region_blur=0.0,
+                       control_guidance_start=0.0, control_guidance_end=1.0):
         """ED:953-965 signature (ControlNet keywords of EDC:1120-1134 are keyword-only here), then ``guidance_rescale``
         (diffusers' keyword) and, keyword-only, ``init_image`` / ``strength`` / ``mask_image`` / ``mask_blur`` / ``mask_mode``
         (see ``generate_latents``) and ``composite``: paste every decoded picture over the 8-bit init picture through the
@@ -2039,7 +2207,8 @@ class ElasticDiffusion(nn.Module):
                                   controlnet_conditioning_scale, guidance_rescale=guidance_rescale, init_image=init_image,
                                   strength=strength, mask_image=mask_image, mask_blur=mask_blur, mask_mode=mask_mode,
                                   ip_adapter_image=ip_adapter_image, ip_adapter_image_embeds=ip_adapter_image_embeds,
-                                  score_pca=score_pca, regions=regions, region_blur=region_blur)
+                                  score_pca=score_pca, regions=regions, region_blur=region_blur,
+                                  control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end)
         dec = self.tiled_decode if tiled_decoder else self.decode_latents
         image_log = self._image_log(dec, guidance_scale, guidance_rescale) if self.verbose else {}  # ED:1092-1118 (before the final decode)
         if score_pca:
@@ -2115,6 +2284,13 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
 
     def __init__(self, device, sd_version="2.0", controlnet_model="canny", verbose=False, log_freq=5,
                  view_batch_size=1, low_vram=False, *, controlnet=None, depth_estimator=None, **kw):
+        kinds = list(controlnet_model) if isinstance(controlnet_model, (list, tuple)) else None
+        if kinds is not None and not 1 <= len(kinds) <= ops.CONTROL_MAX_NETS:
+            raise ValueError(f"controlnet_model lists {len(kinds)} kinds: 1 .. {ops.CONTROL_MAX_NETS} ControlNets are supported")
+        if kinds is not None and controlnet is not None and (not isinstance(controlnet, (list, tuple)) or len(controlnet) != len(kinds)):
+            raise ValueError(f"controlnet_model lists {len(kinds)} kinds: controlnet must list as many nets")
+        if kinds is None and isinstance(controlnet, (list, tuple)):
+            raise ValueError("a list of ControlNets needs controlnet_model to list their kinds, e.g. ['canny', 'depth']")
         if controlnet is None:
             from .models import build_models
             dev = torch.device(device)
@@ -2122,6 +2298,10 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
                                                  weights=kw.get("weights"))
             kw.setdefault("unet", unet)
             kw.setdefault("vae", vae)
+            if kinds is not None:  # one net per kind: the snapshot's subfolders controlnet, controlnet_1, ... (seeds 2, 3, ... without)
+                from .models import build_controlnet
+                controlnet = [controlnet] + [build_controlnet(sd_version, dev, kw.get("model_dtype"), kw.get("weights"), k)
+                                             for k in range(1, len(kinds))]
         super().__init__(device, sd_version, verbose, log_freq, view_batch_size, low_vram, controlnet=controlnet, **kw)
         self.controlnet_model = controlnet_model
         self.depth_estimator = depth_estimator
@@ -2130,6 +2310,13 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
         """EDC:1102-1117: a PIL image (or HWC uint8 array) at the reduced resolution -> the ControlNet condition, a PIL RGB
         image with three identical channels.  ``output_type="pt"`` (extra) returns the fp32 (1,3,H,W) condition tensor on
         the pipeline's device instead, without the PIL round trip."""
+        if isinstance(controlnet_model, (list, tuple)):  # kind by kind (Multi-ControlNet, DESIGN.md section 31)
+            imgs = list(condition_image) if isinstance(condition_image, (list, tuple)) else [condition_image] * len(controlnet_model)
+            if len(imgs) != len(controlnet_model):
+                raise ValueError(f"{len(imgs)} condition images for {len(controlnet_model)} ControlNet kinds")
+            return [self.process_condition_image(im, k, output_type=output_type) for im, k in zip(imgs, controlnet_model)]
+        if isinstance(condition_image, (list, tuple)):
+            raise ValueError("a list of condition images needs a list of ControlNet kinds")
         assert controlnet_model in ["canny", "depth"], f"processing for ControlNet: {controlnet_model} is not implemented"
         if output_type not in ("pil", "pt"):
             raise ValueError(f"output_type must be 'pil' or 'pt', got {output_type!r}")
@@ -2186,6 +2373,21 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
         estimator is a host callable and still receives a PIL image.  Any other PIL mode is resized by PIL on the host."""
         if output_type not in ("pil", "pt"):
             raise ValueError(f"output_type must be 'pil' or 'pt', got {output_type!r}")
+        if isinstance(self.controlnet_model, (list, tuple)):  # a list of photos (or one photo for every net) -> a list, kind by kind
+            kinds = list(self.controlnet_model)
+            imgs = list(image) if isinstance(image, (list, tuple)) else [image] * len(kinds)
+            if len(imgs) != len(kinds):
+                raise ValueError(f"{len(imgs)} condition images for {len(kinds)} ControlNets")
+            out = []
+            for im, kind in zip(imgs, kinds):
+                self.controlnet_model = kind
+                try:
+                    out.append(self.prepare_condition_image(im, height, width, output_type=output_type))
+                finally:
+                    self.controlnet_model = kinds
+            return out
+        if isinstance(image, (list, tuple)):
+            raise ValueError("a list of condition images needs a list of ControlNets")
         ds = self.get_downsample_size(height, width)
         h_px, w_px = ds[0] * self.vae_scale_factor, ds[1] * self.vae_scale_factor
         dev = self._device_image(image) if max(h_px, w_px) <= ops.RESIZE_MAX_DIM else None
@@ -2230,7 +2432,7 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
                        progress=_default_progress, tiled_decoder=False, grid=False, guidance_rescale=0.0, *,
                        output_type="pil", init_image=None, strength=1.0, mask_image=None, mask_blur=0.0, mask_mode="binary",
                        composite=False, ip_adapter_image=None, ip_adapter_image_embeds=None, score_pca=False, regions=None,
-                       region_blur=0.0):
+                       region_blur=0.0, control_guidance_start=0.0, control_guidance_end=1.0):
         check_region_arguments(regions, height, width, self.vae_scale_factor, region_blur, self.unet.config.in_channels)
         check_regions_sampler(regions, getattr(self, "scheduler", None))
         self._check_ip_adapter(ip_adapter_image, ip_adapter_image_embeds)
@@ -2242,7 +2444,12 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
             raise ValueError("condition_image is required (EDC:1183-1193)")
         h, w = self.get_downsample_size(height, width)
         s = self.vae_scale_factor
-        cond = self._to_condition_tensor(condition_image, h * s, w * s)
+        check_control_arguments(len(self.controlnets), self.controlnets_listed, controlnet_conditioning_scale,
+                                control_guidance_start, control_guidance_end, condition_image)
+        if isinstance(condition_image, (list, tuple)):
+            cond = [self._to_condition_tensor(c, h * s, w * s) for c in condition_image]
+        else:
+            cond = self._to_condition_tensor(condition_image, h * s, w * s)
         return super().generate_image(prompts, negative_prompts, height, width, num_inference_steps, guidance_scale,
                                       resampling_steps, new_p, rrg_stop_t, rrg_init_weight, rrg_scherduler_cls,
                                       cosine_scale, repaint_sampling, progress, tiled_decoder, grid, guidance_rescale,
@@ -2250,4 +2457,5 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
                                       output_type=output_type, init_image=init_image, strength=strength,
                                       mask_image=mask_image, mask_blur=mask_blur, mask_mode=mask_mode, composite=composite,
                                       ip_adapter_image=ip_adapter_image, ip_adapter_image_embeds=ip_adapter_image_embeds,
-                                      score_pca=score_pca, regions=regions, region_blur=region_blur)
+                                      score_pca=score_pca, regions=regions, region_blur=region_blur,
+                                      control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end)

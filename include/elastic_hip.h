@@ -923,6 +923,39 @@ int ed_groupnorm_f32_weighted(const void* x, const void* gamma, const void* beta
                               int W, int G, float eps, int act_silu, const float* wx, const float* wy, void* stream);
 int ed_softmax_rows_bias(void* x, int64_t rows, int64_t cols, float scale, const float* bias, void* stream);
 
+/*
+ * ---- Multi-ControlNet hand-off (an addition, still ABI v13).
+ *
+ * ed_control_residuals -- ONE launch adds the weighted residuals of up to ED_CONTROL_MAX_NETS ControlNets to every skip tensor of a
+ *   UNet forward and to its mid-block output.  A level is a dense tensor of B batch rows of `count` elements each, in whatever
+ *   memory order its tensors share (NCHW-contiguous or channels-last: the batch row is outermost in both).  For batch row b and
+ *   element i of a level, with w f32 [B, n_nets] in device memory:
+ *       acc = skip ? f32(skip[b, i]) : +0.0f
+ *       for n = 0 .. n_nets - 1, if w[b, n] != 0:   acc = fadd_rn(acc, fmul_rn(w[b, n], f32(r_n[b, i])))
+ *       out[b, i] = rn_dtype(acc)
+ *   -- a product and a sum each rounded to fp32 (no contraction), one rounding to the type of `out`: the torch fp32 sequence
+ *   `acc = acc + w * r`, bit for bit.  A zero weight leaves its term out and its residual UNREAD: a non-finite value in a closed
+ *   net does not reach the output.  All-zero weights copy the skip (or write +0).
+ *
+ *   The table is one array of int64 words in HOST memory, laid out in the manner of ed_lora_merge's; every word of it is checked
+ *   before anything is launched.  It has no device copy: the checked table travels BY VALUE in the kernel's arguments (at most
+ *   ED_CONTROL_MAX_LEVELS records, 3 KiB), so a launch captured into a hipGraph carries its table in the graph node and no
+ *   host-to-device copy has to be captured for tensors whose addresses exist only during the capture.  The pointers INSIDE the
+ *   table, and `w`, are device pointers.
+ *     words [12 l, 12 l + 12), l in [0, n_levels)                  -- level record:
+ *       0 skip    const void* or 0 (no skip: out = the weighted sum)   4 dtype   ED_F32 / ED_F16 / ED_BF16 of skip and out
+ *       1 out     void*; == skip (in place) or disjoint from it        5 rdtype  the residuals' type: == dtype, or 16-bit under an
+ *       2 count   elements per batch row, >= 1                                   ED_F32 dtype (fp32 residual stream); == dtype if skip == 0
+ *       3 B       batch rows, >= 1, the same in every level            6 tile0   sum of the tile counts of the levels before it
+ *       7 0 (reserved)         8 .. 11  r_n const void*, n < n_nets; 0 for n >= n_nets; none may overlap out
+ *   A level has B * ceil(count / ED_CONTROL_TILE) tiles; n_tiles is their sum over the table (the grid).  Accesses are 16 bytes
+ *   wide where count % 8 == 0 and every pointer of the level is 16-byte aligned, one element wide otherwise -- the same bits either
+ *   way.  A null or misaligned pointer, a dtype code or pair, a count, n_nets outside 1 .. ED_CONTROL_MAX_NETS, n_levels outside
+ *   1 .. ED_CONTROL_MAX_LEVELS, an overlap, a tile0 or an n_tiles that breaks these rules is hipErrorInvalidValue and nothing is launched.
+ */
+enum { ED_CONTROL_MAX_NETS = 4, ED_CONTROL_LEVEL_WORDS = 12, ED_CONTROL_TILE = 4096, ED_CONTROL_MAX_LEVELS = 32 };
+int ed_control_residuals(const int64_t* table_host, int n_levels, int n_nets, const float* w, int64_t n_tiles, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
