@@ -360,8 +360,8 @@ def _flash(ops, q, k, v, H, v_path):
 def test_flash_attention(dtype, B, H, Nq, Nk, v_path):
     """ed_flash_attention vs the fp32 reference; it must be as accurate as the library kernel it replaces (SDPA)."""
     from elasticdiffusion_official_amd import ops
-    if v_path == 8 and Nk > 96:
-        pytest.skip("the small-KV kernel takes Nk <= 96")
+    if v_path == 8 and Nk > ops.SMALLKV_MAX_KEYS:
+        pytest.skip(f"the small-KV kernel takes Nk <= {ops.SMALLKV_MAX_KEYS}")
     if v_path == 6 and Nk < 128:
         pytest.skip("the exponent-domain kernel takes Nk >= 128 (ops.flash_prescale)")
     if v_path in (7, 9, 10) and Nk < 64:
