@@ -32,7 +32,8 @@ and a mask, and conditions on the mask and the blanked picture instead of pastin
 (DESIGN.md section 23); SCALE defaults to 1.
 ``--ip_adapter PATH[:SCALE]`` installs a base IP-Adapter and takes the image prompt either as a picture,
 ``--ip_adapter_image FILE`` with ``--image_encoder DIR`` (a local CLIPVisionModelWithProjection), or as CLIP image embeddings,
-``--ip_adapter_embeds FILE`` (``.pt`` / ``.npy``).
+``--ip_adapter_embeds FILE`` (``.pt`` / ``.npy``).  All four flags are repeatable (up to four adapters, base or Plus; DESIGN.md
+section 32) and matched by position; a Plus adapter given as embeddings also needs ``--ip_adapter_negative_embeds FILE``.
 ``--score_pca true`` saves the reference's diagnostic pictures (pca_diffusion_scores.py) every ``--log_freq``
 steps under the script's own names, ``pca_cls_dir_{i}.png`` / ``pca_uncond_{i}.png``.
 ``--region_prompt TEXT`` with ``--region_mask FILE|x0,y0,x1,y1[:WEIGHT]`` (both repeatable, paired in order) are regional prompts
@@ -50,6 +51,18 @@ import torch
 
 def _bool(v):
     return str(v).lower() in ("1", "true", "yes", "y", "t")
+
+
+class _Repeat(argparse.Action):
+    """A flag that may be given several times: once, the option is its string, as it always was; from the second on, a list."""
+
+    def __call__(self, parser, namespace, value, option_string=None):
+        held = getattr(namespace, self.dest, None)
+        setattr(namespace, self.dest, value if held is None else (held if isinstance(held, list) else [held]) + [value])
+
+
+def _listed(value):
+    return [] if value is None else (list(value) if isinstance(value, list) else [value])
 
 
 def build_parser():
@@ -128,13 +141,16 @@ def build_parser():
     ap.add_argument("--lora", action="append", default=[], metavar="PATH[:SCALE]", help="merge this LoRA adapter "
                     "(*.safetensors; diffusers, PEFT or kohya keys) into the UNet / CLIP weights at SCALE (default 1); repeatable, "
                     "applied in the order given")
-    ap.add_argument("--ip_adapter", type=str, default=None, metavar="PATH[:SCALE]", help="install this base IP-Adapter "
-                    "(*.safetensors, *.bin, *.pt) at SCALE (default 1); needs --ip_adapter_image or --ip_adapter_embeds")
-    ap.add_argument("--ip_adapter_image", type=str, default=None, help="the image prompt (a picture; needs --image_encoder)")
-    ap.add_argument("--ip_adapter_embeds", type=str, default=None, help="the image prompt as CLIP image embeddings "
-                    "[1, clip_dim]: a .pt (torch.save of a tensor) or .npy file")
-    ap.add_argument("--image_encoder", type=str, default=None, help="local directory of a transformers "
-                    "CLIPVisionModelWithProjection, for --ip_adapter_image")
+    ap.add_argument("--ip_adapter", action=_Repeat, default=None, metavar="PATH[:SCALE]", help="install this IP-Adapter, base or "
+                    "Plus (*.safetensors, *.bin, *.pt) at SCALE (default 1); needs --ip_adapter_image or --ip_adapter_embeds.  "
+                    "Repeatable, up to 4: the image flags are then given once per adapter and matched by position")
+    ap.add_argument("--ip_adapter_image", action=_Repeat, default=None, help="the image prompt (a picture; needs --image_encoder)")
+    ap.add_argument("--ip_adapter_embeds", action=_Repeat, default=None, help="the image prompt as CLIP image embeddings "
+                    "[1, clip_dim] (Plus: penultimate hidden states [1, S, embed_dim]): a .pt (torch.save of a tensor) or .npy file")
+    ap.add_argument("--ip_adapter_negative_embeds", action=_Repeat, default=None, help="the unconditional embeddings a Plus adapter "
+                    "given as --ip_adapter_embeds needs (.pt / .npy; 'none' at the position of a base adapter)")
+    ap.add_argument("--image_encoder", action=_Repeat, default=None, help="local directory of a transformers "
+                    "CLIPVisionModelWithProjection, for --ip_adapter_image (one for all adapters, or one per adapter)")
     ap.add_argument("--score_pca", type=_bool, default=False, help="true: every --log_freq steps, save the PCA maps of the class "
                     "direction and of the local unconditional score as pca_cls_dir_{i}.png / pca_uncond_{i}.png")
     ap.add_argument("--region_prompt", action="append", default=[], metavar="TEXT", help="prompt of one region (repeatable, up to 7); "
@@ -251,18 +267,31 @@ def main(argv=None):
             raise SystemExit(f"--lora: no such file {path!r}")
     ip = None
     if opt.ip_adapter is not None:
-        ip = _lora_arg(opt.ip_adapter)
-        if (opt.ip_adapter_image is None) == (opt.ip_adapter_embeds is None):
+        ip = [_lora_arg(v) for v in _listed(opt.ip_adapter)]
+        images, embeds, negs = _listed(opt.ip_adapter_image), _listed(opt.ip_adapter_embeds), _listed(opt.ip_adapter_negative_embeds)
+        encoders = _listed(opt.image_encoder)
+        if bool(images) == bool(embeds):
             raise SystemExit("--ip_adapter needs exactly one of --ip_adapter_image / --ip_adapter_embeds")
-        if opt.ip_adapter_image is not None and opt.image_encoder is None:
+        if len(ip) > 4:
+            raise SystemExit(f"--ip_adapter: up to 4 adapters, got {len(ip)}")
+        if len(images or embeds) != len(ip):
+            raise SystemExit(f"{len(ip)} --ip_adapter flags need as many --ip_adapter_image or --ip_adapter_embeds flags, matched by "
+                             f"position; got {len(images or embeds)}")
+        if images and not encoders:
             raise SystemExit("--ip_adapter_image needs --image_encoder (a local CLIPVisionModelWithProjection directory)")
-        for flag, path in (("--ip_adapter", ip[0]), ("--ip_adapter_image", opt.ip_adapter_image),
-                           ("--ip_adapter_embeds", opt.ip_adapter_embeds)):
-            if path is not None and not os.path.isfile(path):
-                raise SystemExit(f"{flag}: no such file {path!r}")
-        if opt.image_encoder is not None and not os.path.isdir(opt.image_encoder):
-            raise SystemExit(f"--image_encoder: no such directory {opt.image_encoder!r}")
-    elif opt.ip_adapter_image or opt.ip_adapter_embeds or opt.image_encoder:
+        if len(encoders) not in (0, 1, len(ip)):
+            raise SystemExit(f"--image_encoder: one for all adapters or one per adapter, got {len(encoders)} for {len(ip)}")
+        if negs and (images or len(negs) != len(ip)):
+            raise SystemExit("--ip_adapter_negative_embeds goes with --ip_adapter_embeds, once per adapter ('none' for a base adapter)")
+        for flag, paths in (("--ip_adapter", [p for p, _ in ip]), ("--ip_adapter_image", images), ("--ip_adapter_embeds", embeds),
+                            ("--ip_adapter_negative_embeds", [p for p in negs if p.lower() != "none"])):
+            for path in paths:
+                if not os.path.isfile(path):
+                    raise SystemExit(f"{flag}: no such file {path!r}")
+        for d in encoders:
+            if not os.path.isdir(d):
+                raise SystemExit(f"--image_encoder: no such directory {d!r}")
+    elif opt.ip_adapter_image or opt.ip_adapter_embeds or opt.image_encoder or opt.ip_adapter_negative_embeds:
         raise SystemExit("--ip_adapter_image / --ip_adapter_embeds / --image_encoder need --ip_adapter")
     pads = None
     if opt.outpaint is not None:
@@ -325,13 +354,21 @@ def main(argv=None):
         name = sd.load_lora(path, scale)
         print(f"LoRA {name!r} merged at scale {scale:g}: {sd.loras[-1][2]} tensors")
     if ip is not None:
-        name = sd.load_ip_adapter(ip[0], ip[1], image_encoder=opt.image_encoder)
-        print(f"IP-Adapter {name!r} installed at scale {ip[1]:g}: {sd.ip_adapter[2]} image tokens")
-        if opt.ip_adapter_image:
+        for a, (path, scale) in enumerate(ip):
+            enc = None if not encoders else encoders[a if len(encoders) > 1 else 0]
+            name = sd.load_ip_adapter(path, scale, image_encoder=enc, add=a > 0)
+            print(f"IP-Adapter {name!r} installed at scale {scale:g}: {sd.ip_adapters[-1][2]} image tokens ({sd.ip_adapters[-1][3]})")
+        one = len(ip) == 1    # one adapter: the bare value, as always
+        if images:
             from PIL import Image
-            extra["ip_adapter_image"] = Image.open(opt.ip_adapter_image).convert("RGB")
+            pics = [Image.open(f).convert("RGB") for f in images]
+            extra["ip_adapter_image"] = pics[0] if one else pics
         else:
-            extra["ip_adapter_image_embeds"] = _load_embeds(opt.ip_adapter_embeds)
+            loaded = [_load_embeds(f) for f in embeds]
+            extra["ip_adapter_image_embeds"] = loaded[0] if one else loaded
+            if negs:
+                neg = [None if f.lower() == "none" else _load_embeds(f) for f in negs]
+                extra["ip_adapter_negative_image_embeds"] = neg[0] if one else neg
     if opt.init_image:
         from PIL import Image
         extra["init_image"], extra["strength"] = Image.open(opt.init_image).convert("RGB"), opt.strength

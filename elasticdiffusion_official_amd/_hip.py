@@ -136,6 +136,8 @@ SIGNATURES = {
     "ed_groupnorm_f32_weighted": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp],
     "ed_softmax_rows_bias": [_vp, _i64, _i64, _f, _vp, _vp],
     "ed_control_residuals": [_vp, _i, _i, _vp, _i64, _vp],
+    "ed_flash_attention_ipn": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f,
+                               _vp, _vp],
 }
 
 _LIB = None

@@ -555,15 +555,50 @@ class Attention(nn.Module):
         self.to_k_ip = self.to_v_ip = None
         self.ip_tokens = 0
         self.ip_scale = 1.0
+        # Several adapters: ``ip_segments`` = every adapter's token count in context order (``ip_tokens`` is
+        # their sum); adapter a >= 1 lives in ``to_k_ip_{a}`` / ``to_v_ip_{a}``; ``ip_weights`` is the UNet's one fp32 device tensor
+        # [A] that replaces the by-value ``ip_scale`` from two adapters on.
+        self.ip_segments = ()
+        self.ip_weights = None
+
+    @staticmethod
+    def ip_names(a):
+        return ("to_k_ip", "to_v_ip") if a == 0 else (f"to_k_ip_{a}", f"to_v_ip_{a}")
 
     def set_ip_adapter(self, to_k_ip=None, to_v_ip=None, tokens=0):
-        """install (two bias-free Linear(cross_dim, inner) and the image-token count) or, without arguments, remove"""
+        """install (two bias-free Linear(cross_dim, inner) and the image-token count) as the ONLY adapter or, without arguments,
+        remove every adapter"""
+        for a in range(1, len(self.ip_segments)):
+            for name in self.ip_names(a):
+                delattr(self, name)
         for name, mod in (("to_k_ip", to_k_ip), ("to_v_ip", to_v_ip)):
             if isinstance(getattr(self, name), nn.Module):
                 delattr(self, name)     # out of _modules, so the key leaves state_dict()
             setattr(self, name, mod)
         self.ip_tokens = int(tokens) if to_k_ip is not None else 0
+        self.ip_segments = (self.ip_tokens,) if self.ip_tokens else ()
+        self.ip_weights = None
         self.__dict__.pop("_derived", None)
+
+    def add_ip_adapter(self, to_k_ip, to_v_ip, tokens, weights):
+        """append one more adapter behind the installed one(s); ``weights``: the fp32 tensor [A] all layers of the model share"""
+        a = len(self.ip_segments)
+        if a == 0:
+            raise ValueError("add_ip_adapter appends to an installed adapter: use set_ip_adapter for the first")
+        for name, mod in zip(self.ip_names(a), (to_k_ip, to_v_ip)):
+            setattr(self, name, mod)
+        self.ip_segments = self.ip_segments + (int(tokens),)
+        self.ip_tokens = sum(self.ip_segments)
+        self.ip_weights = weights
+        self.__dict__.pop("_derived", None)
+
+    def _ip_rows(self, n):
+        """[(first row, one past the last)] of every adapter's rows in a context / k|v of ``n`` rows"""
+        out, off = [], n - self.ip_tokens
+        for ni in self.ip_segments:
+            out.append((off, off + ni))
+            off += ni
+        return out
 
     def _fused_weight(self, names, q_scale=None):
         """cat of the projection weights (bias-free in every SD / SDXL attention).
@@ -591,7 +626,11 @@ class Attention(nn.Module):
             # (rows in the order ed_flash_attention_ip reads them).  Same calls for the first projection and every refresh.
             nt = context.shape[-2] - self.ip_tokens
             out[..., :nt, :] = torch.matmul(context[..., :nt, :], w.t())
-            out[..., nt:, :] = torch.matmul(context[..., nt:, :], self._fused_weight(("to_k_ip", "to_v_ip")).t())
+            if len(self.ip_segments) < 2:
+                out[..., nt:, :] = torch.matmul(context[..., nt:, :], self._fused_weight(("to_k_ip", "to_v_ip")).t())
+                return out
+            for a, (lo, hi) in enumerate(self._ip_rows(context.shape[-2])):   # each adapter's rows through its own fused weight
+                out[..., lo:hi, :] = torch.matmul(context[..., lo:hi, :], self._fused_weight(self.ip_names(a)).t())
             return out
         torch.matmul(context, w.t(), out=out)
         return out
@@ -627,7 +666,17 @@ class Attention(nn.Module):
                     kv = self.project_kv(context)
                 k, v = kv[..., :inner], kv[..., inner:]
                 nt = kv.shape[1] - self.ip_tokens
-                if ops.flash_attention_ip_ok(inner // self.heads, nt, self.ip_tokens):
+                if len(self.ip_segments) >= 2:
+                    # several adapters: one ed_flash_attention_ipn launch where it takes the shape, else A + 1 attentions combined
+                    # with the DEVICE weights by a tensor multiply -- never a Python float, so a replayed graph follows a new scale
+                    if ops.flash_attention_ipn_ok(inner // self.heads, nt, self.ip_segments):
+                        o = ops.flash_attention_ipn(q, k, v, self.heads, nt, self.ip_segments, self.ip_weights)
+                    else:
+                        o = ops.flash_attention(q, k[:, :nt], v[:, :nt], self.heads)
+                        wd = self.ip_weights.to(o.dtype)
+                        for a, (lo, hi) in enumerate(self._ip_rows(kv.shape[1])):
+                            o = o.addcmul_(ops.flash_attention(q, k[:, lo:hi], v[:, lo:hi], self.heads), wd[a])
+                elif ops.flash_attention_ip_ok(inner // self.heads, nt, self.ip_tokens):
                     o = ops.flash_attention_ip(q, k, v, self.heads, nt, self.ip_scale)
                 else:
                     o = ops.flash_attention(q, k[:, :nt], v[:, :nt], self.heads)
@@ -651,7 +700,12 @@ class Attention(nn.Module):
             nt = kv.shape[1] - self.ip_tokens
             k, v = (t.reshape(B, kv.shape[1], self.heads, -1).transpose(1, 2) for t in (kv[..., :inner], kv[..., inner:]))
             o = F.scaled_dot_product_attention(q, k[:, :, :nt], v[:, :, :nt])
-            o = o + self.ip_scale * F.scaled_dot_product_attention(q, k[:, :, nt:], v[:, :, nt:])
+            if len(self.ip_segments) >= 2:
+                wd = self.ip_weights.to(o.dtype)
+                for a, (lo, hi) in enumerate(self._ip_rows(kv.shape[1])):
+                    o = o + wd[a] * F.scaled_dot_product_attention(q, k[:, :, lo:hi], v[:, :, lo:hi])
+            else:
+                o = o + self.ip_scale * F.scaled_dot_product_attention(q, k[:, :, nt:], v[:, :, nt:])
             return self.to_out[0](o.transpose(1, 2).reshape(B, N, -1)), False
         if kv is not None:
             k, v = (t.reshape(B, ctx.shape[1], self.heads, -1).transpose(1, 2) for t in (kv[..., :inner], kv[..., inner:]))
@@ -948,6 +1002,100 @@ class ImageProjection(nn.Module):
         return self.norm(self.proj(embeds).reshape(-1, self.tokens, self.cross_dim))
 
 
+class PerceiverAttention(nn.Module):
+    """One attention of the Resampler: the latents attend over [x | latents]; heads of 64, all projections bias-free."""
+    DIM_HEAD = 64
+
+    def __init__(self, dim, heads):
+        super().__init__()
+        inner = heads * self.DIM_HEAD
+        self.heads = heads
+        self.norm1, self.norm2 = nn.LayerNorm(dim), nn.LayerNorm(dim)
+        self.to_q = nn.Linear(dim, inner, bias=False)
+        self.to_kv = nn.Linear(dim, 2 * inner, bias=False)
+        self.to_out = nn.Linear(inner, dim, bias=False)
+
+    def forward(self, x, latents):
+        x, latents = self.norm1(x), self.norm2(latents)
+        B, N, _ = latents.shape
+        q = self.to_q(latents)
+        k, v = self.to_kv(torch.cat([x, latents], dim=-2)).chunk(2, dim=-1)
+        q, k, v = (t.reshape(B, t.shape[1], self.heads, self.DIM_HEAD).transpose(1, 2) for t in (q, k, v))
+        c = self.DIM_HEAD ** -0.25            # dh^-1/4 on q and on k, as published (the product is the usual dh^-1/2)
+        w = torch.softmax((q * c) @ (k * c).transpose(-1, -2), dim=-1)
+        return self.to_out((w @ v).transpose(1, 2).reshape(B, N, -1))
+
+
+class Resampler(nn.Module):
+    """The IP-Adapter Plus image projection (the published ``resampler.py``): the CLIP vision model's penultimate hidden states
+    [B, S, embed_dim] -> Ni learned latents that attend over them through ``depth`` Perceiver layers -> [B, Ni, cross_dim] image
+    tokens.  Attribute names are the file's keys (``image_proj.<name>``).  Runs once per image in torch: not on the hot path."""
+
+    def __init__(self, dim, depth, heads, tokens, embed_dim, cross_dim, ff_inner):
+        super().__init__()
+        self.tokens, self.cross_dim = tokens, cross_dim
+        self.latents = nn.Parameter(torch.zeros(1, tokens, dim))
+        self.proj_in = nn.Linear(embed_dim, dim)
+        self.proj_out = nn.Linear(dim, cross_dim)
+        self.norm_out = nn.LayerNorm(cross_dim)
+        self.layers = nn.ModuleList(
+            nn.ModuleList([PerceiverAttention(dim, heads),
+                           nn.Sequential(nn.LayerNorm(dim), nn.Linear(dim, ff_inner, bias=False), nn.GELU(),
+                                         nn.Linear(ff_inner, dim, bias=False))])
+            for _ in range(depth))
+
+    def forward(self, x):
+        latents = self.latents.repeat(x.shape[0], 1, 1)
+        x = self.proj_in(x)
+        for attn, ff in self.layers:
+            latents = attn(x, latents) + latents
+            latents = ff(latents) + latents
+        return self.norm_out(self.proj_out(latents))
+
+    @staticmethod
+    def expected_keys(flat, cross):
+        """{``image_proj.*`` key: shape} a Plus file must hold, every size read from the shapes of ``flat``; ValueError where the
+        anchor tensors are missing or do not fit (naming Plus and Resampler) -> (expected, constructor arguments)"""
+        def need(key, dims):
+            t = flat.get(key)
+            if t is None or t.dim() != dims:
+                raise ValueError(f"IP-Adapter Plus: the Resampler's {key} is missing or not {dims}-dimensional; nothing installed")
+            return t
+        lat = need("image_proj.latents", 3)
+        ni, dim = int(lat.shape[1]), int(lat.shape[2])
+        if lat.shape[0] != 1 or not 1 <= ni <= ops.IP_MAX_IMAGE_KEYS:
+            raise ValueError(f"IP-Adapter Plus: the Resampler's image_proj.latents is {tuple(lat.shape)}: not [1, 1..{ops.IP_MAX_IMAGE_KEYS}, "
+                             "dim]; nothing installed")
+        embed_dim = int(need("image_proj.proj_in.weight", 2).shape[1])
+        out_w = need("image_proj.proj_out.weight", 2)
+        if out_w.shape[0] != cross:
+            raise ValueError(f"IP-Adapter Plus: the Resampler's proj_out has {out_w.shape[0]} output features, this UNet's cross-attention "
+                             f"width is {cross}; nothing installed")
+        layer_ids = sorted({int(k.split(".")[2]) for k in flat if k.startswith("image_proj.layers.") and k.split(".")[2].isdigit()})
+        depth = len(layer_ids)
+        if depth == 0 or layer_ids != list(range(depth)):
+            raise ValueError(f"IP-Adapter Plus: the Resampler's layers are numbered {layer_ids[:8]}: not 0 .. depth - 1; nothing installed")
+        inner = int(need("image_proj.layers.0.0.to_q.weight", 2).shape[0])
+        ffi = int(need("image_proj.layers.0.1.1.weight", 2).shape[0])
+        if inner % PerceiverAttention.DIM_HEAD or inner == 0:
+            raise ValueError(f"IP-Adapter Plus: the Resampler's to_q has {inner} output features: not heads of {PerceiverAttention.DIM_HEAD}")
+        exp = {"image_proj.latents": (1, ni, dim), "image_proj.proj_in.weight": (dim, embed_dim), "image_proj.proj_in.bias": (dim,),
+               "image_proj.proj_out.weight": (cross, dim), "image_proj.proj_out.bias": (cross,),
+               "image_proj.norm_out.weight": (cross,), "image_proj.norm_out.bias": (cross,)}
+        for i in range(depth):
+            p = f"image_proj.layers.{i}"
+            for n in ("norm1", "norm2"):
+                exp[f"{p}.0.{n}.weight"] = exp[f"{p}.0.{n}.bias"] = (dim,)
+            exp[f"{p}.0.to_q.weight"], exp[f"{p}.0.to_kv.weight"], exp[f"{p}.0.to_out.weight"] = (inner, dim), (2 * inner, dim), (dim, inner)
+            exp[f"{p}.1.0.weight"] = exp[f"{p}.1.0.bias"] = (dim,)
+            exp[f"{p}.1.1.weight"], exp[f"{p}.1.3.weight"] = (ffi, dim), (dim, ffi)
+        return exp, dict(dim=dim, depth=depth, heads=inner // PerceiverAttention.DIM_HEAD, tokens=ni, embed_dim=embed_dim,
+                         cross_dim=cross, ff_inner=ffi)
+
+
+IP_MAX_ADAPTERS = 4
+
+
 def flatten_ip_adapter_state(state):
     """An IP-Adapter state dict with flat keys, from either form a file holds: already flat (``image_proj.proj.weight``,
     ``ip_adapter.1.to_k_ip.weight``: safetensors) or nested ``{"image_proj": {...}, "ip_adapter": {...}}`` (the pickled files)."""
@@ -1000,7 +1148,9 @@ class UNet2DConditionModel(nn.Module):
         self.conv_norm_out = nn.GroupNorm(32, boc[0], eps=1e-5)
         self.conv_out = nn.Conv2d(boc[0], out_channels, 3, padding=1)
         self.ip_tokens = 0          # IP-Adapter image tokens at the end of the context; 0: no adapter installed
-        self.ip_image_proj = None   # the installed adapter's ImageProjection
+        self.ip_image_proj = None   # the (first) installed adapter's ImageProjection / Resampler
+        self.ip_weights = None      # two or more adapters: fp32 [IP_MAX_ADAPTERS] on the device, one weight per adapter (section 32)
+        self._ip_entries = []
 
     @property
     def dtype(self):
@@ -1041,26 +1191,40 @@ class UNet2DConditionModel(nn.Module):
         return out
 
     @torch.no_grad()
-    def install_ip_adapter(self, state):
-        """Install a base IP-Adapter from its state dict (flat ``image_proj.*`` / ``ip_adapter.*`` keys or the nested
-        ``{"image_proj": {...}, "ip_adapter": {...}}`` form).  Every expected key must be present with a fitting shape and no other
-        key may be: otherwise ValueError, and nothing is installed.  Returns the image-token count."""
+    def install_ip_adapter(self, state, add=False):
+        """Install an IP-Adapter from its state dict (flat ``image_proj.*`` / ``ip_adapter.*`` keys or the nested
+        ``{"image_proj": {...}, "ip_adapter": {...}}`` form): a base adapter (``image_proj.proj`` / ``image_proj.norm``:
+        ``ImageProjection``) or a Plus adapter (``image_proj.latents`` / ``layers`` / ``proj_in`` / ``proj_out`` / ``norm_out``:
+        ``Resampler``).  Every expected key must be present with a fitting shape and no other key may be: otherwise ValueError, and
+        nothing is installed.  ``add``: append behind the installed adapters (up to ``IP_MAX_ADAPTERS``) instead of replacing them.
+        Returns the image-token count of this adapter."""
         flat = flatten_ip_adapter_state(state)
-        if any(k.startswith("image_proj.latents") or k.startswith("image_proj.layers.") or k.startswith("image_proj.proj_in")
-               for k in flat):
-            raise ValueError("this is an IP-Adapter 'Plus' / FaceID file (Resampler keys such as image_proj.latents): only the base "
-                             "adapters' ImageProjection (image_proj.proj / image_proj.norm) is supported")
+        if any(k.startswith("image_proj.proj.0.") or k.startswith("image_proj.proj.2.") or "lora" in k for k in flat):
+            raise ValueError("this is an IP-Adapter FaceID file (image_proj.proj.0.* / LoRA keys): FaceID / ID-embedding adapters are not "
+                             "supported; nothing installed")
+        resampler_keys = [k for k in flat if k.startswith(("image_proj.latents", "image_proj.layers.", "image_proj.proj_in",
+                                                            "image_proj.proj_out", "image_proj.norm_out"))]
+        base_keys = [k for k in flat if k.startswith(("image_proj.proj.", "image_proj.norm."))]
+        if resampler_keys and base_keys:
+            raise ValueError(f"this file mixes an IP-Adapter 'Plus' Resampler's keys ({resampler_keys[0]}) with a base adapter's "
+                             f"ImageProjection keys ({base_keys[0]}): it is neither; nothing installed")
+        if add and len(self.__dict__.get("_ip_entries", ())) >= IP_MAX_ADAPTERS:
+            raise ValueError(f"{IP_MAX_ADAPTERS} IP-Adapters are installed already: a fifth does not fit; nothing installed")
         attns = self.ip_attentions()
         cross = self.config.cross_attention_dim
-        proj_w = flat.get("image_proj.proj.weight")
-        if proj_w is None or proj_w.dim() != 2:
-            raise ValueError("IP-Adapter: image_proj.proj.weight is missing or not a matrix")
-        if proj_w.shape[0] % cross or not 1 <= proj_w.shape[0] // cross <= ops.IP_MAX_IMAGE_KEYS:
-            raise ValueError(f"IP-Adapter: image_proj.proj has {proj_w.shape[0]} output features: not 1..{ops.IP_MAX_IMAGE_KEYS} "
-                             f"image tokens of cross-attention width {cross}")
-        ni, clip_dim = proj_w.shape[0] // cross, proj_w.shape[1]
-        expected = {"image_proj.proj.weight": (ni * cross, clip_dim), "image_proj.proj.bias": (ni * cross,),
-                    "image_proj.norm.weight": (cross,), "image_proj.norm.bias": (cross,)}
+        if resampler_keys:
+            expected, rs_args = Resampler.expected_keys(flat, cross)
+            ni = rs_args["tokens"]
+        else:
+            proj_w = flat.get("image_proj.proj.weight")
+            if proj_w is None or proj_w.dim() != 2:
+                raise ValueError("IP-Adapter: image_proj.proj.weight is missing or not a matrix")
+            if proj_w.shape[0] % cross or not 1 <= proj_w.shape[0] // cross <= ops.IP_MAX_IMAGE_KEYS:
+                raise ValueError(f"IP-Adapter: image_proj.proj has {proj_w.shape[0]} output features: not 1..{ops.IP_MAX_IMAGE_KEYS} "
+                                 f"image tokens of cross-attention width {cross}")
+            ni, clip_dim = proj_w.shape[0] // cross, proj_w.shape[1]
+            expected = {"image_proj.proj.weight": (ni * cross, clip_dim), "image_proj.proj.bias": (ni * cross,),
+                        "image_proj.norm.weight": (cross,), "image_proj.norm.bias": (cross,)}
         for n, a in enumerate(attns):
             for name in ("to_k_ip", "to_v_ip"):
                 expected[f"ip_adapter.{2 * n + 1}.{name}.weight"] = (a.to_k.out_features, cross)
@@ -1079,27 +1243,75 @@ class UNet2DConditionModel(nn.Module):
             if b is not None:
                 m.bias.copy_(b)
             return m.requires_grad_(False)
-        self.remove_ip_adapter()
-        proj = ImageProjection(clip_dim, cross, ni).to(device=like.device, dtype=like.dtype).requires_grad_(False)
-        proj.proj.weight.copy_(flat["image_proj.proj.weight"]), proj.proj.bias.copy_(flat["image_proj.proj.bias"])
-        proj.norm.weight.copy_(flat["image_proj.norm.weight"]), proj.norm.bias.copy_(flat["image_proj.norm.bias"])
-        self.ip_image_proj = proj
-        for n, a in enumerate(attns):
-            a.set_ip_adapter(linear(flat[f"ip_adapter.{2 * n + 1}.to_k_ip.weight"]),
-                             linear(flat[f"ip_adapter.{2 * n + 1}.to_v_ip.weight"]), ni)
-        self.ip_tokens = ni
+        if resampler_keys:    # (first to the model's dtype, then the copy: the file's values are rounded once)
+            proj = Resampler(**rs_args).to(device=like.device, dtype=like.dtype).requires_grad_(False)
+            proj.load_state_dict({k[len("image_proj."):]: flat[k] for k in expected if k.startswith("image_proj.")})
+        else:
+            proj = ImageProjection(clip_dim, cross, ni).to(device=like.device, dtype=like.dtype).requires_grad_(False)
+            proj.proj.weight.copy_(flat["image_proj.proj.weight"]), proj.proj.bias.copy_(flat["image_proj.proj.bias"])
+            proj.norm.weight.copy_(flat["image_proj.norm.weight"]), proj.norm.bias.copy_(flat["image_proj.norm.bias"])
+        # (a replacement keeps the scale in force, as it always did; an appended adapter starts at 1)
+        entry = {"proj": proj, "kind": "plus" if resampler_keys else "base", "tokens": ni, "scale": 1.0 if add else float(self.ip_scale),
+                 "kv": [(linear(flat[f"ip_adapter.{2 * n + 1}.to_k_ip.weight"]), linear(flat[f"ip_adapter.{2 * n + 1}.to_v_ip.weight"]))
+                        for n in range(len(attns))]}
+        held = list(self.__dict__.get("_ip_entries", ())) if add else []
+        self._install_ip_entries(held + [entry])
         return ni
 
-    def remove_ip_adapter(self):
-        for a in self.ip_attentions():
-            a.set_ip_adapter()
-        if isinstance(self.ip_image_proj, nn.Module):
-            del self.ip_image_proj
+    @staticmethod
+    def _ip_proj_name(a):
+        return "ip_image_proj" if a == 0 else f"ip_image_proj_{a}"
+
+    def _install_ip_entries(self, entries):
+        """Make ``entries`` (image projection, kind, token count, scale, per-layer (to_k_ip, to_v_ip)) the installed adapters, in
+        order.  One adapter: the attribute names, state_dict() keys and by-value scale the project always had.  Two or more: the
+        further adapters under ``ip_image_proj_{a}`` / ``to_k_ip_{a}`` / ``to_v_ip_{a}`` and ONE fp32 device tensor of weights, at
+        an address that stays for the life of this UNet, shared by all its attention layers."""
+        attns = self.ip_attentions()
+        for a in range(len(self.__dict__.get("_ip_entries", ()))):
+            if isinstance(getattr(self, self._ip_proj_name(a), None), nn.Module):
+                delattr(self, self._ip_proj_name(a))
+        for at in attns:
+            at.set_ip_adapter()
         self.ip_image_proj = None
-        self.ip_tokens = 0
+        self._ip_entries = list(entries)
+        self.ip_tokens = sum(e["tokens"] for e in entries)
+        if not entries:
+            return
+        if len(entries) >= 2 and self.__dict__.get("ip_weights") is None:
+            self.ip_weights = torch.zeros(IP_MAX_ADAPTERS, dtype=torch.float32, device=self.conv_in.weight.device)
+        for a, e in enumerate(entries):
+            setattr(self, self._ip_proj_name(a), e["proj"])
+            for at, (to_k, to_v) in zip(attns, e["kv"]):
+                if a == 0:
+                    at.set_ip_adapter(to_k, to_v, e["tokens"])
+                else:
+                    at.add_ip_adapter(to_k, to_v, e["tokens"], self.ip_weights[:len(entries)])
+        self.ip_scales = [e["scale"] for e in entries]
+
+    def remove_ip_adapter(self, index=None):
+        """remove every adapter, or the ``index``-th one (the others keep their order and scales)"""
+        entries = list(self.__dict__.get("_ip_entries", ()))
+        if index is not None:
+            del entries[index]
+        else:
+            entries = []
+        self._install_ip_entries(entries)
+
+    @property
+    def ip_adapters(self):
+        """[(kind "base" | "plus", image tokens, scale)] of the installed adapters, in context order"""
+        return [(e["kind"], e["tokens"], e["scale"]) for e in self.__dict__.get("_ip_entries", ())]
+
+    @property
+    def ip_segments(self):
+        return tuple(e["tokens"] for e in self.__dict__.get("_ip_entries", ()))
 
     @property
     def ip_scale(self):
+        entries = self.__dict__.get("_ip_entries", ())
+        if len(entries) >= 2:
+            return entries[0]["scale"]
         a = self.ip_attentions()
         return a[0].ip_scale if a else 1.0
 
@@ -1108,16 +1320,53 @@ class UNet2DConditionModel(nn.Module):
         scale = float(scale)
         if not math.isfinite(scale):
             raise ValueError(f"IP-Adapter scale must be finite, got {scale}")
+        entries = self.__dict__.get("_ip_entries", ())
+        if len(entries) >= 2:
+            self.ip_scales = [scale] * len(entries)
+            return
+        for e in entries:
+            e["scale"] = scale
         for a in self.ip_attentions():
             a.ip_scale = scale
 
+    @property
+    def ip_scales(self):
+        return [e["scale"] for e in self.__dict__.get("_ip_entries", ())]
+
+    @ip_scales.setter
+    def ip_scales(self, scales):
+        """one scale per installed adapter.  One adapter: the by-value kernel argument.  Several: a copy into the device weights the
+        kernels read when they run -- no captured graph has to be dropped."""
+        entries = self.__dict__.get("_ip_entries", ())
+        scales = [float(s) for s in scales]
+        if len(scales) != len(entries):
+            raise ValueError(f"{len(entries)} IP-Adapter(s) installed, {len(scales)} scale(s) given")
+        if not all(math.isfinite(s) for s in scales):
+            raise ValueError(f"IP-Adapter scales must be finite, got {scales}")
+        if len(entries) == 1:
+            self.ip_scale = scales[0]
+            return
+        for e, s in zip(entries, scales):
+            e["scale"] = s
+        if entries:
+            with torch.no_grad():
+                self.ip_weights[:len(entries)].copy_(torch.tensor(scales, dtype=torch.float32))
+
     @torch.no_grad()
-    def ip_image_tokens(self, clip_embeds):
-        """[B, clip_dim] CLIP image embeddings -> [B, Ni, cross_dim] image tokens (a zero embedding gives the unconditional ones)"""
-        if self.ip_image_proj is None:
+    def ip_image_tokens(self, embeds, index=0):
+        """adapter ``index``: [B, clip_dim] CLIP image embeddings (base) or [B, S, embed_dim] penultimate hidden states (Plus) ->
+        [B, Ni, cross_dim] image tokens (for a base adapter a zero embedding gives the unconditional ones)"""
+        entries = self.__dict__.get("_ip_entries", ())
+        if not entries:
             raise ValueError("no IP-Adapter is installed")
-        p = self.ip_image_proj.proj.weight
-        return self.ip_image_proj(clip_embeds.to(device=p.device, dtype=p.dtype))
+        proj = entries[index]["proj"]
+        p = proj.norm.weight if entries[index]["kind"] == "base" else proj.norm_out.weight
+        return proj(embeds.to(device=p.device, dtype=p.dtype))
+
+    def ip_embed_shape(self, index=0):
+        """(rank, last dimension) of the embeddings adapter ``index`` takes: (2, clip_dim) base, (3, embed_dim) Plus"""
+        e = self.__dict__["_ip_entries"][index]
+        return (2, e["proj"].proj.in_features) if e["kind"] == "base" else (3, e["proj"].proj_in.in_features)
 
     def forward(self, sample, timestep, encoder_hidden_states=None, added_cond_kwargs=None,
                 down_block_additional_residuals=None, mid_block_additional_residual=None, cross_kv=None, control_residuals=None, **_):

@@ -2,6 +2,7 @@
 buffers and the stream; every wrapper validates its arguments, passes raw device pointers and raises on a HIP
 error.  No wrapper has a fallback path -- a tensor that is not on a ROCm device is an error.  (One stated exception:
 ``control_residuals`` runs the torch op sequence it replaces for a level whose tensors do not share dense strides, and for host tensors.)"""
+import ctypes
 import math
 
 import torch
@@ -1578,6 +1579,55 @@ def flash_attention_ip(q, k, v, heads, n_text, ip_scale):
     _call("ed_flash_attention_ip", q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _code(q, "q"), B, heads, Nq, n_text,
           N - n_text, hd, q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1), out.stride(0), out.stride(1),
           hd ** -0.5, ip_scale, _stream())
+    return out
+
+
+IPN_MAX_ADAPTERS = 4                  # ed_flash_attention_ipn: up to four segments inside the one image block
+
+
+def flash_attention_ipn_ok(head_dim, n_text, n_image):
+    """does ed_flash_attention_ipn take this shape?  ``n_image``: one key count per adapter.  (models.Attention runs A + 1
+    attentions and A weighted adds otherwise)"""
+    n_image = tuple(int(n) for n in n_image)
+    return (head_dim == 64 and 1 <= n_text <= IP_MAX_TEXT_KEYS and 1 <= len(n_image) <= IPN_MAX_ADAPTERS
+            and all(n >= 1 for n in n_image) and sum(n_image) <= IP_MAX_IMAGE_KEYS)
+
+
+def flash_attention_ipn(q, k, v, heads, n_text, n_image, w):
+    """Decoupled cross attention with several IP-Adapters in one launch: q [B,Nq,H*64], k / v
+    [B,Nt+sum(n_image),H*64] 16-bit with the ``n_text`` text rows first, then each adapter's ``n_image[a]`` rows in order; ``w`` a
+    float32 DEVICE tensor [A] the kernel reads when it runs (so a captured graph replays a change of weights) ->
+    softmax(q k_t^T / 8) v_t + sum_a w[a] softmax(q k_a^T / 8) v_a, contiguous [B,Nq,H*64].  1 <= Nt <= 160, 1 <= A <= 4,
+    sum(n_image) <= 32, head dim 64.  See ed_flash_attention_ipn."""
+    B, Nq, HD = q.shape
+    N = k.shape[1]
+    hd = HD // heads
+    n_text, n_image = int(n_text), tuple(int(n) for n in n_image)
+    if HD != heads * hd or hd != 64 or k.shape != (B, N, HD) or v.shape != (B, N, HD):
+        _reject(f"flash_attention_ipn: head_dim must be 64 and shapes consistent (q {tuple(q.shape)}, k {tuple(k.shape)}, "
+                f"v {tuple(v.shape)}, heads {heads})")
+    if not flash_attention_ipn_ok(hd, n_text, n_image) or n_text + sum(n_image) != N:
+        _reject(f"flash_attention_ipn: needs 1 <= text keys <= {IP_MAX_TEXT_KEYS}, 1 to {IPN_MAX_ADAPTERS} adapters of >= 1 image keys "
+                f"each, <= {IP_MAX_IMAGE_KEYS} image keys together and text + image keys = {N} rows, got {n_text} and {n_image}")
+    if (not isinstance(w, torch.Tensor) or not w.is_cuda or w.dtype != torch.float32 or w.shape != (len(n_image),)
+            or not w.is_contiguous()):
+        _reject(f"flash_attention_ipn: w must be a contiguous float32 tensor [{len(n_image)}] on the MI355X (one weight per adapter)")
+    for t, name in ((q, "q"), (k, "k"), (v, "v")):
+        if not t.is_cuda or t.dtype != q.dtype or t.dtype not in (torch.float16, torch.bfloat16) or t.stride(2) != 1:
+            _reject(f"flash_attention_ipn: {name} must be a 16-bit tensor on the MI355X with unit last stride; no CPU fallback")
+        if _LAUNCH["device"] is None:
+            _LAUNCH["device"] = t.device
+        elif _LAUNCH["device"] != t.device:
+            _reject(f"flash_attention_ipn: {name} lives on {t.device}, q on {_LAUNCH['device']}")
+    if w.device != q.device:
+        _reject(f"flash_attention_ipn: w lives on {w.device}, q on {q.device}")
+    out = torch.empty(B, Nq, HD, dtype=q.dtype, device=q.device)
+    TIMER.note_work("ed_flash_attention_ipn", flops=4.0 * B * heads * Nq * N * hd,
+                    nbytes=2.0 * q.element_size() * HD * B * (Nq + N))
+    ni = (ctypes.c_int32 * len(n_image))(*n_image)   # read by the entry point before it returns
+    _call("ed_flash_attention_ipn", q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _code(q, "q"), B, heads, Nq, n_text,
+          len(n_image), ctypes.addressof(ni), hd, q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
+          out.stride(0), out.stride(1), hd ** -0.5, w.data_ptr(), _stream())
     return out
 
 

@@ -230,13 +230,26 @@ def check_score_pca_arguments(score_pca, channels):
     return bool(score_pca)
 
 
-def check_ip_adapter_arguments(loaded, has_image_encoder, ip_adapter_image=None, ip_adapter_image_embeds=None):
+def check_ip_adapter_arguments(loaded, has_image_encoder, ip_adapter_image=None, ip_adapter_image_embeds=None,
+                               ip_adapter_negative_image_embeds=None):
     """The argument rules of ``ip_adapter_image`` / ``ip_adapter_image_embeds``, pure host code that runs
     before anything is launched -> does this run carry an image prompt?  ValueError: an adapter is loaded and no image is given
-    (or both forms are), an image is given without an adapter, ``ip_adapter_image`` without an image encoder."""
+    (or both forms are), an image is given without an adapter, ``ip_adapter_image`` without an image encoder.
+    ``loaded`` / ``has_image_encoder`` may be lists, one entry per loaded adapter -- its kind ("base" | "plus") and whether it has an
+    encoder: the rules of several adapters and of Plus adapters (section 32; ``check_ip_adapters_arguments``)."""
+    if not isinstance(loaded, (list, tuple)):
+        loaded, has_image_encoder = (["base"], [bool(has_image_encoder)]) if loaded else ([], [])
+    if len(loaded) > 1 or "plus" in loaded or (loaded and ip_adapter_negative_image_embeds is not None):
+        return check_ip_adapters_arguments(list(loaded), list(has_image_encoder), ip_adapter_image, ip_adapter_image_embeds,
+                                           ip_adapter_negative_image_embeds)
+    loaded, has_image_encoder = bool(loaded), bool(loaded and has_image_encoder[0])   # one base adapter: the rules as they were
+    if isinstance(ip_adapter_image, (list, tuple)) and len(ip_adapter_image) == 1:
+        ip_adapter_image = ip_adapter_image[0]
+    if isinstance(ip_adapter_image_embeds, (list, tuple)) and len(ip_adapter_image_embeds) == 1:
+        ip_adapter_image_embeds = ip_adapter_image_embeds[0]
     given = (ip_adapter_image is not None) + (ip_adapter_image_embeds is not None)
     if not loaded:
-        if given:
+        if given or ip_adapter_negative_image_embeds is not None:
             raise ValueError("ip_adapter_image / ip_adapter_image_embeds given but no IP-Adapter is loaded (load_ip_adapter)")
         return False
     if given != 1:
@@ -252,6 +265,62 @@ def check_ip_adapter_arguments(loaded, has_image_encoder, ip_adapter_image=None,
     elif not isinstance(ip_adapter_image_embeds, torch.Tensor) or ip_adapter_image_embeds.dim() != 2:
         raise ValueError("ip_adapter_image_embeds must be a [1 or B, clip_dim] tensor, got "
                          f"{tuple(getattr(ip_adapter_image_embeds, 'shape', ())) or type(ip_adapter_image_embeds).__name__}")
+    return True
+
+
+def ip_adapter_entries(value, count, what):
+    """``value`` of a run keyword as a list with one entry per loaded adapter: a list / tuple of ``count`` entries, or a bare value
+    where one adapter is loaded"""
+    if isinstance(value, (list, tuple)):
+        if len(value) != count:
+            raise ValueError(f"{what} has {len(value)} entries but {count} IP-Adapter(s) are loaded: one entry per adapter, in load order")
+        return list(value)
+    if count != 1:
+        raise ValueError(f"{count} IP-Adapters are loaded: {what} must be a list with one entry per adapter, in load order")
+    return [value]
+
+
+def check_ip_adapters_arguments(kinds, has_encoder, ip_adapter_image=None, ip_adapter_image_embeds=None,
+                                ip_adapter_negative_image_embeds=None):
+    """``check_ip_adapter_arguments`` for several adapters and for Plus adapters: ``kinds`` = "base" | "plus"
+    per loaded adapter, ``has_encoder`` alike.  Exactly one of the two forms, as a list with one entry per adapter (a bare value with
+    one adapter); a picture needs that adapter's encoder; embeddings are [1 or B, clip_dim] for a base adapter and [1 or B, S,
+    embed_dim] (the CLIP vision model's penultimate hidden states) for a Plus adapter; a Plus adapter given as embeddings needs its
+    unconditional embeddings too (``ip_adapter_negative_image_embeds``, same list form; an entry may be None for a base adapter,
+    whose unconditional tokens are the projection of zeros)."""
+    A = len(kinds)
+    given = (ip_adapter_image is not None) + (ip_adapter_image_embeds is not None)
+    if given != 1:
+        raise ValueError(f"{A} IP-Adapter(s) are loaded: every image needs exactly one of ip_adapter_image / ip_adapter_image_embeds "
+                         f"({'both' if given else 'neither'} given); unload_ip_adapter() goes back to text-only generation")
+    if ip_adapter_image is not None:
+        if ip_adapter_negative_image_embeds is not None:
+            raise ValueError("ip_adapter_negative_image_embeds goes with ip_adapter_image_embeds: with ip_adapter_image the unconditional "
+                             "tokens come from the image encoder")
+        for a, img in enumerate(ip_adapter_entries(ip_adapter_image, A, "ip_adapter_image")):
+            if not has_encoder[a]:
+                raise ValueError(f"ip_adapter_image needs the image_encoder given to load_ip_adapter (adapter {a} has none); without "
+                                 "one pass ip_adapter_image_embeds")
+            if not _is_8bit_picture(img, 3):
+                raise ValueError(f"ip_adapter_image[{a}] must be an RGB PIL image or a uint8 [H,W,3] array / tensor, got {type(img).__name__}")
+        return True
+    embeds = ip_adapter_entries(ip_adapter_image_embeds, A, "ip_adapter_image_embeds")
+    neg = ([None] * A if ip_adapter_negative_image_embeds is None
+           else ip_adapter_entries(ip_adapter_negative_image_embeds, A, "ip_adapter_negative_image_embeds"))
+    for a, (kind, e, n) in enumerate(zip(kinds, embeds, neg)):
+        rank, shape = (3, "[1 or B, S, embed_dim]") if kind == "plus" else (2, "[1 or B, clip_dim]")
+        for name, t in (("ip_adapter_image_embeds", e), ("ip_adapter_negative_image_embeds", n)):
+            if t is None and name == "ip_adapter_negative_image_embeds":
+                continue
+            if not isinstance(t, torch.Tensor) or t.dim() != rank:
+                raise ValueError(f"{name}[{a}] must be a {shape} tensor for a {kind} adapter, got "
+                                 f"{tuple(getattr(t, 'shape', ())) or type(t).__name__}")
+        if kind == "plus" and n is None:
+            raise ValueError(f"adapter {a} is a Plus adapter given as embeddings: its unconditional image tokens are the Resampler of the "
+                             "encoder's output for an all-zero picture, which only the caller has -- pass "
+                             "ip_adapter_negative_image_embeds (same list form)")
+        if n is not None and tuple(n.shape[1:]) != tuple(e.shape[1:]):
+            raise ValueError(f"ip_adapter_negative_image_embeds[{a}] is {tuple(n.shape)}, ip_adapter_image_embeds[{a}] {tuple(e.shape)}")
     return True
 
 
@@ -730,8 +799,10 @@ class ElasticDiffusion(nn.Module):
         return out
 
     @staticmethod
-    def _image_encoder_callable(image_encoder, device):
-        """``image_encoder`` of ``load_ip_adapter`` -> callable pixel_values [1,3,S,S] fp32 -> [1, clip_dim] embeddings (or None)"""
+    def _image_encoder_callable(image_encoder, device, plus=False):
+        """``image_encoder`` of ``load_ip_adapter`` -> callable pixel_values [1,3,S,S] fp32 -> [1, clip_dim] embeddings (or None).
+        ``plus``: a Plus adapter reads the vision model's penultimate hidden states [1, S, embed_dim] instead (section 32); a
+        callable returns whatever its adapter needs."""
         if image_encoder is None:
             return None
         if isinstance(image_encoder, (str, bytes)) or hasattr(image_encoder, "__fspath__"):
@@ -740,63 +811,133 @@ class ElasticDiffusion(nn.Module):
         if isinstance(image_encoder, nn.Module) and hasattr(image_encoder, "config") and hasattr(image_encoder.config, "projection_dim"):
             model = image_encoder.to(device).eval()
             dt = next(model.parameters()).dtype
+            if plus:
+                return lambda pixels: model(pixel_values=pixels.to(dt), output_hidden_states=True).hidden_states[-2]
             return lambda pixels: model(pixel_values=pixels.to(dt)).image_embeds
         if not callable(image_encoder):
             raise ValueError("image_encoder must be a callable pixel_values -> embeds, a transformers.CLIPVisionModelWithProjection "
                              f"or a local directory of one, got {type(image_encoder).__name__}")
         return image_encoder
 
+    def _ip_list(self):
+        """the loaded adapters' pipeline-side state, in load order: [{"name", "encoder", "kind"}]"""
+        st = self.__dict__.get("_ips")
+        if st is None:      # (a pipeline that only ever carried the single-adapter state)
+            one = self.__dict__.get("_ip")
+            return [dict(one, kind=one.get("kind", "base"))] if one else []
+        return st
+
+    def _ip_set(self, entries):
+        self._ips = list(entries)
+        self._ip = self._ips[0] if self._ips else None
+
     @torch.no_grad()
-    def load_ip_adapter(self, source, scale=1.0, image_encoder=None):
-        """Install a base IP-Adapter (``read_ip_adapter``'s sources) into the UNet's cross attentions at ``scale``; every key must
-        fit or nothing is installed (``UNet2DConditionModel.install_ip_adapter``).  ``image_encoder``: what turns
-        ``ip_adapter_image`` into CLIP image embeddings -- a callable pixel_values -> embeds, a
-        ``transformers.CLIPVisionModelWithProjection`` or a local directory of one; without it only
-        ``ip_adapter_image_embeds`` can be given.  One adapter at a time: a second call replaces the first.  Returns its name."""
+    def load_ip_adapter(self, source, scale=1.0, image_encoder=None, *, add=False):
+        """Install an IP-Adapter (``read_ip_adapter``'s sources) into the UNet's cross attentions at ``scale``: a base adapter or a
+        Plus adapter (Resampler image projection).  Every key must fit or nothing is installed
+        (``UNet2DConditionModel.install_ip_adapter``).  ``image_encoder``: what turns ``ip_adapter_image`` into what the adapter
+        reads -- a callable pixel_values -> embeddings (base: [1, clip_dim]; Plus: the penultimate hidden states [1, S, embed_dim]),
+        a ``transformers.CLIPVisionModelWithProjection`` or a local directory of one; without it only ``ip_adapter_image_embeds``
+        can be given.  ``add=False`` replaces whatever is installed; ``add=True`` appends behind it, up to four adapters -- their
+        image tokens follow the text tokens in load order and every run keyword takes one entry per adapter.  Returns its name."""
         if not hasattr(self.unet, "install_ip_adapter"):
             raise ValueError(f"this pipeline's UNet ({type(self.unet).__name__}) cannot carry an IP-Adapter")
         scale = float(scale)
         if not math.isfinite(scale):
             raise ValueError(f"IP-Adapter scale must be finite, got {scale}")
         state, name = read_ip_adapter(source)
-        enc = self._image_encoder_callable(image_encoder, self.device)
+        kind = "plus" if "image_proj.latents" in state else "base"
+        enc = self._image_encoder_callable(image_encoder, self.device, plus=kind == "plus")
+        held = self._ip_list() if add else []
 
         def change():
-            self.unet.install_ip_adapter(state)
-            self.unet.ip_scale = scale
+            self.unet.install_ip_adapter(state, add=bool(add and held))
+            if held:
+                self.unet.ip_scales = self.unet.ip_scales[:-1] + [scale]
+            else:
+                self.unet.ip_scale = scale
             self.unet = self._model_layout(self.unet)
-            self._ip = {"name": name, "encoder": enc}
+            self._ip_set(held + [{"name": name, "encoder": enc, "kind": kind}])
         self._ip_change(change)
         return name
 
-    def set_ip_adapter_scale(self, scale):
-        """New weight of the image prompt (0 = the text-only result, bit for bit where the fused kernel runs)"""
-        if self.ip_adapter is None:
+    def set_ip_adapter_scale(self, scale, name=None):
+        """New weight(s) of the image prompt(s): a float (for the adapter ``name``, or for every adapter) or a list of one float per
+        adapter.  0 = the text-only result, bit for bit where a fused kernel runs.  With two or more adapters the weights are
+        device data every attention reads when it runs: the captured graphs stay and replay with the new weights.  With one
+        adapter the scale is a kernel argument, and the graphs are captured again, as before."""
+        ips = self._ip_list()
+        if not ips:
             raise ValueError("no IP-Adapter is loaded")
-
-        def change():
-            self.unet.ip_scale = scale
-        self._ip_change(change)
-
-    def unload_ip_adapter(self):
-        if self.ip_adapter is None:
+        if isinstance(scale, (list, tuple)):
+            if name is not None or len(scale) != len(ips):
+                raise ValueError(f"{len(ips)} IP-Adapter(s) are loaded: a list of scales has one float per adapter (and no name), got "
+                                 f"{len(scale)}")
+            scales = [float(s) for s in scale]
+        elif name is None:
+            scales = [float(scale)] * len(ips)
+        else:
+            names = [st["name"] for st in ips]
+            if name not in names:
+                raise ValueError(f"no IP-Adapter named {name!r} is loaded (loaded: {names})")
+            scales = list(self.unet.ip_scales)
+            scales[names.index(name)] = float(scale)
+        if not all(math.isfinite(s) for s in scales):
+            raise ValueError(f"IP-Adapter scales must be finite, got {scales}")
+        if len(ips) == 1:
+            def change():
+                self.unet.ip_scale = scales[0]
+            self._ip_change(change)
             return
+        if self.__dict__.get("_live_jobs"):
+            raise RuntimeError("IP-Adapter state cannot change while generate_latents_interleaved has images in flight")
+        with torch.cuda.device(self.device):
+            self.unet.ip_scales = scales       # one copy into the device weights; every captured graph reads them when it replays
+
+    def unload_ip_adapter(self, name=None):
+        """remove the adapter ``name`` (the others keep their order and scales) or, without a name, all of them"""
+        ips = self._ip_list()
+        if not ips:
+            return
+        if name is not None:
+            names = [st["name"] for st in ips]
+            if name not in names:
+                raise ValueError(f"no IP-Adapter named {name!r} is loaded (loaded: {names})")
+            keep = [st for k, st in enumerate(ips) if k != names.index(name)]
+        else:
+            keep = []
 
         def change():
-            self.unet.remove_ip_adapter()
-            self._ip = None
+            if name is None or not keep:
+                self.unet.remove_ip_adapter()
+            else:
+                self.unet.remove_ip_adapter(names.index(name))
+            self._ip_set(keep)
         self._ip_change(change)
 
     @property
     def ip_adapter(self):
-        """None | (name, scale, image tokens)"""
-        st = self.__dict__.get("_ip")
-        return None if not st else (st["name"], self.unet.ip_scale, self.unet.ip_tokens)
+        """None | (name, scale, image tokens) of the first adapter"""
+        ips = self._ip_list()
+        if not ips:
+            return None
+        if len(ips) == 1:
+            return (ips[0]["name"], self.unet.ip_scale, self.unet.ip_tokens)
+        kind, tokens, scale = self.unet.ip_adapters[0]
+        return (ips[0]["name"], scale, tokens)
 
-    def _check_ip_adapter(self, ip_adapter_image=None, ip_adapter_image_embeds=None):
-        st = self.__dict__.get("_ip")
-        return check_ip_adapter_arguments(bool(st), bool(st and st["encoder"] is not None), ip_adapter_image,
-                                          ip_adapter_image_embeds)
+    @property
+    def ip_adapters(self):
+        """[(name, scale, image tokens, "base" | "plus")] in load order"""
+        ips = self._ip_list()
+        if not ips or not hasattr(self.unet, "ip_adapters"):
+            return []
+        return [(st["name"], scale, tokens, kind) for st, (kind, tokens, scale) in zip(ips, self.unet.ip_adapters)]
+
+    def _check_ip_adapter(self, ip_adapter_image=None, ip_adapter_image_embeds=None, ip_adapter_negative_image_embeds=None):
+        ips = self._ip_list()
+        return check_ip_adapter_arguments([st["kind"] for st in ips], [st["encoder"] is not None for st in ips], ip_adapter_image,
+                                          ip_adapter_image_embeds, ip_adapter_negative_image_embeds)
 
     def _clip_pixels(self, image, size=224):
         """``ip_adapter_image`` -> CLIPImageProcessor's pixel_values [1,3,size,size] fp32, on the device: one upload, Pillow's
@@ -813,18 +954,42 @@ class ElasticDiffusion(nn.Module):
             u8 = ops.resize_u8(u8, new, "bicubic")
         return ops.u8_to_clip_input(u8, size)
 
-    def _ip_tokens(self, B, ip_adapter_image=None, ip_adapter_image_embeds=None):
-        """-> (unconditional, conditional) image tokens [B, Ni, cross_dim]: the projection of a zero embedding and of the picture's"""
+    def _ip_tokens(self, B, ip_adapter_image=None, ip_adapter_image_embeds=None, ip_adapter_negative_image_embeds=None):
+        """-> (unconditional, conditional) image tokens [B, sum Ni, cross_dim], the adapters' tokens side by side in load order.
+        Base adapter: the projection of a zero embedding (or of the negative embeddings given) and of the picture's.  Plus adapter:
+        the Resampler of the encoder's output for an all-zero picture (or of the negative embeddings) and of the picture's."""
+        ips = self._ip_list()
+        A = len(ips)
         if ip_adapter_image is not None:
-            embeds = self._ip["encoder"](self._clip_pixels(ip_adapter_image))
+            images, embeds, neg = ip_adapter_entries(ip_adapter_image, A, "ip_adapter_image"), [None] * A, [None] * A
         else:
-            embeds = ip_adapter_image_embeds
-        embeds = torch.as_tensor(embeds).to(self.device)
-        clip_dim = self.unet.ip_image_proj.proj.in_features
-        if embeds.dim() != 2 or embeds.shape[0] not in (1, B) or embeds.shape[1] != clip_dim:
-            raise ValueError(f"image embeddings must be [1 or {B}, {clip_dim}], got {tuple(embeds.shape)}")
-        embeds = embeds.expand(B, -1)
-        return self.unet.ip_image_tokens(torch.zeros_like(embeds)), self.unet.ip_image_tokens(embeds)
+            images, embeds = [None] * A, ip_adapter_entries(ip_adapter_image_embeds, A, "ip_adapter_image_embeds")
+            neg = ([None] * A if ip_adapter_negative_image_embeds is None
+                   else ip_adapter_entries(ip_adapter_negative_image_embeds, A, "ip_adapter_negative_image_embeds"))
+        uns, cos = [], []
+        for a, st in enumerate(ips):
+            rank, width = self.unet.ip_embed_shape(a)
+            e, n = embeds[a], neg[a]
+            if images[a] is not None:
+                pixels = self._clip_pixels(images[a])
+                e = st["encoder"](pixels)
+                if st["kind"] == "plus":
+                    n = st["encoder"](torch.zeros_like(pixels))    # the published pipeline's unconditional image: all-zero pixel values
+            e = torch.as_tensor(e).to(self.device)
+            if e.dim() != rank or e.shape[0] not in (1, B) or e.shape[-1] != width:
+                want = f"[1 or {B}, {width}]" if rank == 2 else f"[1 or {B}, S, {width}]"
+                raise ValueError(f"image embeddings must be {want}, got {tuple(e.shape)}")
+            e = e.expand(B, *e.shape[1:])
+            if n is None:
+                n = torch.zeros_like(e)
+            else:
+                n = torch.as_tensor(n).to(self.device)
+                if n.dim() != rank or n.shape[0] not in (1, B) or n.shape[1:] != e.shape[1:]:
+                    raise ValueError(f"negative image embeddings must match the image embeddings {tuple(e.shape)}, got {tuple(n.shape)}")
+                n = n.expand(B, *n.shape[1:])
+            uns.append(self.unet.ip_image_tokens(n, a))
+            cos.append(self.unet.ip_image_tokens(e, a))
+        return (uns[0], cos[0]) if A == 1 else (torch.cat(uns, dim=1), torch.cat(cos, dim=1))
 
     @torch.no_grad()
     def get_text_embeds(self, prompt, min_chunks=None):
@@ -1650,7 +1815,7 @@ class ElasticDiffusion(nn.Module):
     def _program(self, S, prompts, negative_prompts, condition_image=None, trace=None, progress=_identity_progress,
                  direct=True, frames=None, init_image=None, mask_image=None, mask_blur=0.0, mask_mode="binary",
                  min_chunks=None, ip_adapter_image=None, ip_adapter_image_embeds=None, score_maps=None, regions=None,
-                 region_blur=0.0):
+                 region_blur=0.0, ip_adapter_negative_image_embeds=None):
         """Generator: the denoising loop of ONE image (ED:981-1078), yielding ``_ModelCall``s; returns the final latent.
         All host RNG draws happen inside, in the reference's order.  ``init_image`` / ``mask_image``: image-to-image and
         inpainting -- the loop starts at timestep index ``S.t_start`` from the noised encoding of the
@@ -1688,7 +1853,8 @@ class ElasticDiffusion(nn.Module):
         if ip_adapter_image is not None or ip_adapter_image_embeds is not None:
             # image prompt: the context of every row is [text tokens | image tokens] -- conditional rows carry the picture's tokens,
             # unconditional rows (the V view rows among them, through _embed_rows) the projection of a zero embedding
-            iun, ico = self._ip_tokens(B, ip_adapter_image, ip_adapter_image_embeds)
+            neg = {} if ip_adapter_negative_image_embeds is None else dict(ip_adapter_negative_image_embeds=ip_adapter_negative_image_embeds)
+            iun, ico = self._ip_tokens(B, ip_adapter_image, ip_adapter_image_embeds, **neg)   # (the call as it always was without the keyword)
             un = torch.cat([un, iun.to(un.dtype)], dim=1)
             cos = [torch.cat([c, ico.to(c.dtype)], dim=1) for c in cos]  # the image tokens ride on every conditional row
             co = cos[0]
@@ -1807,7 +1973,7 @@ class ElasticDiffusion(nn.Module):
                          progress=_identity_progress, condition_image=None, controlnet_conditioning_scale=1.0,
                          trace=None, guidance_rescale=0.0, init_image=None, strength=1.0, mask_image=None, *, mask_blur=0.0,
                          mask_mode="binary", min_chunks=None, ip_adapter_image=None, ip_adapter_image_embeds=None,
-                         score_pca=False, regions=None, region_blur=0.0, control_guidance_start=0.0, control_guidance_end=1.0):
+                         ip_adapter_negative_image_embeds=None, score_pca=False, regions=None, region_blur=0.0, control_guidance_start=0.0, control_guidance_end=1.0):
         """``condition_image`` / ``controlnet_conditioning_scale`` / ``control_guidance_start`` / ``control_guidance_end``
         (diffusers 0.21.4's Multi-ControlNet keywords): with a pipeline built on a LIST of N ControlNets,
         ``condition_image`` is a list of N conditions and the other three are floats (applied to every net) or lists of N; net n
@@ -1865,7 +2031,7 @@ class ElasticDiffusion(nn.Module):
         regions, region_blur = check_region_arguments(regions, height, width, self.vae_scale_factor, region_blur,
                                                       self.unet.config.in_channels)
         check_regions_sampler(regions, getattr(self, "scheduler", None))
-        self._check_ip_adapter(ip_adapter_image, ip_adapter_image_embeds)
+        self._check_ip_adapter(ip_adapter_image, ip_adapter_image_embeds, ip_adapter_negative_image_embeds)
         check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
         score_pca = check_score_pca_arguments(score_pca, self._score_channels())
         mask_blur = check_soft_inpaint_arguments(init_image, mask_image, mask_blur, mask_mode,
@@ -1879,7 +2045,7 @@ class ElasticDiffusion(nn.Module):
         x = self._drive(self._program(S, prompts, negative_prompts, condition_image, trace, progress, direct=True,
                                       init_image=init_image, mask_image=mask_image, mask_blur=mask_blur, mask_mode=mask_mode,
                                       min_chunks=min_chunks, ip_adapter_image=ip_adapter_image,
-                                      ip_adapter_image_embeds=ip_adapter_image_embeds, score_maps=maps, regions=regions,
+                                      ip_adapter_image_embeds=ip_adapter_image_embeds, ip_adapter_negative_image_embeds=ip_adapter_negative_image_embeds, score_maps=maps, regions=regions,
                                       region_blur=region_blur))
         self.last_score_pca = maps
         self.last_latents = x
@@ -1919,7 +2085,8 @@ class ElasticDiffusion(nn.Module):
             raise ValueError("either every job of a call carries an image prompt (ip_adapter_image / ip_adapter_image_embeds) or "
                              "none does: the rows of all jobs share one context width")
         for job in jobs:
-            self._check_ip_adapter(job.get("ip_adapter_image"), job.get("ip_adapter_image_embeds"))
+            self._check_ip_adapter(job.get("ip_adapter_image"), job.get("ip_adapter_image_embeds"),
+                                   job.get("ip_adapter_negative_image_embeds"))
         n_chunks = None
         job_regions = [check_region_arguments(job.get("regions"), height, width, self.vae_scale_factor, job.get("region_blur", 0.0),
                                               self.unet.config.in_channels) for job in jobs]
@@ -1970,7 +2137,9 @@ class ElasticDiffusion(nn.Module):
                                  mask_image=job.get("mask_image"), mask_blur=float(job.get("mask_blur", 0.0)),
                                  mask_mode=job.get("mask_mode", "binary"), min_chunks=n_chunks,
                                  ip_adapter_image=job.get("ip_adapter_image"),
-                                 ip_adapter_image_embeds=job.get("ip_adapter_image_embeds"), score_maps=self.job_score_pca.get(j),
+                                 ip_adapter_image_embeds=job.get("ip_adapter_image_embeds"),
+                                 ip_adapter_negative_image_embeds=job.get("ip_adapter_negative_image_embeds"),
+                                 score_maps=self.job_score_pca.get(j),
                                  regions=job_regions[j][0], region_blur=job_regions[j][1])
             with rng:
                 call = next(prog)
@@ -2182,7 +2351,8 @@ class ElasticDiffusion(nn.Module):
                        progress=_default_progress, tiled_decoder=False, grid=False, guidance_rescale=0.0, *,
                        condition_image=None, controlnet_conditioning_scale=1.0, output_type="pil", init_image=None,
                        strength=1.0, mask_image=None, mask_blur=0.0, mask_mode="binary", composite=False,
-                       ip_adapter_image=None, ip_adapter_image_embeds=None, score_pca=False, regions=None, region_blur=0.0,
+                       ip_adapter_image=None, ip_adapter_image_embeds=None, ip_adapter_negative_image_embeds=None, score_pca=False,
+                       regions=None, region_blur=0.0,
                        control_guidance_start=0.0, control_guidance_end=1.0):
         """ED:953-965 signature (ControlNet keywords of EDC:1120-1134 are keyword-only here), then ``guidance_rescale``
         (diffusers' keyword) and, keyword-only, ``init_image`` / ``strength`` / ``mask_image`` / ``mask_blur`` / ``mask_mode``
@@ -2196,7 +2366,7 @@ class ElasticDiffusion(nn.Module):
         Returns ``(images, image_log)``; images are PIL by default, a float tensor with ``output_type='pt'``."""
         check_region_arguments(regions, height, width, self.vae_scale_factor, region_blur, self.unet.config.in_channels)
         check_regions_sampler(regions, getattr(self, "scheduler", None))
-        self._check_ip_adapter(ip_adapter_image, ip_adapter_image_embeds)
+        self._check_ip_adapter(ip_adapter_image, ip_adapter_image_embeds, ip_adapter_negative_image_embeds)
         check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
         check_soft_inpaint_arguments(init_image, mask_image, mask_blur, mask_mode, composite, output_type, grid,
                                      latent_size=(height // self.vae_scale_factor, width // self.vae_scale_factor))
@@ -2206,7 +2376,7 @@ class ElasticDiffusion(nn.Module):
                                   cosine_scale, repaint_sampling, progress, condition_image,
                                   controlnet_conditioning_scale, guidance_rescale=guidance_rescale, init_image=init_image,
                                   strength=strength, mask_image=mask_image, mask_blur=mask_blur, mask_mode=mask_mode,
-                                  ip_adapter_image=ip_adapter_image, ip_adapter_image_embeds=ip_adapter_image_embeds,
+                                  ip_adapter_image=ip_adapter_image, ip_adapter_image_embeds=ip_adapter_image_embeds, ip_adapter_negative_image_embeds=ip_adapter_negative_image_embeds,
                                   score_pca=score_pca, regions=regions, region_blur=region_blur,
                                   control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end)
         dec = self.tiled_decode if tiled_decoder else self.decode_latents
@@ -2431,11 +2601,12 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
                        rrg_scherduler_cls=CosineScheduler, cosine_scale=3.0, repaint_sampling=True,
                        progress=_default_progress, tiled_decoder=False, grid=False, guidance_rescale=0.0, *,
                        output_type="pil", init_image=None, strength=1.0, mask_image=None, mask_blur=0.0, mask_mode="binary",
-                       composite=False, ip_adapter_image=None, ip_adapter_image_embeds=None, score_pca=False, regions=None,
+                       composite=False, ip_adapter_image=None, ip_adapter_image_embeds=None, ip_adapter_negative_image_embeds=None,
+                       score_pca=False, regions=None,
                        region_blur=0.0, control_guidance_start=0.0, control_guidance_end=1.0):
         check_region_arguments(regions, height, width, self.vae_scale_factor, region_blur, self.unet.config.in_channels)
         check_regions_sampler(regions, getattr(self, "scheduler", None))
-        self._check_ip_adapter(ip_adapter_image, ip_adapter_image_embeds)
+        self._check_ip_adapter(ip_adapter_image, ip_adapter_image_embeds, ip_adapter_negative_image_embeds)
         check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
         check_soft_inpaint_arguments(init_image, mask_image, mask_blur, mask_mode, composite, output_type, grid,
                                      latent_size=(height // self.vae_scale_factor, width // self.vae_scale_factor))
@@ -2456,6 +2627,6 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
                                       condition_image=cond, controlnet_conditioning_scale=controlnet_conditioning_scale,
                                       output_type=output_type, init_image=init_image, strength=strength,
                                       mask_image=mask_image, mask_blur=mask_blur, mask_mode=mask_mode, composite=composite,
-                                      ip_adapter_image=ip_adapter_image, ip_adapter_image_embeds=ip_adapter_image_embeds,
+                                      ip_adapter_image=ip_adapter_image, ip_adapter_image_embeds=ip_adapter_image_embeds, ip_adapter_negative_image_embeds=ip_adapter_negative_image_embeds,
                                       score_pca=score_pca, regions=regions, region_blur=region_blur,
                                       control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end)

@@ -606,6 +606,22 @@ int ed_flash_attention_ip(const void* q, const void* k, const void* v, void* out
                           int64_t o_sb, int64_t o_sn, float scale, float ip_scale, void* stream);
 
 /*
+ * ed_flash_attention_ipn -- several IP-Adapters in one launch (an addition, still ABI v13):
+ *       out = softmax(q k_t^T scale) v_t + sum_{a < A} w[a] * softmax(q k_a^T scale) v_a
+ *   k, v dtype [B, Nt + sum ni, H, 64]: the Nt text rows, then adapter 0's ni[0] rows, adapter 1's ni[1] rows, ...; ni is a HOST
+ *   array of A ints, w a DEVICE pointer to A fp32 weights read when the kernel runs (a captured graph replays a change of weights).
+ *   q, out, dtype, strides and alignment as ed_flash_attention_ip.  head_dim = 64, 1 <= Nt <= 160, 1 <= A <= 4, every ni[a] >= 1,
+ *   sum ni <= 32; anything else returns hipErrorInvalidValue before any launch.  ed_flash_attention_ip's staging with the image
+ *   block cut into A segments: one maximum and one sum per segment, probabilities normalised and weighted in fp32 before they are
+ *   packed (p_j = e_j * fl(w[a] * inv_a)), one accumulator for the whole image term, stored fl(o_t * inv_t) + o_i rounded once.
+ *   The text term is the small-KV kernel's operation for operation: with every w[a] = 0 the output equals
+ *   ed_flash_attention(v_path 8) on the text rows alone bit for bit.
+ */
+int ed_flash_attention_ipn(const void* q, const void* k, const void* v, void* out, int dtype, int B, int H, int Nq, int Nt, int A,
+                           const int* ni, int head_dim, int64_t q_sb, int64_t q_sn, int64_t k_sb, int64_t k_sn, int64_t v_sb,
+                           int64_t v_sn, int64_t o_sb, int64_t o_sn, float scale, const float* w, void* stream);
+
+/*
  * ed_groupnorm_f32 -- GroupNorm (+SiLU) of an fp32 NCHW activation: the VAE's normalisation layers (AutoencoderKL inside
  * ED:270 decode / ED:350 encode; fp32 like the reference keeps it, ED:328).  HW % 4 == 0.  Two launches: partial sums over
  * 64 K-element chunks of every (sample, group), then an apply pass whose blocks combine their group's partials in double.
