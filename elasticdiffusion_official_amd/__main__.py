@@ -149,6 +149,9 @@ def build_parser():
                     "[1, clip_dim] (Plus: penultimate hidden states [1, S, embed_dim]): a .pt (torch.save of a tensor) or .npy file")
     ap.add_argument("--ip_adapter_negative_embeds", action=_Repeat, default=None, help="the unconditional embeddings a Plus adapter "
                     "given as --ip_adapter_embeds needs (.pt / .npy; 'none' at the position of a base adapter)")
+    ap.add_argument("--ip_adapter_mask", action="append", default=[], metavar="FILE|x0,y0,x1,y1", help="where an adapter's image "
+                    "prompt applies: a mask picture at H x W (white = applies), a box in pixels, or 'none'; repeatable, matched by "
+                    "position with --ip_adapter (DESIGN.md section 33)")
     ap.add_argument("--image_encoder", action=_Repeat, default=None, help="local directory of a transformers "
                     "CLIPVisionModelWithProjection, for --ip_adapter_image (one for all adapters, or one per adapter)")
     ap.add_argument("--score_pca", type=_bool, default=False, help="true: every --log_freq steps, save the PCA maps of the class "
@@ -197,6 +200,31 @@ def parse_regions(opt, open_image=None):
             mask = open_image(mask)
         regions.append((prompt, mask, weight))
     return regions
+
+
+def parse_ip_adapter_masks(opt, n_adapters, open_image=None):
+    """The ``ip_adapter_masks`` list of ``generate_image`` from --ip_adapter_mask, or None without the flag; SystemExit on a count
+    other than --ip_adapter's or a mask file that does not exist.  ``open_image`` as in ``parse_regions``."""
+    if not opt.ip_adapter_mask:
+        return None
+    if len(opt.ip_adapter_mask) != n_adapters:
+        raise SystemExit(f"--ip_adapter_mask is matched by position with --ip_adapter ('none' for an adapter without a mask): got "
+                         f"{len(opt.ip_adapter_mask)} masks for {n_adapters} adapters")
+    if open_image is None:
+        from PIL import Image
+        open_image = lambda path: Image.open(path).convert("L")  # noqa: E731
+    masks = []
+    for text in opt.ip_adapter_mask:
+        parts = text.split(",")
+        if text.lower() == "none":
+            masks.append(None)
+        elif len(parts) == 4 and all(p.strip().lstrip("-").isdigit() for p in parts):
+            masks.append(tuple(int(p) for p in parts))
+        elif not os.path.isfile(text):
+            raise SystemExit(f"--ip_adapter_mask: no such file {text!r} (a box is x0,y0,x1,y1)")
+        else:
+            masks.append(open_image(text))
+    return masks
 
 
 def _load_embeds(path):
@@ -293,6 +321,13 @@ def main(argv=None):
                 raise SystemExit(f"--image_encoder: no such directory {d!r}")
     elif opt.ip_adapter_image or opt.ip_adapter_embeds or opt.image_encoder or opt.ip_adapter_negative_embeds:
         raise SystemExit("--ip_adapter_image / --ip_adapter_embeds / --image_encoder need --ip_adapter")
+    ip_masks = parse_ip_adapter_masks(opt, len(ip or ()))
+    if ip_masks is not None:
+        from .pipeline import check_ip_adapter_mask_arguments
+        try:
+            check_ip_adapter_mask_arguments(len(ip), ip_masks, opt.H, opt.W)
+        except ValueError as e:
+            raise SystemExit(f"--ip_adapter_mask: {e}")
     pads = None
     if opt.outpaint is not None:
         if opt.mask_image or not opt.init_image:
@@ -369,6 +404,8 @@ def main(argv=None):
             if negs:
                 neg = [None if f.lower() == "none" else _load_embeds(f) for f in negs]
                 extra["ip_adapter_negative_image_embeds"] = neg[0] if one else neg
+        if ip_masks is not None:
+            extra["ip_adapter_masks"] = ip_masks
     if opt.init_image:
         from PIL import Image
         extra["init_image"], extra["strength"] = Image.open(opt.init_image).convert("RGB"), opt.strength

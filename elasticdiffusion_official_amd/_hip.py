@@ -138,6 +138,9 @@ SIGNATURES = {
     "ed_control_residuals": [_vp, _i, _i, _vp, _i64, _vp],
     "ed_flash_attention_ipn": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f,
                                _vp, _vp],
+    "ed_flash_attention_ipm": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f,
+                               _vp, _vp, _i64, _i64, _vp],
+    "ed_ip_mask_rows": [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp],
 }
 
 _LIB = None

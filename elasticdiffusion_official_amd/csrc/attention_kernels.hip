@@ -1259,6 +1259,178 @@ k_flash_attn_ipn(const ParamsIpn pi) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// IP-Adapter attention masks: k_flash_attn_ipn with a per-row, per-adapter factor on the image term,
+//   out = softmax(q k_t^T s) v_t + sum_a (w[a] * m[b, a, i]) * softmax(q k_a^T s) v_a        (i: the query row)
+// Staging, segments, softmaxes, accumulators and the store are k_flash_attn_ipn's; the one change is the coefficient of
+// segment a for the lane's query row, c_a = fl(fl(w[a] * m[b, a, q_row]) * (1 / psum_a)).  m is read once per lane, adapter
+// and query block, only for q_row < Nq (a lane past Nq computes with 0 and stores nothing).  m == 1 gives k_flash_attn_ipn's
+// bits (w * 1 is w), m == 0 or w == 0 the small-KV kernel's on the text rows.
+// ---------------------------------------------------------------------------------------------------------------------
+struct ParamsIpm {
+  ParamsIpn n;
+  const float* m;      // [.., A, >= Nq] floats: element (b, a, i) at b * m_sb + a * m_sa + i
+  int64_t m_sb, m_sa;  // m_sb may be 0: one mask for the whole batch
+};
+
+template <typename T, int NKB>
+__global__ void __launch_bounds__(256, 2)
+k_flash_attn_ipm(const ParamsIpm pm) {
+  __shared__ SmemSmall<NKB + 1> sm;
+  const ParamsIpn& pi = pm.n;
+  const Params& p = pi.p;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int ln = lane & 31, hi = lane >> 5;
+  const int nqg = p.nqb;
+  const int bh = blockIdx.x / nqg, qgrp = blockIdx.x - bh * nqg;
+  const int b = bh / p.H, h = bh - b * p.H;
+  const uint16_t* qg = p.q + b * p.q_sb + h * D;
+  const uint16_t* kg = p.k + b * p.k_sb + h * D;
+  const uint16_t* vg = p.v + b * p.v_sb + h * D;
+  uint16_t* og = p.o + b * p.o_sb + h * D;
+  const float* mg = pm.m + b * pm.m_sb;
+  const int Nt = p.Nk, Ni = pi.end[IPN_MAX - 1], A = pi.A;
+  float wa[IPN_MAX];
+#pragma unroll
+  for (int a = 0; a < IPN_MAX; ++a) wa[a] = a < A ? pi.w[a] : 0.f;
+  int seg[16];  // as in k_flash_attn_ipn: the segment of each of this lane's 16 image keys, IPN_MAX for a key of no segment
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int j = 8 * (r >> 2) + 4 * hi + (r & 3);
+    seg[r] = 0;
+#pragma unroll
+    for (int a = 0; a < IPN_MAX; ++a) seg[r] += j >= pi.end[a] ? 1 : 0;
+  }
+
+  for (int idx = tid; idx < 32 * (NKB + 1) * 8; idx += 256) {
+    const int row = idx >> 3, col = (idx & 7) * 8;
+    const bool img = row >= 32 * NKB;
+    const int j = row - 32 * NKB;
+    const int src = img ? Nt + j : row;
+    const int lim = img ? Nt + Ni : Nt;
+    *reinterpret_cast<Vec16*>(&sm.k[row * K_LD + col]) = load_row16(kg, p.k_sn, src, lim, col);
+    *reinterpret_cast<Vec16*>(&sm.v[row * V_LD_TR + col]) = load_row16(vg, p.v_sn, src, lim, col);
+  }
+  __syncthreads();
+  const float sl = p.scale_log2e;
+
+  for (int qb = 0; qb < SK_QBLOCKS; ++qb) {
+    const int q_row = (qgrp * SK_QBLOCKS + qb) * QB + wave * 32 + ln;
+    if ((qgrp * SK_QBLOCKS + qb) * QB + wave * 32 >= p.Nq) break;  // wave-uniform: nothing left for this wave
+    typename T::v8 qf[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) qf[ks] = as_v8<typename T::v8>(load_row16(qg, p.q_sn, q_row, p.Nq, 16 * ks + 8 * hi));
+    f32x16 s[NKB + 1];
+#pragma unroll
+    for (int kb = 0; kb <= NKB; ++kb)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) s[kb][i] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+      for (int kb = 0; kb <= NKB; ++kb) {
+        const Vec16 kf = *reinterpret_cast<const Vec16*>(&sm.k[(32 * kb + ln) * K_LD + 16 * ks + 8 * hi]);
+        s[kb] = T::mfma(as_v8<typename T::v8>(kf), qf[ks], s[kb]);
+      }
+    // text softmax: k_flash_attn_smallkv's, over blocks 0 .. NKB - 1
+    float mx = -INFINITY;
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        if (32 * kb + 8 * (r >> 2) + 4 * hi + (r & 3) >= Nt) s[kb][r] = -INFINITY;
+        mx = fmaxf(mx, s[kb][r]);
+      }
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float mb = mx * sl;
+    float psum = 0.f;
+#pragma unroll
+    for (int kb = 0; kb < NKB; ++kb)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(s[kb][r], sl, -mb));
+        s[kb][r] = e;
+        psum += e;
+      }
+    psum += __shfl_xor(psum, 32, 64);
+    const float inv = 1.0f / psum;
+    // image softmaxes: k_flash_attn_ipn's, with wm[a] in the place of w[a]
+    // the row's weights: w[a] * m[b, a, q_row], rounded once; both half-waves of a row read the same word
+    float wm[IPN_MAX];
+#pragma unroll
+    for (int a = 0; a < IPN_MAX; ++a) wm[a] = (a < A && q_row < p.Nq) ? wa[a] * mg[a * pm.m_sa + q_row] : 0.f;
+    float mxa[IPN_MAX], mba[IPN_MAX], psa[IPN_MAX], ca[IPN_MAX], sel[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      if (seg[r] == IPN_MAX) s[NKB][r] = -INFINITY;
+#pragma unroll
+    for (int a = 0; a < IPN_MAX; ++a) {
+      mxa[a] = -INFINITY;
+      if (a < A) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) mxa[a] = fmaxf(mxa[a], seg[r] == a ? s[NKB][r] : -INFINITY);
+        mxa[a] = fmaxf(mxa[a], __shfl_xor(mxa[a], 32, 64));
+      }
+      mba[a] = mxa[a] * sl;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sel[r] = 0.f;
+#pragma unroll
+    for (int a = 0; a < IPN_MAX; ++a)
+      if (a < A) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sel[r] = seg[r] == a ? mba[a] : sel[r];
+      }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s[NKB][r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[NKB][r], sl, -sel[r]));
+#pragma unroll
+    for (int r = 0; r < 16; ++r) sel[r] = 0.f;
+#pragma unroll
+    for (int a = 0; a < IPN_MAX; ++a) {
+      psa[a] = 0.f, ca[a] = 0.f;
+      if (a < A) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) psa[a] += seg[r] == a ? s[NKB][r] : 0.f;
+        psa[a] += __shfl_xor(psa[a], 32, 64);
+        ca[a] = wm[a] * (1.0f / psa[a]);   // a segment's sum is >= 1: its maximum gives e = 1
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sel[r] = seg[r] == a ? ca[a] : sel[r];
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s[NKB][r] *= sel[r];
+    f32x16 o[2], oi[2];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) o[0][i] = o[1][i] = oi[0][i] = oi[1][i] = 0.f;
+#pragma unroll
+    for (int st = 0; st < 2 * NKB; ++st) {
+      f32x8 pv;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) pv[j] = s[st >> 1][8 * (st & 1) + j];
+      const typename T::v8 pf = T::pack(pv);
+#pragma unroll
+      for (int db = 0; db < 2; ++db)
+        o[db] = T::mfma(as_v8<typename T::v8>(v_frag_tr(sm.v, lane, hi, st, db)), pf, o[db]);
+    }
+#pragma unroll
+    for (int st = 2 * NKB; st < 2 * NKB + 2; ++st) {
+      f32x8 pv;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) pv[j] = s[NKB][8 * (st & 1) + j];
+      const typename T::v8 pf = T::pack(pv);
+#pragma unroll
+      for (int db = 0; db < 2; ++db)
+        oi[db] = T::mfma(as_v8<typename T::v8>(v_frag_tr(sm.v, lane, hi, st, db)), pf, oi[db]);
+    }
+#pragma unroll
+    for (int db = 0; db < 2; ++db)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) o[db][i] = o[db][i] * inv + oi[db][i];
+    store_o_row<T>(og + (int64_t)q_row * p.o_sn, o, 1.0f, hi, q_row < p.Nq);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Round 4: any head dimension that is a multiple of 8 up to 160 (SD 1.x: 8 heads of 40 / 80 / 160; SD 2.x: 64).  Round 3's
 // kernels are head_dim 64 only, so the SD1.5 workload (BASELINE.json configs[1]) still went through SDPA -- AOTriton's
 // `attn_fwd`, 25 % of its GPU time (profiles/r4_s5_bench_cfg2_sd15_512x1024_kernel_stats.csv).  Same design as
@@ -1600,6 +1772,46 @@ int ed_flash_attention_ipn(const void* q, const void* k, const void* v, void* ou
   else k_flash_attn_ipn<HF, NKB><<<grid, block, 0, st>>>(pi);
   if (Nt <= 64) { ED_FIPN(2) } else if (Nt <= 96) { ED_FIPN(3) } else { ED_FIPN(5) }
 #undef ED_FIPN
+  return (int)hipGetLastError();
+}
+
+int ed_flash_attention_ipm(const void* q, const void* k, const void* v, void* out, int dtype, int B, int H, int Nq, int Nt, int A,
+                           const int* ni, int head_dim, int64_t q_sb, int64_t q_sn, int64_t k_sb, int64_t k_sn, int64_t v_sb,
+                           int64_t v_sn, int64_t o_sb, int64_t o_sn, float scale, const float* w, const float* m, int64_t m_sb,
+                           int64_t m_sa, void* stream) {
+  if (head_dim != D || Nt < 1 || Nt > 160 || A < 1 || A > IPN_MAX || !ni || !w || !m) return (int)hipErrorInvalidValue;
+  ParamsIpm pm;
+  ParamsIpn& pi = pm.n;
+  int total = 0;
+  for (int a = 0; a < A; ++a) {
+    if (ni[a] < 1 || ni[a] > 32) return (int)hipErrorInvalidValue;
+    total += ni[a];
+    pi.end[a] = total;
+  }
+  if (total > 32) return (int)hipErrorInvalidValue;
+  for (int a = A; a < IPN_MAX; ++a) pi.end[a] = total;   // empty segments
+  if (dtype != ED_BF16 && dtype != ED_F16) return (int)hipErrorInvalidValue;
+  if (B < 0 || H < 0 || Nq < 0) return (int)hipErrorInvalidValue;
+  if (m_sb < 0 || m_sa < Nq || ((uintptr_t)m & 3u)) return (int)hipErrorInvalidValue;
+  if (B == 0 || H == 0 || Nq == 0) return 0;
+  if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15u) || ((uintptr_t)out & 7u) || ((uintptr_t)w & 3u)) return (int)hipErrorInvalidValue;
+  if ((q_sb | q_sn | k_sb | k_sn | v_sb | v_sn) % 8 || (o_sb | o_sn) % 4) return (int)hipErrorInvalidValue;
+  Params& p = pi.p;
+  p.q = (const uint16_t*)q, p.k = (const uint16_t*)k, p.v = (const uint16_t*)v, p.o = (uint16_t*)out;
+  p.Nq = Nq, p.Nk = Nt, p.H = H, p.BH = B * H, p.nqb = (Nq + QB * SK_QBLOCKS - 1) / (QB * SK_QBLOCKS);
+  p.q_sb = q_sb, p.q_sn = q_sn, p.k_sb = k_sb, p.k_sn = k_sn, p.v_sb = v_sb, p.v_sn = v_sn, p.o_sb = o_sb, p.o_sn = o_sn;
+  p.scale_log2e = scale * 1.44269504088896340736f;
+  pi.A = A, pi.w = w;
+  pm.m = m, pm.m_sb = m_sb, pm.m_sa = m_sa;
+  const int64_t nb = (int64_t)p.BH * p.nqb;
+  if (nb > 0x7fffffff) return (int)hipErrorInvalidValue;
+  const dim3 grid((unsigned)nb), block(256);
+  hipStream_t st = (hipStream_t)stream;
+#define ED_FIPM(NKB)                                                           \
+  if (dtype == ED_BF16) k_flash_attn_ipm<BF, NKB><<<grid, block, 0, st>>>(pm); \
+  else k_flash_attn_ipm<HF, NKB><<<grid, block, 0, st>>>(pm);
+  if (Nt <= 64) { ED_FIPM(2) } else if (Nt <= 96) { ED_FIPM(3) } else { ED_FIPM(5) }
+#undef ED_FIPM
   return (int)hipGetLastError();
 }
 

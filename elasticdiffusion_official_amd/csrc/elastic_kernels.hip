@@ -664,6 +664,89 @@ k_assemble_rows_n(const AssembleArgsN a) {
   }
 }
 
+// ---- ed_ip_mask_rows: per-row IP-Adapter attention masks, four pyramid levels in ONE launch ----------
+// A workgroup of one wave owns an 8 x 8 patch of level 0 of one (step or view, sample, adapter) plane: lane (ty, tx) gathers its
+// pixel exactly as the extra channels of ed_assemble_rows_n are gathered with pad_value = 0, the patch goes to LDS, and 16 / 4 / 1
+// lanes form its 4 x 4 / 2 x 2 / 1 pixels of levels 1 / 2 / 3 as 0.25f * ((a + b) + (c + d)), each operation rounded on its own.
+// A step's plane is stored `copies` times (the rows of one step share their frame), a view's once.
+struct IpMaskArgs {
+  const float* masks;  // [B,A,H,W]
+  int B, A, H, W;
+  const uint8_t* idx;
+  const int32_t *src_row, *src_col;
+  int K, h, w, g_off_y, g_off_x;
+  const int32_t *win_y0, *win_x0;
+  int V, Sh, Sw, v_off_y, v_off_x;
+  int PH, PW, copies;
+  float* m;            // [(K*copies + V)*B, A, S]
+  int S, pick_blocks;  // S = sum over the four levels; pick_blocks = K*B*A*(PH/8)*(PW/8)
+};
+
+__global__ void __launch_bounds__(64)
+k_ip_mask_rows(const IpMaskArgs a) {
+  __shared__ float l0[64], l1[16], l2[4];
+  const int tid = threadIdx.x, ty = tid >> 3, tx = tid & 7;
+  const bool pick = (int)blockIdx.x < a.pick_blocks;
+  int r = pick ? (int)blockIdx.x : (int)blockIdx.x - a.pick_blocks;
+  const int npx = a.PW >> 3, npy = a.PH >> 3;
+  const int px = r % npx;
+  r /= npx;
+  const int py = r % npy;
+  r /= npy;
+  const int ad = r % a.A;
+  r /= a.A;
+  const int b = r % a.B, kv = r / a.B;  // kv: the resampling step or the view
+  const int y = 8 * py + ty, x = 8 * px + tx;
+  const float* plane = a.masks + ((int64_t)b * a.A + ad) * a.H * a.W;
+  float val = 0.0f;
+  int sy = -1, sx = -1;
+  if (pick) {
+    const int i = y - a.g_off_y, j = x - a.g_off_x;
+    if (i >= 0 && i < a.h && j >= 0 && j < a.w) {
+      const int q = a.idx[(int64_t)kv * a.h * a.w + (int64_t)i * a.w + j];
+      sy = a.src_row[2 * i + ((q >> 1) & 1)];
+      sx = a.src_col[2 * j + (q & 1)];
+    }
+  } else {
+    const int yy = y - a.v_off_y, xx = x - a.v_off_x;
+    if (yy >= 0 && yy < a.Sh && xx >= 0 && xx < a.Sw) sy = a.win_y0[kv] + yy, sx = a.win_x0[kv] + xx;
+  }
+  if (sy >= 0 && sy < a.H && sx >= 0 && sx < a.W) val = plane[(int64_t)sy * a.W + sx];
+  l0[tid] = val;
+  __syncthreads();
+  float v1 = 0.0f, v2 = 0.0f, v3 = 0.0f;
+  if (tid < 16) {
+    const int yy = tid >> 2, xx = tid & 3;
+    v1 = __fmul_rn(0.25f, __fadd_rn(__fadd_rn(l0[16 * yy + 2 * xx], l0[16 * yy + 2 * xx + 1]),
+                                    __fadd_rn(l0[16 * yy + 8 + 2 * xx], l0[16 * yy + 8 + 2 * xx + 1])));
+    l1[tid] = v1;
+  }
+  __syncthreads();
+  if (tid < 4) {
+    const int yy = tid >> 1, xx = tid & 1;
+    v2 = __fmul_rn(0.25f, __fadd_rn(__fadd_rn(l1[8 * yy + 2 * xx], l1[8 * yy + 2 * xx + 1]),
+                                    __fadd_rn(l1[8 * yy + 4 + 2 * xx], l1[8 * yy + 4 + 2 * xx + 1])));
+    l2[tid] = v2;
+  }
+  __syncthreads();
+  if (tid == 0) v3 = __fmul_rn(0.25f, __fadd_rn(__fadd_rn(l2[0], l2[1]), __fadd_rn(l2[2], l2[3])));
+  // level L at offset sum_{l<L} (PH>>l)(PW>>l) of the row's [S] floats
+  const int o1 = a.PH * a.PW, o2 = o1 + (o1 >> 2), o3 = o2 + (o1 >> 4);
+  const int e0 = y * a.PW + x;
+  const int e1 = o1 + (4 * py + (tid >> 2)) * (a.PW >> 1) + 4 * px + (tid & 3);
+  const int e2 = o2 + (2 * py + (tid >> 1)) * (a.PW >> 2) + 2 * px + (tid & 1);
+  const int e3 = o3 + py * (a.PW >> 3) + px;
+  const int n = pick ? a.copies : 1;
+  for (int q = 0; q < n; ++q) {
+    const int64_t row = pick ? ((int64_t)kv * a.copies + q) * a.B + b : ((int64_t)a.K * a.copies + kv) * a.B + b;
+    float* out = a.m + (row * a.A + ad) * a.S;
+    out[e0] = val;
+    if (tid < 16) out[e1] = v1;
+    if (tid < 4) out[e2] = v2;
+    if (tid == 0) out[e3] = v3;
+  }
+}
+
 // ---- ed_phase_epilogue: unpad + fill + scatter + CFG/DDIM (+ RRG) in ONE launch ---------------------
 // Everything downstream of the model call is a per-output-pixel gather: which resampling step covers the pixel (stamp
 // table) -> cond - uncond of that step's rows; the first non-zero covering view centre; the DDIM update; optionally the
@@ -1689,6 +1772,30 @@ int ed_assemble_rows_n(const float* latent, int B, int C, int H, int W, const ui
     default: return (int)hipErrorInvalidValue;
   }
 #undef ED_ASM_N
+  return done();
+}
+
+int ed_ip_mask_rows(const float* masks, int B, int A, int H, int W, const uint8_t* idx, const int32_t* src_row,
+                    const int32_t* src_col, int K, int h, int w, int g_off_y, int g_off_x, const int32_t* win_y0,
+                    const int32_t* win_x0, int V, int Sh, int Sw, int v_off_y, int v_off_x, int PH, int PW, int copies, float* m,
+                    void* stream) {
+  if (!masks || !m || A < 1 || A > 4 || copies < 2 || copies > 1 + ED_MAX_REGION_ROWS || B < 0 || K < 0 || V < 0 || H < 1 || W < 1 ||
+      h < 0 || w < 0 || Sh < 0 || Sw < 0 || PH < 8 || PW < 8 || (PH & 7) || (PW & 7) || PH > 4096 || PW > 4096 || g_off_y < 0 ||
+      g_off_x < 0 || g_off_y + h > PH || g_off_x + w > PW || v_off_y < 0 || v_off_x < 0 || v_off_y + Sh > PH || v_off_x + Sw > PW)
+    return (int)hipErrorInvalidValue;
+  if ((int64_t)(K + V) * B == 0) return 0;
+  if ((K && (!idx || !src_row || !src_col)) || (V && (!win_y0 || !win_x0))) return (int)hipErrorInvalidValue;
+  const int64_t patches = (int64_t)B * A * (PH >> 3) * (PW >> 3);
+  if (patches * ((int64_t)K + V) > 0x7fffffff) return (int)hipErrorInvalidValue;
+  IpMaskArgs a;
+  a.masks = masks, a.B = B, a.A = A, a.H = H, a.W = W;
+  a.idx = idx, a.src_row = src_row, a.src_col = src_col, a.K = K, a.h = h, a.w = w, a.g_off_y = g_off_y, a.g_off_x = g_off_x;
+  a.win_y0 = win_y0, a.win_x0 = win_x0, a.V = V, a.Sh = Sh, a.Sw = Sw, a.v_off_y = v_off_y, a.v_off_x = v_off_x;
+  a.PH = PH, a.PW = PW, a.copies = copies, a.m = m;
+  a.S = PH * PW + (PH >> 1) * (PW >> 1) + (PH >> 2) * (PW >> 2) + (PH >> 3) * (PW >> 3);
+  a.pick_blocks = (int)(patches * K);
+  dim3 grid((unsigned)(patches * ((int64_t)K + V))), block(64);
+  k_ip_mask_rows<<<grid, block, 0, (hipStream_t)stream>>>(a);
   return done();
 }
 

@@ -560,6 +560,20 @@ class Attention(nn.Module):
         # [A] that replaces the by-value ``ip_scale`` from two adapters on.
         self.ip_segments = ()
         self.ip_weights = None
+        # Attention masks: (m f32 [B, A, S], PH, PW, w f32 [A]) for the duration of one
+        # ``UNet2DConditionModel.forward(ip_masks=)``, None otherwise -- and then every branch below is what it was.
+        self.ip_mask = None
+
+    def _ip_mask_level(self, B, N):
+        """the level of the mask pyramid a cross attention of ``N`` query rows reads: a view [B, A, N] of the rows' buffer"""
+        m, PH, PW, _ = self.ip_mask
+        if m.shape[0] != B:
+            raise ValueError(f"ip_masks holds {m.shape[0]} rows, the batch {B}")
+        for off, n in ops.ip_mask_layout(PH, PW)[0]:
+            if n == N:
+                return m[:, :, off:off + n]
+        raise ValueError(f"a cross attention with {N} query rows matches no level of the {PH} x {PW} mask pyramid "
+                         f"({[n for _, n in ops.ip_mask_layout(PH, PW)[0]]})")
 
     @staticmethod
     def ip_names(a):
@@ -666,7 +680,20 @@ class Attention(nn.Module):
                     kv = self.project_kv(context)
                 k, v = kv[..., :inner], kv[..., inner:]
                 nt = kv.shape[1] - self.ip_tokens
-                if len(self.ip_segments) >= 2:
+                if self.ip_mask is not None:
+                    # masked image prompts (section 33), any adapter count: one ed_flash_attention_ipm launch where it takes the shape,
+                    # else A + 1 attentions combined with DEVICE tensors only -- a replayed graph follows new masks and scales
+                    mv, w = self._ip_mask_level(B, N), self.ip_mask[3]
+                    if ops.flash_attention_ipm_ok(inner // self.heads, nt, self.ip_segments):
+                        o = ops.flash_attention_ipm(q, k, v, self.heads, nt, self.ip_segments, w, mv)
+                    else:
+                        o = ops.flash_attention(q, k[:, :nt], v[:, :nt], self.heads)
+                        wd = w.to(o.dtype)
+                        for a, (lo, hi) in enumerate(self._ip_rows(kv.shape[1])):
+                            o_a = ops.flash_attention(q, k[:, lo:hi], v[:, lo:hi], self.heads)
+                            # o + (w[a] m_a) o_a as section 32's addcmul: at m == 1 the bits of the unmasked fallback
+                            o = o.addcmul_(o_a, (wd[a] * mv[:, a].to(o.dtype))[..., None])
+                elif len(self.ip_segments) >= 2:
                     # several adapters: one ed_flash_attention_ipn launch where it takes the shape, else A + 1 attentions combined
                     # with the DEVICE weights by a tensor multiply -- never a Python float, so a replayed graph follows a new scale
                     if ops.flash_attention_ipn_ok(inner // self.heads, nt, self.ip_segments):
@@ -700,7 +727,12 @@ class Attention(nn.Module):
             nt = kv.shape[1] - self.ip_tokens
             k, v = (t.reshape(B, kv.shape[1], self.heads, -1).transpose(1, 2) for t in (kv[..., :inner], kv[..., inner:]))
             o = F.scaled_dot_product_attention(q, k[:, :, :nt], v[:, :, :nt])
-            if len(self.ip_segments) >= 2:
+            if self.ip_mask is not None:
+                mv, wd = self._ip_mask_level(B, N), self.ip_mask[3].to(o.dtype)
+                for a, (lo, hi) in enumerate(self._ip_rows(kv.shape[1])):
+                    o_a = F.scaled_dot_product_attention(q, k[:, :, lo:hi], v[:, :, lo:hi])
+                    o = o + (wd[a] * mv[:, a].to(o.dtype))[:, None, :, None] * o_a
+            elif len(self.ip_segments) >= 2:
                 wd = self.ip_weights.to(o.dtype)
                 for a, (lo, hi) in enumerate(self._ip_rows(kv.shape[1])):
                     o = o + wd[a] * F.scaled_dot_product_attention(q, k[:, :, lo:hi], v[:, :, lo:hi])
@@ -1288,6 +1320,20 @@ class UNet2DConditionModel(nn.Module):
                 else:
                     at.add_ip_adapter(to_k, to_v, e["tokens"], self.ip_weights[:len(entries)])
         self.ip_scales = [e["scale"] for e in entries]
+        if len(entries) == 1 and self.__dict__.get("ip_weights") is not None:
+            self.ip_weights[:1].fill_(entries[0]["scale"])     # read by the masked path alone (ip_mask_weights)
+
+    def ip_mask_weights(self):
+        """The fp32 device weights [A] the masked cross attentions read (section 33): the tensor of section 32, allocated here for a
+        single adapter as well -- the masked path reads its scale from the device at every adapter count.  Call it once outside a
+        graph capture; afterwards ``ip_scale`` / ``ip_scales`` keep it current."""
+        entries = self.__dict__.get("_ip_entries", ())
+        if not entries:
+            raise ValueError("no IP-Adapter is installed")
+        if self.__dict__.get("ip_weights") is None:
+            self.ip_weights = torch.zeros(IP_MAX_ADAPTERS, dtype=torch.float32, device=self.conv_in.weight.device)
+            self.ip_weights[:1].fill_(entries[0]["scale"])
+        return self.ip_weights[:len(entries)]
 
     def remove_ip_adapter(self, index=None):
         """remove every adapter, or the ``index``-th one (the others keep their order and scales)"""
@@ -1328,6 +1374,9 @@ class UNet2DConditionModel(nn.Module):
             e["scale"] = scale
         for a in self.ip_attentions():
             a.ip_scale = scale
+        if entries and self.__dict__.get("ip_weights") is not None:
+            with torch.no_grad():
+                self.ip_weights[:1].fill_(scale)
 
     @property
     def ip_scales(self):
@@ -1369,10 +1418,31 @@ class UNet2DConditionModel(nn.Module):
         return (2, e["proj"].proj.in_features) if e["kind"] == "base" else (3, e["proj"].proj_in.in_features)
 
     def forward(self, sample, timestep, encoder_hidden_states=None, added_cond_kwargs=None,
-                down_block_additional_residuals=None, mid_block_additional_residual=None, cross_kv=None, control_residuals=None, **_):
+                down_block_additional_residuals=None, mid_block_additional_residual=None, cross_kv=None, control_residuals=None, ip_masks=None, **_):
         """``control_residuals`` = (per-net lists of raw down residuals, per-net raw mid residuals, w f32 [B, N]): the hand-off of
         several ControlNets -- every skip and the mid-block output receive sum_n w[:, n] * r_n in ONE
-        ``ops.control_residuals`` launch, in place.  Mutually exclusive with the two ``*_additional_residual(s)`` keywords."""
+        ``ops.control_residuals`` launch, in place.  Mutually exclusive with the two ``*_additional_residual(s)`` keywords.
+        ``ip_masks`` = (m f32 [B, A, S], PH, PW): IP-Adapter attention masks -- per row and adapter the four
+        levels of ``ops.ip_mask_rows``; every cross attention multiplies adapter a's term at query row i by its level's m[b, a, i]."""
+        if ip_masks is not None:
+            m, PH, PW = ip_masks
+            A = len(self.ip_segments)
+            S = ops.ip_mask_layout(PH, PW)[1]
+            if not A:
+                raise ValueError("ip_masks without an installed IP-Adapter")
+            if not isinstance(m, torch.Tensor) or m.dtype != torch.float32 or tuple(m.shape) != (sample.shape[0], A, S):
+                raise ValueError(f"ip_masks: m must be f32 [{sample.shape[0]}, {A}, {S}] for {PH} x {PW} rows, got "
+                                 f"{tuple(getattr(m, 'shape', ()))} {getattr(m, 'dtype', None)}")
+            w = self.ip_mask_weights()
+            attns = self.ip_attentions()
+            for at in attns:
+                at.ip_mask = (m, int(PH), int(PW), w)
+            try:
+                return self.forward(sample, timestep, encoder_hidden_states, added_cond_kwargs, down_block_additional_residuals,
+                                    mid_block_additional_residual, cross_kv, control_residuals)
+            finally:
+                for at in attns:
+                    at.ip_mask = None
         if control_residuals is not None and (down_block_additional_residuals is not None or mid_block_additional_residual is not None):
             raise ValueError("control_residuals and down_block_additional_residuals / mid_block_additional_residual exclude each other")
         x = sample.to(self.dtype)

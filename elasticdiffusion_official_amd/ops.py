@@ -285,6 +285,62 @@ def assemble_rows_n(latent, idx, src_row, src_col, g_rows, h, w, g_off_y, g_off_
                                                        + K * h * w + (0 if low is None else 4 * low.numel())))
 
 
+IP_MASK_LEVELS = 4        # ed_ip_mask_rows: levels 0..3 of the 2 x 2-mean pyramid
+IP_MASK_MAX_ADAPTERS = 4
+
+
+def ip_mask_layout(PH, PW):
+    """[(offset, (PH >> L) * (PW >> L)) for L in 0..3] inside one row's [S] floats of ``ip_mask_rows``' buffer, and S"""
+    sizes = [(PH >> L) * (PW >> L) for L in range(IP_MASK_LEVELS)]
+    return [(sum(sizes[:L]), sizes[L]) for L in range(IP_MASK_LEVELS)], sum(sizes)
+
+
+def ip_mask_rows(masks, idx, src_row, src_col, h, w, g_off_y, g_off_x, win_y0, win_x0, Sh, Sw, v_off_y, v_off_x, PH, PW, copies,
+                 out=None):
+    """IP-Adapter attention masks of every row of one fused model batch (see ed_ip_mask_rows): ``masks`` f32
+    [B,A,H,W] on the device, the gather arguments of ``assemble_rows_n`` (``idx`` [K,h*w] / ``win_y0`` [V] may be None for a batch
+    without global / view rows) -> f32 [(K*copies+V)*B, A, S]: per row and adapter the level-0 frame [PH,PW] followed by its
+    2 x 2-mean levels 1..3 (``ip_mask_layout``).  One launch."""
+    if not isinstance(masks, torch.Tensor) or masks.dim() != 4 or not masks.is_cuda or masks.dtype != torch.float32:
+        _reject(f"ip_mask_rows: masks must be an f32 [B,A,H,W] tensor on the MI355X; no CPU fallback (got "
+                f"{tuple(getattr(masks, 'shape', ()))} {getattr(masks, 'dtype', None)})")
+    B, A, H, W = masks.shape
+    if not 1 <= A <= IP_MASK_MAX_ADAPTERS:
+        _reject(f"ip_mask_rows: 1 to {IP_MASK_MAX_ADAPTERS} adapters, got {A}")
+    if not isinstance(copies, int) or not 2 <= copies <= 1 + MAX_REGION_ROWS:
+        _reject(f"ip_mask_rows: copies must be an int in [2, {1 + MAX_REGION_ROWS}], got {copies!r}")
+    PH, PW = int(PH), int(PW)
+    if PH < 8 or PW < 8 or PH % 8 or PW % 8:
+        _reject(f"ip_mask_rows: the padded row size must be a multiple of 8 on both axes, got {PH} x {PW}")
+    K = 0 if idx is None else idx.shape[0]
+    V = 0 if win_y0 is None else win_y0.numel()
+    if K and (idx.shape[1] != h * w or src_row.numel() != 2 * h or src_col.numel() != 2 * w):
+        _reject(f"ip_mask_rows: idx [K,{h * w}], src_row [{2 * h}] and src_col [{2 * w}] expected, got {tuple(idx.shape)}, "
+                f"{src_row.numel()}, {src_col.numel()}")
+    if V and win_x0.numel() != V:
+        _reject(f"ip_mask_rows: win_y0 and win_x0 must hold one entry per view, got {V} and {win_x0.numel()}")
+    if (K and (g_off_y < 0 or g_off_x < 0 or g_off_y + h > PH or g_off_x + w > PW)) or \
+            (V and (v_off_y < 0 or v_off_x < 0 or v_off_y + Sh > PH or v_off_x + Sw > PW)):
+        _reject(f"ip_mask_rows: the picked frame ({h} x {w} at {g_off_y}, {g_off_x}) / the window ({Sh} x {Sw} at {v_off_y}, "
+                f"{v_off_x}) does not fit a {PH} x {PW} row")
+    S = ip_mask_layout(PH, PW)[1]
+    rows = (K * copies + V) * B
+    if out is None:
+        out = torch.empty(rows, A, S, device=masks.device, dtype=torch.float32)
+    elif tuple(out.shape) != (rows, A, S) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != masks.device:
+        _reject(f"ip_mask_rows: out must be a contiguous f32 [{rows},{A},{S}] tensor beside masks, got {tuple(out.shape)} {out.dtype}")
+    if rows == 0:
+        return out
+    _call("ed_ip_mask_rows", _dev(masks, torch.float32, "masks"), B, A, H, W, _opt(idx if K else None, torch.uint8, "idx"),
+          _opt(src_row if K else None, torch.int32, "src_row"), _opt(src_col if K else None, torch.int32, "src_col"), K,
+          h if K else 0, w if K else 0, g_off_y if K else 0, g_off_x if K else 0, _opt(win_y0 if V else None, torch.int32, "win_y0"),
+          _opt(win_x0 if V else None, torch.int32, "win_x0"), V, Sh if V else 0, Sw if V else 0, v_off_y if V else 0,
+          v_off_x if V else 0, PH, PW, copies, _dev(out, torch.float32, "out"), _stream())
+    # algorithmic bytes: every output float once, one fp32 read per gathered level-0 pixel, the picks
+    TIMER.note_work("ed_ip_mask_rows", nbytes=float(4 * out.numel() + 4 * (K + V) * B * A * PH * PW + K * h * w))
+    return out
+
+
 def _region_w(region_w, H, W, what, outputs=()):
     """``region_w`` f32 [P,H,W] on the device, 1 <= P <= 8, sharing no memory with the launch's outputs -> (pointer, P)"""
     if not isinstance(region_w, torch.Tensor) or region_w.dim() != 3 or tuple(region_w.shape[1:]) != (H, W) or \
@@ -1628,6 +1684,58 @@ def flash_attention_ipn(q, k, v, heads, n_text, n_image, w):
     _call("ed_flash_attention_ipn", q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _code(q, "q"), B, heads, Nq, n_text,
           len(n_image), ctypes.addressof(ni), hd, q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
           out.stride(0), out.stride(1), hd ** -0.5, w.data_ptr(), _stream())
+    return out
+
+
+def flash_attention_ipm_ok(head_dim, n_text, n_image):
+    """does ed_flash_attention_ipm take this shape?  ed_flash_attention_ipn's range (the mask changes one coefficient per row and
+    segment); models.Attention runs A + 1 attentions and A masked, weighted adds otherwise."""
+    return flash_attention_ipn_ok(head_dim, n_text, n_image)
+
+
+def flash_attention_ipm(q, k, v, heads, n_text, n_image, w, m):
+    """``flash_attention_ipn`` with IP-Adapter attention masks: ``m`` a float32 DEVICE tensor [B,A,Nq], or
+    [1,A,Nq] / [A,Nq] shared by the batch, unit last stride, any batch / adapter strides (a level of ``ip_mask_rows``' buffer is
+    such a view), read when the kernel runs ->
+    softmax(q k_t^T / 8) v_t + sum_a (w[a] m[b,a,i]) softmax(q k_a^T / 8) v_a, contiguous [B,Nq,H*64].  See ed_flash_attention_ipm."""
+    B, Nq, HD = q.shape
+    N = k.shape[1]
+    hd = HD // heads
+    n_text, n_image = int(n_text), tuple(int(n) for n in n_image)
+    A = len(n_image)
+    if HD != heads * hd or hd != 64 or k.shape != (B, N, HD) or v.shape != (B, N, HD):
+        _reject(f"flash_attention_ipm: head_dim must be 64 and shapes consistent (q {tuple(q.shape)}, k {tuple(k.shape)}, "
+                f"v {tuple(v.shape)}, heads {heads})")
+    if not flash_attention_ipm_ok(hd, n_text, n_image) or n_text + sum(n_image) != N:
+        _reject(f"flash_attention_ipm: needs 1 <= text keys <= {IP_MAX_TEXT_KEYS}, 1 to {IPN_MAX_ADAPTERS} adapters of >= 1 image keys "
+                f"each, <= {IP_MAX_IMAGE_KEYS} image keys together and text + image keys = {N} rows, got {n_text} and {n_image}")
+    if (not isinstance(w, torch.Tensor) or not w.is_cuda or w.dtype != torch.float32 or w.shape != (A,) or not w.is_contiguous()):
+        _reject(f"flash_attention_ipm: w must be a contiguous float32 tensor [{A}] on the MI355X (one weight per adapter)")
+    if isinstance(m, torch.Tensor) and m.dim() == 2:
+        m = m[None]
+    if (not isinstance(m, torch.Tensor) or not m.is_cuda or m.dtype != torch.float32 or m.dim() != 3 or m.shape[0] not in (1, B)
+            or tuple(m.shape[1:]) != (A, Nq) or (Nq > 1 and m.stride(2) != 1) or (A > 1 and m.stride(1) < Nq)
+            or (m.shape[0] > 1 and m.stride(0) < 0)):
+        _reject(f"flash_attention_ipm: m must be a float32 tensor [{B} or 1,{A},{Nq}] on the MI355X with unit last stride, got "
+                f"{tuple(getattr(m, 'shape', ()))} / {getattr(m, 'dtype', None)}")
+    for t, name in ((q, "q"), (k, "k"), (v, "v")):
+        if not t.is_cuda or t.dtype != q.dtype or t.dtype not in (torch.float16, torch.bfloat16) or t.stride(2) != 1:
+            _reject(f"flash_attention_ipm: {name} must be a 16-bit tensor on the MI355X with unit last stride; no CPU fallback")
+        if _LAUNCH["device"] is None:
+            _LAUNCH["device"] = t.device
+        elif _LAUNCH["device"] != t.device:
+            _reject(f"flash_attention_ipm: {name} lives on {t.device}, q on {_LAUNCH['device']}")
+    if w.device != q.device or m.device != q.device:
+        _reject(f"flash_attention_ipm: w lives on {w.device}, m on {m.device}, q on {q.device}")
+    m_sb = 0 if m.shape[0] == 1 else m.stride(0)
+    m_sa = max(m.stride(1), Nq) if A > 1 else Nq   # one adapter: the stride is never applied
+    out = torch.empty(B, Nq, HD, dtype=q.dtype, device=q.device)
+    TIMER.note_work("ed_flash_attention_ipm", flops=4.0 * B * heads * Nq * N * hd,
+                    nbytes=2.0 * q.element_size() * HD * B * (Nq + N) + 4.0 * m.shape[0] * A * Nq)
+    ni = (ctypes.c_int32 * A)(*n_image)   # read by the entry point before it returns
+    _call("ed_flash_attention_ipm", q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _code(q, "q"), B, heads, Nq, n_text,
+          A, ctypes.addressof(ni), hd, q.stride(0), q.stride(1), k.stride(0), k.stride(1), v.stride(0), v.stride(1),
+          out.stride(0), out.stride(1), hd ** -0.5, w.data_ptr(), m.data_ptr(), m_sb, m_sa, _stream())
     return out
 
 

@@ -455,6 +455,33 @@ def check_region_arguments(regions, height, width, scale=8, region_blur=0.0, in_
     return out, blur
 
 
+def check_ip_adapter_mask_arguments(n_adapters, ip_adapter_masks, height, width, scale=8):
+    """The argument rules of ``ip_adapter_masks`` (IP-Adapter attention masks), pure host code that runs before
+    anything is launched -> None without masks, else one entry per loaded adapter: None (no mask: all ones) or what
+    ``check_region_arguments`` makes of a region's mask -- ("box", (x0, y0, x1, y1)), ("pixel", picture), ("latent", array) -- read
+    through that function, so the accepted forms are ``regions``' forms.
+    ValueError: masks without a loaded adapter; a count other than the adapters'; a size that is neither the picture's nor the
+    latent's; a box that is empty or leaves the picture; any other kind of mask."""
+    if ip_adapter_masks is None:
+        return None
+    if not n_adapters:
+        raise ValueError("ip_adapter_masks given but no IP-Adapter is loaded")
+    if not isinstance(ip_adapter_masks, (list, tuple)) or len(ip_adapter_masks) != n_adapters:
+        n = len(ip_adapter_masks) if isinstance(ip_adapter_masks, (list, tuple)) else 1
+        raise ValueError(f"ip_adapter_masks must be a list with one entry per adapter (a mask or None): {n_adapters} adapter(s) "
+                         f"loaded, {n} mask(s) given")
+    out = []
+    for k, mask in enumerate(ip_adapter_masks):
+        if mask is None:
+            out.append(None)
+            continue
+        try:
+            out.append(check_region_arguments([("", mask)], height, width, scale)[0][0][1])
+        except ValueError as e:
+            raise ValueError(str(e).replace("regions[0]", f"ip_adapter_masks[{k}]")) from None
+    return out
+
+
 class _Plan:
     """Per-call geometry: host plans (geometry.py) + their int32 device tables + the pick sampler."""
 
@@ -478,13 +505,15 @@ class _ModelCall:
     ``t`` (0-d device tensor) with per-row text / pooled / ControlNet-condition rows.  Programs are generators that
     yield these and receive the model output rows (see ``_phase_steps``): the driver decides whether a call runs on its
     own (one image in flight) or fused with the calls of other images (``generate_latents_interleaved``)."""
-    __slots__ = ("rows", "t", "text", "pooled", "cond", "direct", "ctl")
+    __slots__ = ("rows", "t", "text", "pooled", "cond", "direct", "ctl", "ipm")
 
-    def __init__(self, rows, t, text, pooled, cond=None, direct=False, ctl=None):
+    def __init__(self, rows, t, text, pooled, cond=None, direct=False, ctl=None, ipm=None):
         self.rows, self.t, self.text, self.pooled, self.cond, self.direct = rows, t, text, pooled, cond, direct
         # Multi-ControlNet (section 31): (indices of the nets this call runs, f32 [n, len(indices)] per-row weights); ``cond``
         # then holds those nets' condition rows stacked along the channels
         self.ctl = ctl
+        # IP-Adapter attention masks (section 33): (f32 [n, A, S] per-row masks of ``ops.ip_mask_rows``, PH, PW) or None
+        self.ipm = ipm
 
 
 class _HostRng:
@@ -1192,12 +1221,15 @@ class ElasticDiffusion(nn.Module):
         ni = getattr(self.unet, "ip_tokens", 0)
         return txt[:, :txt.shape[1] - ni].contiguous() if ni else txt
 
-    def _forward_rows(self, x, t_dev, txt, pl, cond, text_kv=None, ctl=None):
+    def _forward_rows(self, x, t_dev, txt, pl, cond, text_kv=None, ctl=None, ipm=None):
         """ED:413-426 / EDC:476-518 for an arbitrary batch of d x d rows (this is what a hipGraph captures).  ``ctl`` = (active
         net indices, w f32 [rows, len(active)]): the Multi-ControlNet path -- ``cond`` holds the active
         nets' condition rows stacked along the channels, every active net returns its raw residuals and ONE
-        ``ops.control_residuals`` launch hands sum_n w[:, n] * r_n to the UNet."""
+        ``ops.control_residuals`` launch hands sum_n w[:, n] * r_n to the UNet.  ``ipm`` = (m f32 [rows, A, S], PH, PW): the rows'
+        IP-Adapter attention masks (section 33), handed to the UNet alone -- a ControlNet still sees text only."""
         kw, ckw = {}, {}
+        if ipm is not None:
+            kw["ip_masks"] = ipm
         if self.sd_version.startswith("XL"):
             ids = self._time_ids.to(txt.dtype).expand(x.shape[0], -1)
             kw["added_cond_kwargs"] = {"text_embeds": pl, "time_ids": ids}
@@ -1207,7 +1239,7 @@ class ElasticDiffusion(nn.Module):
         if cond is not None and ctl is not None:
             from . import models
             active, w = ctl
-            cn_kw = {k: v for k, v in kw.items() if k != "cross_kv"}
+            cn_kw = {k: v for k, v in kw.items() if k not in ("cross_kv", "ip_masks")}
             downs, mids = [], []
             for k, n in enumerate(active):
                 cn, nkw = self.controlnets[n], {}
@@ -1226,16 +1258,27 @@ class ElasticDiffusion(nn.Module):
                 sums = ops.control_residuals(None, [d + [m] for d, m in zip(downs, mids)], w)
                 kw["down_block_additional_residuals"], kw["mid_block_additional_residual"] = sums[:-1], sums[-1]
         elif cond is not None:
-            cn_kw = {k: v for k, v in kw.items() if k != "cross_kv"}
+            cn_kw = {k: v for k, v in kw.items() if k not in ("cross_kv", "ip_masks")}
             down, mid = self.controlnet(x, t_dev, encoder_hidden_states=self._text_part(txt), controlnet_cond=cond,
                                         conditioning_scale=self._cn_scale, guess_mode=False, return_dict=False, **cn_kw, **ckw)
             kw["down_block_additional_residuals"], kw["mid_block_additional_residual"] = down, mid
         return self.unet(x, t_dev, encoder_hidden_states=txt, **kw)["sample"].contiguous()
 
-    def _run_model(self, x_rows, t_dev, text, pooled, cond_rows=None, fresh_side=False, ctl=None):
+    def _run_model(self, x_rows, t_dev, text, pooled, cond_rows=None, fresh_side=False, ctl=None, ipm=None):
         """Rows are sharded across ranks (sharding.py); each rank's share runs as one (graph-replayed) forward.
         ``t_dev``: 0-d timestep shared by all rows, or one timestep per row (fused batches of several images).  ``ctl``
-        (``_ModelCall.ctl``): its per-row weights shard with the rows, like a per-row timestep."""
+        (``_ModelCall.ctl``): its per-row weights shard with the rows, like a per-row timestep.  ``ipm`` (``_ModelCall.ipm``): the
+        per-row mask buffer shards the same way."""
+        if ipm is not None:
+            per_row, active = t_dev.dim() != 0, None if ctl is None else ctl[0]
+
+            def fn(x, txt, pl, cond, *more):
+                more = list(more)
+                t = more.pop(0) if per_row else t_dev
+                c = None if active is None else (active, more.pop(0))
+                return self._runner(x, t, txt, pl, cond, fresh_side, ctl=c, ipm=(more.pop(0), ipm[1], ipm[2]))
+            return self.sharder.run(fn, x_rows, text, pooled, cond_rows, *((t_dev,) if per_row else ()),
+                                    *(() if ctl is None else (ctl[1],)), ipm[0])
         if ctl is not None:
             active, per_row = ctl[0], t_dev.dim() != 0
 
@@ -1250,7 +1293,8 @@ class ElasticDiffusion(nn.Module):
 
     # ---- one estimation phase (ED:1016-1035 or ED:1043-1056) ---------------------------------------
     def _phase_steps(self, P, x, ti, K, g, drop_p, emb, cond=None, direct=True, rrg_w=None, rrg_norm=0.0, frames=None,
-                     rescale=None, extras=None, multistep=None, keep_scores=False, region_w=None, step_noise=None, ctl=None):
+                     rescale=None, extras=None, multistep=None, keep_scores=False, region_w=None, step_noise=None, ctl=None,
+                     ip_masks=None):
         """Generator: pre-model glue -> ``yield _ModelCall`` (receives the model output rows) -> post-model glue;
         returns (prev, x0, info).  ``direct``: assemble straight into the hipGraph's static input (one image in flight,
         one rank); otherwise into a scratch batch the driver concatenates / the sharder slices.  ``rrg_w``: this is the
@@ -1267,7 +1311,10 @@ class ElasticDiffusion(nn.Module):
         plain launches; None launches what it always did.  ``step_noise`` (the step's c_n, section 29; None for a step that is not
         stochastic): the phase's latent-sized normal draw is made with the other host draws -- after the picks and the strip
         reseeds, where the reference's ``scheduler.step`` would draw -- and added by the step's own launch; with ``rrg_w`` the
-        reduced-resolution step's draw, whose result the reference discards, only advances the generator."""
+        reduced-resolution step's draw, whose result the reference discards, only advances the generator.  ``ip_masks`` (f32
+        [B,A,Hl,Wl]; IP-Adapter attention masks, section 33): one ``ops.ip_mask_rows`` launch beside the assemble launch forms the
+        per-row masks of this model call from the same picks and windows, and the ``_ModelCall`` carries them; None launches what it
+        always did."""
         ms_kw = {} if multistep is None else dict(multistep=multistep)
         B, C = x.shape[:2]
         CR = C if extras is None else C + extras[0].shape[1]  # channels of a model INPUT row
@@ -1297,8 +1344,12 @@ class ElasticDiffusion(nn.Module):
         direct = direct and P.one_batch and self.sharder.world_size == 1
         if P.one_batch:
             shape = (n_g + n_v, CR, P.gpad.PH, P.gpad.PW)
+            ipm_kw = {}
+            if ip_masks is not None and direct:   # (the key of the static input: the buffer's shape, known before it is filled)
+                S_m = ops.ip_mask_layout(P.gpad.PH, P.gpad.PW)[1]
+                ipm_kw = dict(ipm=(torch.empty(n_g + n_v, ip_masks.shape[1], S_m, device="meta"), P.gpad.PH, P.gpad.PW))
             rows = (self._runner.input_rows(shape, mdt, dev, None if cond is None else cond[K], *emb[K],
-                                            ctl=None if ctl is None else ctl[K]) if direct
+                                            ctl=None if ctl is None else ctl[K], **ipm_kw) if direct
                     else torch.empty(shape, device=dev, dtype=mdt))
             g_rows, v_rows = rows[:n_g], rows[n_g:]
         else:
@@ -1325,19 +1376,29 @@ class ElasticDiffusion(nn.Module):
         else:
             ops.pick_assemble(x, idx, P.src_row, P.src_col, g_rows, P.h, P.w, P.gpad.top, P.gpad.left, gframe, low)
             ops.gather_views(x, v_rows, P.win_y0, P.win_x0, P.views.Sh, P.views.Sw, P.vpad.top, P.vpad.left, vframe)
+        ipm = ipm_g = ipm_v = None
+        if ip_masks is not None:   # the rows' masks: the gather of the assemble launch applied to the masks, four levels, one launch
+            pick_a = (idx, P.src_row, P.src_col, P.h, P.w, P.gpad.top, P.gpad.left)
+            view_a = (P.win_y0, P.win_x0, P.views.Sh, P.views.Sw, P.vpad.top, P.vpad.left)
+            if P.one_batch:
+                ipm = (ops.ip_mask_rows(ip_masks, *pick_a, *view_a, P.gpad.PH, P.gpad.PW, copies), P.gpad.PH, P.gpad.PW)
+            else:
+                ipm_g = (ops.ip_mask_rows(ip_masks, *pick_a, None, None, 0, 0, 0, 0, P.gpad.PH, P.gpad.PW, copies), P.gpad.PH, P.gpad.PW)
+                ipm_v = (ops.ip_mask_rows(ip_masks, None, None, None, 0, 0, 0, 0, *view_a, P.vpad.PH, P.vpad.PW, copies),
+                         P.vpad.PH, P.vpad.PW)
         text, pooled = emb[K]
         t_dev = self._t_dev[ti]
         self.host_s["phase_total"] += time.perf_counter() - h0
         if P.one_batch:
             out = yield _ModelCall(rows, t_dev, text, pooled, None if cond is None else cond[K], direct,
-                                   None if ctl is None else ctl[K])
+                                   None if ctl is None else ctl[K], ipm)
             g_out, v_out = out[:n_g], out[n_g:]
         else:
             g_out = yield _ModelCall(g_rows, t_dev, text[:n_g].contiguous(), pooled[:n_g].contiguous(),
-                                     None if cond is None else cond[K][0], ctl=None if ctl is None else ctl[K][0])
+                                     None if cond is None else cond[K][0], ctl=None if ctl is None else ctl[K][0], ipm=ipm_g)
             g_out = g_out.clone()  # the two calls may share one graph output buffer when their shapes coincide
             v_out = yield _ModelCall(v_rows, t_dev, text[n_g:].contiguous(), pooled[n_g:].contiguous(),
-                                     None if cond is None else cond[K][1], ctl=None if ctl is None else ctl[K][1])
+                                     None if cond is None else cond[K][1], ctl=None if ctl is None else ctl[K][1], ipm=ipm_v)
         h0 = time.perf_counter()
         uncond_last = torch.empty(B, C, P.h, P.w, device=dev, dtype=torch.float32)
         low_dir = torch.empty(B, C, P.h, P.w, device=dev, dtype=torch.float32)
@@ -1433,7 +1494,8 @@ class ElasticDiffusion(nn.Module):
         try:
             call = next(program)
             while True:
-                call = program.send(self._run_model(call.rows, call.t, call.text, call.pooled, call.cond, ctl=call.ctl))
+                call = program.send(self._run_model(call.rows, call.t, call.text, call.pooled, call.cond, ctl=call.ctl,
+                                                    ipm=call.ipm))
         except StopIteration as stop:
             return stop.value
 
@@ -1787,22 +1849,42 @@ class ElasticDiffusion(nn.Module):
         H, W = P.Hl * s, P.Wl * s
         masks = torch.empty(len(regions), P.Hl, P.Wl, dtype=torch.uint8, device=dev)
         for k, (_, (kind, m), _) in enumerate(regions):
-            if kind == "latent":
-                t = torch.from_numpy(np.ascontiguousarray(m)) if isinstance(m, np.ndarray) else m
-                masks[k] = t.to(dev).reshape(P.Hl, P.Wl)
-                continue
-            if kind == "box":
-                u8 = torch.zeros(H, W, dtype=torch.uint8, device=dev)
-                u8[m[1]:m[3], m[0]:m[2]] = 255
-            else:
-                u8 = self._u8_image(m, 1, "region mask")
-                if isinstance(u8, np.ndarray):
-                    u8 = torch.from_numpy(np.ascontiguousarray(u8))
-                u8 = u8.to(dev).contiguous().view(H, W)
-            if region_blur > 0:
-                u8 = ops.gaussian_blur_u8(u8, region_blur)
-            masks[k] = ops.resize_u8(u8, (P.Hl, P.Wl), "bilinear")
+            masks[k] = self._latent_size_mask(S, kind, m, region_blur, "region mask")
         return ops.region_weights(masks, [w for _, _, w in regions])
+
+    def _latent_size_mask(self, S, kind, m, blur, what):
+        """one mask of ``check_region_arguments``' kinds -> uint8 [Hl,Wl] on the device (see ``_region_weights``)"""
+        P, s, dev = S.P, self.vae_scale_factor, self.device
+        H, W = P.Hl * s, P.Wl * s
+        if kind == "latent":
+            t = torch.from_numpy(np.ascontiguousarray(m)) if isinstance(m, np.ndarray) else m
+            return t.to(dev).reshape(P.Hl, P.Wl)
+        if kind == "box":
+            u8 = torch.zeros(H, W, dtype=torch.uint8, device=dev)
+            u8[m[1]:m[3], m[0]:m[2]] = 255
+        else:
+            u8 = self._u8_image(m, 1, what)
+            if isinstance(u8, np.ndarray):
+                u8 = torch.from_numpy(np.ascontiguousarray(u8))
+            u8 = u8.to(dev).contiguous().view(H, W)
+        if blur > 0:
+            u8 = ops.gaussian_blur_u8(u8, blur)
+        return ops.resize_u8(u8, (P.Hl, P.Wl), "bilinear")
+
+    def _ip_masks(self, S, entries, B):
+        """``check_ip_adapter_mask_arguments``' entries -> f32 [B,A,Hl,Wl] on the device, fp32(u8) / 255 rounded once, all ones for
+        an adapter without a mask: uploaded and reduced to the latent grid once per image, through ``regions``' path (section 33)."""
+        P = S.P
+        u8 = torch.full((len(entries), P.Hl, P.Wl), 255, dtype=torch.uint8, device=self.device)
+        for a, e in enumerate(entries):
+            if e is not None:
+                u8[a] = self._latent_size_mask(S, e[0], e[1], 0.0, "ip_adapter_masks")
+        if hasattr(self.unet, "ip_mask_weights"):   # the device weights of the masked path exist before any capture (a single adapter included)
+            self.unet.ip_mask_weights()
+        # fp32(u8) / 255 through a 256-entry table divided on the host: a device division by a Python scalar is a multiplication by
+        # its reciprocal, two roundings
+        lut = torch.from_numpy(np.arange(256, dtype=np.float32) / np.float32(255)).to(self.device)
+        return lut[u8.long()][None].expand(B, -1, -1, -1).contiguous()
 
     def _prompt_chunks(self, prompts, negative_prompts):
         """Chunk count the encoder needs for these prompts and negative prompts together, or None for an encoder that does not
@@ -1815,7 +1897,7 @@ class ElasticDiffusion(nn.Module):
     def _program(self, S, prompts, negative_prompts, condition_image=None, trace=None, progress=_identity_progress,
                  direct=True, frames=None, init_image=None, mask_image=None, mask_blur=0.0, mask_mode="binary",
                  min_chunks=None, ip_adapter_image=None, ip_adapter_image_embeds=None, score_maps=None, regions=None,
-                 region_blur=0.0, ip_adapter_negative_image_embeds=None):
+                 region_blur=0.0, ip_adapter_negative_image_embeds=None, ip_adapter_masks=None):
         """Generator: the denoising loop of ONE image (ED:981-1078), yielding ``_ModelCall``s; returns the final latent.
         All host RNG draws happen inside, in the reference's order.  ``init_image`` / ``mask_image``: image-to-image and
         inpainting -- the loop starts at timestep index ``S.t_start`` from the noised encoding of the
@@ -1881,6 +1963,8 @@ class ElasticDiffusion(nn.Module):
             emb = {K: self._embed_rows(K, P.views.V, un, co, pun, pco) for K in S.Ks}
         self.last_region_weights = region_w
         rg_kw = {} if region_w is None else dict(region_w=region_w)
+        if ip_adapter_masks is not None:   # ``check_ip_adapter_mask_arguments``' entries: every model call carries its rows' masks
+            rg_kw["ip_masks"] = self._ip_masks(S, ip_adapter_masks, B)
         cond = control_at = None
         if condition_image is not None:
             if self.controlnet is None:
@@ -1973,8 +2057,13 @@ class ElasticDiffusion(nn.Module):
                          progress=_identity_progress, condition_image=None, controlnet_conditioning_scale=1.0,
                          trace=None, guidance_rescale=0.0, init_image=None, strength=1.0, mask_image=None, *, mask_blur=0.0,
                          mask_mode="binary", min_chunks=None, ip_adapter_image=None, ip_adapter_image_embeds=None,
-                         ip_adapter_negative_image_embeds=None, score_pca=False, regions=None, region_blur=0.0, control_guidance_start=0.0, control_guidance_end=1.0):
-        """``condition_image`` / ``controlnet_conditioning_scale`` / ``control_guidance_start`` / ``control_guidance_end``
+                         ip_adapter_negative_image_embeds=None, score_pca=False, regions=None, region_blur=0.0, control_guidance_start=0.0, control_guidance_end=1.0,
+                         ip_adapter_masks=None):
+        """``ip_adapter_masks`` (keyword-only): one entry per loaded IP-Adapter -- None, an L PIL image / uint8
+        array at picture or latent size, or a box (x0, y0, x1, y1) in pixels, the forms of a region's mask -- that confines the
+        adapter's image prompt to a part of the picture: at every cross attention adapter a's term is multiplied per query row by
+        its mask, followed through the picks and view windows of each model row and averaged 2 x 2 per UNet level.
+        ``condition_image`` / ``controlnet_conditioning_scale`` / ``control_guidance_start`` / ``control_guidance_end``
         (diffusers 0.21.4's Multi-ControlNet keywords): with a pipeline built on a LIST of N ControlNets,
         ``condition_image`` is a list of N conditions and the other three are floats (applied to every net) or lists of N; net n
         acts with weight ``scale[n]`` on the executed timesteps i with start[n] <= i / T and (i + 1) / T <= end[n] and is not run on
@@ -2032,6 +2121,7 @@ class ElasticDiffusion(nn.Module):
                                                       self.unet.config.in_channels)
         check_regions_sampler(regions, getattr(self, "scheduler", None))
         self._check_ip_adapter(ip_adapter_image, ip_adapter_image_embeds, ip_adapter_negative_image_embeds)
+        ip_adapter_masks = check_ip_adapter_mask_arguments(len(self._ip_list()), ip_adapter_masks, height, width, self.vae_scale_factor)
         check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
         score_pca = check_score_pca_arguments(score_pca, self._score_channels())
         mask_blur = check_soft_inpaint_arguments(init_image, mask_image, mask_blur, mask_mode,
@@ -2046,7 +2136,7 @@ class ElasticDiffusion(nn.Module):
                                       init_image=init_image, mask_image=mask_image, mask_blur=mask_blur, mask_mode=mask_mode,
                                       min_chunks=min_chunks, ip_adapter_image=ip_adapter_image,
                                       ip_adapter_image_embeds=ip_adapter_image_embeds, ip_adapter_negative_image_embeds=ip_adapter_negative_image_embeds, score_maps=maps, regions=regions,
-                                      region_blur=region_blur))
+                                      region_blur=region_blur, ip_adapter_masks=ip_adapter_masks))
         self.last_score_pca = maps
         self.last_latents = x
         self.host_s["blocked_ahead_of_gpu"] = self._stager.waited
@@ -2064,7 +2154,7 @@ class ElasticDiffusion(nn.Module):
 
         ``jobs`` = list of dicts {prompts, negative_prompts="", seed, condition_image=None, init_image=None,
         mask_image=None, mask_blur=0.0, mask_mode="binary", ip_adapter_image=None, ip_adapter_image_embeds=None, score_pca=False,
-        regions=None, region_blur=0.0}
+        regions=None, region_blur=0.0, ip_adapter_masks=None}
         (``score_pca``: that job's maps, as ``generate_latents`` makes them, in ``job_score_pca[index]``); ``strength`` is a setting of the call like the other schedule parameters, and jobs with and without
         an init image may mix (at ``strength`` 1: below it every job needs one; on a 9-channel inpainting UNet every job carries
         both ``init_image`` and ``mask_image``).  Each job is one
@@ -2087,6 +2177,8 @@ class ElasticDiffusion(nn.Module):
         for job in jobs:
             self._check_ip_adapter(job.get("ip_adapter_image"), job.get("ip_adapter_image_embeds"),
                                    job.get("ip_adapter_negative_image_embeds"))
+        job_ip_masks = [check_ip_adapter_mask_arguments(len(self._ip_list()), job.get("ip_adapter_masks"), height, width,
+                                                        self.vae_scale_factor) for job in jobs]
         n_chunks = None
         job_regions = [check_region_arguments(job.get("regions"), height, width, self.vae_scale_factor, job.get("region_blur", 0.0),
                                               self.unet.config.in_channels) for job in jobs]
@@ -2140,7 +2232,7 @@ class ElasticDiffusion(nn.Module):
                                  ip_adapter_image_embeds=job.get("ip_adapter_image_embeds"),
                                  ip_adapter_negative_image_embeds=job.get("ip_adapter_negative_image_embeds"),
                                  score_maps=self.job_score_pca.get(j),
-                                 regions=job_regions[j][0], region_blur=job_regions[j][1])
+                                 regions=job_regions[j][0], region_blur=job_regions[j][1], ip_adapter_masks=job_ip_masks[j])
             with rng:
                 call = next(prog)
             live.append([j, prog, rng, call])
@@ -2165,7 +2257,7 @@ class ElasticDiffusion(nn.Module):
                     sizes = [c.rows.shape[0] for c in calls]
                     if len(calls) == 1:
                         c = calls[0]
-                        outs = [self._run_model(c.rows, c.t, c.text, c.pooled, c.cond, fresh_side=True, ctl=c.ctl)]
+                        outs = [self._run_model(c.rows, c.t, c.text, c.pooled, c.cond, fresh_side=True, ctl=c.ctl, ipm=c.ipm)]
                     else:
                         rows = torch.cat([c.rows for c in calls])
                         t = torch.cat([c.t.reshape(1).expand(n) for c, n in zip(calls, sizes)])
@@ -2173,7 +2265,12 @@ class ElasticDiffusion(nn.Module):
                         pooled = torch.cat([c.pooled for c in calls])
                         cond = None if calls[0].cond is None else torch.cat([c.cond for c in calls])
                         ctl = None if calls[0].ctl is None else (calls[0].ctl[0], torch.cat([c.ctl[1] for c in calls]))
-                        outs = self._run_model(rows, t, text, pooled, cond, fresh_side=True, ctl=ctl).split(sizes)
+                        ipm = None
+                        if any(c.ipm is not None for c in calls):   # a job without masks contributes all-ones rows
+                            like = next(c.ipm for c in calls if c.ipm is not None)
+                            ipm = (torch.cat([c.ipm[0] if c.ipm is not None else like[0].new_ones((n,) + tuple(like[0].shape[1:]))
+                                              for c, n in zip(calls, sizes)]), like[1], like[2])
+                        outs = self._run_model(rows, t, text, pooled, cond, fresh_side=True, ctl=ctl, ipm=ipm).split(sizes)
                     self.ticks += 1
                     for ent, out in zip(ents, outs):
                         j, prog, rng = ent[0], ent[1], ent[2]
@@ -2353,7 +2450,7 @@ class ElasticDiffusion(nn.Module):
                        strength=1.0, mask_image=None, mask_blur=0.0, mask_mode="binary", composite=False,
                        ip_adapter_image=None, ip_adapter_image_embeds=None, ip_adapter_negative_image_embeds=None, score_pca=False,
                        regions=None, region_blur=0.0,
-                       control_guidance_start=0.0, control_guidance_end=1.0):
+                       control_guidance_start=0.0, control_guidance_end=1.0, ip_adapter_masks=None):
         """ED:953-965 signature (ControlNet keywords of EDC:1120-1134 are keyword-only here), then ``guidance_rescale``
         (diffusers' keyword) and, keyword-only, ``init_image`` / ``strength`` / ``mask_image`` / ``mask_blur`` / ``mask_mode``
         (see ``generate_latents``) and ``composite``: paste every decoded picture over the 8-bit init picture through the
@@ -2363,10 +2460,12 @@ class ElasticDiffusion(nn.Module):
         ``score_pca``: the PCA maps of ``generate_latents``, the first sample's enlarged by the VAE factor with Pillow's BILINEAR bytes
         on the device, in ``image_log`` as {"pca_cls_dir": {i: PIL}, "pca_uncond": {i: PIL}} (the script's pictures and names).
         ``regions`` / ``region_blur``: regional prompts (see ``generate_latents``).
+        ``ip_adapter_masks``: one attention mask per loaded IP-Adapter (see ``generate_latents``).
         Returns ``(images, image_log)``; images are PIL by default, a float tensor with ``output_type='pt'``."""
         check_region_arguments(regions, height, width, self.vae_scale_factor, region_blur, self.unet.config.in_channels)
         check_regions_sampler(regions, getattr(self, "scheduler", None))
         self._check_ip_adapter(ip_adapter_image, ip_adapter_image_embeds, ip_adapter_negative_image_embeds)
+        check_ip_adapter_mask_arguments(len(self._ip_list()), ip_adapter_masks, height, width, self.vae_scale_factor)
         check_img2img_arguments(num_inference_steps, init_image, strength, mask_image)
         check_soft_inpaint_arguments(init_image, mask_image, mask_blur, mask_mode, composite, output_type, grid,
                                      latent_size=(height // self.vae_scale_factor, width // self.vae_scale_factor))
@@ -2378,7 +2477,8 @@ class ElasticDiffusion(nn.Module):
                                   strength=strength, mask_image=mask_image, mask_blur=mask_blur, mask_mode=mask_mode,
                                   ip_adapter_image=ip_adapter_image, ip_adapter_image_embeds=ip_adapter_image_embeds, ip_adapter_negative_image_embeds=ip_adapter_negative_image_embeds,
                                   score_pca=score_pca, regions=regions, region_blur=region_blur,
-                                  control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end)
+                                  control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end,
+                                  ip_adapter_masks=ip_adapter_masks)
         dec = self.tiled_decode if tiled_decoder else self.decode_latents
         image_log = self._image_log(dec, guidance_scale, guidance_rescale) if self.verbose else {}  # ED:1092-1118 (before the final decode)
         if score_pca:
@@ -2603,7 +2703,7 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
                        output_type="pil", init_image=None, strength=1.0, mask_image=None, mask_blur=0.0, mask_mode="binary",
                        composite=False, ip_adapter_image=None, ip_adapter_image_embeds=None, ip_adapter_negative_image_embeds=None,
                        score_pca=False, regions=None,
-                       region_blur=0.0, control_guidance_start=0.0, control_guidance_end=1.0):
+                       region_blur=0.0, control_guidance_start=0.0, control_guidance_end=1.0, ip_adapter_masks=None):
         check_region_arguments(regions, height, width, self.vae_scale_factor, region_blur, self.unet.config.in_channels)
         check_regions_sampler(regions, getattr(self, "scheduler", None))
         self._check_ip_adapter(ip_adapter_image, ip_adapter_image_embeds, ip_adapter_negative_image_embeds)
@@ -2629,4 +2729,5 @@ class ElasticDiffusionControlNet(ElasticDiffusion):
                                       mask_image=mask_image, mask_blur=mask_blur, mask_mode=mask_mode, composite=composite,
                                       ip_adapter_image=ip_adapter_image, ip_adapter_image_embeds=ip_adapter_image_embeds, ip_adapter_negative_image_embeds=ip_adapter_negative_image_embeds,
                                       score_pca=score_pca, regions=regions, region_blur=region_blur,
-                                      control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end)
+                                      control_guidance_start=control_guidance_start, control_guidance_end=control_guidance_end,
+                                      ip_adapter_masks=ip_adapter_masks)

@@ -622,6 +622,38 @@ int ed_flash_attention_ipn(const void* q, const void* k, const void* v, void* ou
                            int64_t v_sn, int64_t o_sb, int64_t o_sn, float scale, const float* w, void* stream);
 
 /*
+ * IP-Adapter attention masks (additions, still ABI v13).
+ *
+ * ed_flash_attention_ipm -- ed_flash_attention_ipn with a factor per query row and adapter on the image term:
+ *       out = softmax(q k_t^T scale) v_t + sum_{a < A} (w[a] * m[b, a, i]) * softmax(q k_a^T scale) v_a      (i: the query row)
+ *   ed_flash_attention_ipn's argument list, then m, a DEVICE pointer to fp32 read when the kernel runs -- element (b, a, i) at
+ *   m + b * m_sb + a * m_sa + i -- and its batch and adapter strides in floats.  m_sb may be 0 (one mask for the whole batch);
+ *   m 4-byte aligned, m_sb >= 0, m_sa >= Nq.  Range and every other condition as ed_flash_attention_ipn; anything else, a NULL or
+ *   misaligned m or m_sa < Nq returns hipErrorInvalidValue before any launch.  The kernel is ed_flash_attention_ipn's with the
+ *   segment coefficient of a row c_a = fl(fl(w[a] * m[b, a, i]) * inv_a); m is read for i < Nq only.  m == 1 gives
+ *   ed_flash_attention_ipn's output bit for bit; m == 0, or every w[a] = 0, gives ed_flash_attention(v_path 8) on the text rows.
+ *
+ * ed_ip_mask_rows -- the masks every row of a fused model batch reads, all four levels, in one launch.  masks f32 [B, A, H, W]
+ *   (values in [0, 1] at latent resolution), 1 <= A <= 4; the gather arguments are ed_assemble_rows_n's (idx .. g_off_x for the
+ *   K * copies * B global rows, win_y0 .. v_off_x for the V * B view rows) with ONE padded row size PH x PW, both multiples of 8,
+ *   for both parts.  m f32 [(K * copies + V) * B, A, S], S = sum_{L < 4} (PH >> L)(PW >> L), rows in the model batch's order,
+ *   level L at offset sum_{l < L} (PH >> l)(PW >> l).  Level 0 is what ed_assemble_rows_n writes into its extra channels from
+ *   extra = masks with pad_value = 0 and fp32 rows: the picked source pixel's value for a global row, the window's for a view row,
+ *   0 on pad strips and outside the picture.  Level L + 1 is the 2 x 2 mean 0.25f * ((l[2y,2x] + l[2y,2x+1]) + (l[2y+1,2x] +
+ *   l[2y+1,2x+1])), every operation rounded in fp32 in that association.  hipErrorInvalidValue before any launch: a NULL masks / m
+ *   (or gather table of a part that has rows), A outside 1..4, copies outside 2..9, PH or PW not a multiple of 8, a picked frame
+ *   or a window that does not fit the row.
+ */
+int ed_flash_attention_ipm(const void* q, const void* k, const void* v, void* out, int dtype, int B, int H, int Nq, int Nt, int A,
+                           const int* ni, int head_dim, int64_t q_sb, int64_t q_sn, int64_t k_sb, int64_t k_sn, int64_t v_sb,
+                           int64_t v_sn, int64_t o_sb, int64_t o_sn, float scale, const float* w, const float* m, int64_t m_sb,
+                           int64_t m_sa, void* stream);
+int ed_ip_mask_rows(const float* masks, int B, int A, int H, int W, const uint8_t* idx, const int32_t* src_row,
+                    const int32_t* src_col, int K, int h, int w, int g_off_y, int g_off_x, const int32_t* win_y0,
+                    const int32_t* win_x0, int V, int Sh, int Sw, int v_off_y, int v_off_x, int PH, int PW, int copies, float* m,
+                    void* stream);
+
+/*
  * ed_groupnorm_f32 -- GroupNorm (+SiLU) of an fp32 NCHW activation: the VAE's normalisation layers (AutoencoderKL inside
  * ED:270 decode / ED:350 encode; fp32 like the reference keeps it, ED:328).  HW % 4 == 0.  Two launches: partial sums over
  * 64 K-element chunks of every (sample, group), then an apply pass whose blocks combine their group's partials in double.
