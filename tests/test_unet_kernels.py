@@ -767,7 +767,8 @@ def test_linear_hip(dtype, M, K, N, any_grid, tile_rows):
 @pytest.mark.parametrize("B,H,W,Cin,N", [(2, 12, 20, 64, 200), (3, 16, 16, 128, 320), (1, 32, 32, 320, 320), (2, 8, 8, 1280, 640), (5, 7, 9, 192, 72)])
 def test_conv3x3_nhwc(dtype, B, H, W, Cin, N, any_grid, tile_rows):
     """ed_conv3x3_nhwc vs F.conv2d in fp32 (+ bias, + per-sample channel bias, + residual): image borders, batch seams inside a
-    256-row tile (B H W not a multiple of 256), 1..20 K tiles per tap, partial column blocks; bit-identical over launches."""
+    256-row tile (B H W not a multiple of 256), 1, 2, 3, 5 and 20 K tiles per tap (Cin = 64 ... 1280; 15 and 40 -- Cin = 960 and
+    2560 -- and images of 1 x 1 to 2 x 2 run in tests/test_gemm_adversarial_gpu.py), partial column blocks; bit-identical over launches."""
     from elasticdiffusion_official_amd import ops
     cl = torch.channels_last
     g = torch.Generator().manual_seed(B * H + Cin)
